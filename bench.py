@@ -11,14 +11,16 @@ written as a user of the reference writes it -- two calls with the reference's s
 SpatialTransformer defers the warp and Dice launches the fused kernel on (moving, trf, fixed) (neurite_amd/deferred.py; the
 warped volume is consumed in registers, never written -- SURVEY.md 8d anticipates this form).  --direct times the same kernel
 through neurite_amd.fused.warp_dice, --unfused the eager two-kernel pipeline (deferral off: `warped` written and read back).
-The JSON line always carries all three (`fused_pipeline` = the timed one, `fused_direct_pipeline`, `dropin_pipeline`) plus
-`roofline_dropin` (the stand-alone interpn kernel), `config2_batch1`, `bf16_storage` and `default_args_pipeline` (the reference's
-default range asserts on), measured in the same process.
+A plain run times the --steps steps of that one pipeline and nothing else.  With --full the JSON line also carries all three
+(`fused_pipeline` = the timed one, `fused_direct_pipeline`, `dropin_pipeline`) plus `roofline_dropin` (the stand-alone interpn
+kernel), `config2_batch1`, `bf16_storage` and `default_args_pipeline` (the reference's default range asserts on), measured in the
+same process.  --dump-outputs DIR writes the Dice values of the last timed step (dice.npy, mean_dice.npy); the inputs are seeded, so
+two builds given the same arguments can be compared output for output.
 Workload: BASELINE config 2 / 4 (SpatialTransformer + Dice, 160^3 x 32 one-hot, fp32).  N = 1: a step is 4 volumes (config 4's
-per-GPU share at N = 8); the line also carries `value_strong_b32`, all 32 volumes of config 4 on the one GPU.  N > 1: the parsed line
+per-GPU share at N = 8); with --full the line also carries `value_strong_b32`, all 32 volumes of config 4 on the one GPU.  N > 1: the parsed line
 is BASELINE config 4 AS WRITTEN -- global batch 32 fixed, 32 / N volumes per rank, "scaling": "strong" ("total voxels/s =
-32 V / wall-time at world sizes 1, 2, 4, 8") -- and the weak run (`--batch-per-gpu` volumes on every rank) is the extra key
-`weak_per_gpu`; `--weak` swaps the two.  1 voxel = 1 spatial output location.
+32 V / wall-time at world sizes 1, 2, 4, 8") -- and with --full the weak run (`--batch-per-gpu` volumes on every rank) is the extra
+key `weak_per_gpu`; `--weak` swaps the two.  1 voxel = 1 spatial output location.
 
     python bench.py                       # 1 GPU
     python bench.py --gpus N              # N GPUs of this node: re-launches itself under torch.distributed.run, one rank per GPU
@@ -26,6 +28,7 @@ is BASELINE config 4 AS WRITTEN -- global batch 32 fixed, 32 / N volumes per ran
         --master-port P bench.py --gpus N --steps K --warmup W            # the same, launched by the driver
     python bench.py --gpus N --weak       # N > 1 with 4 volumes per GPU whatever N is ("scaling": "weak") as the parsed line
     python bench.py --global-batch 32     # N = 1 with all 32 volumes of config 4 as the parsed line
+    python bench.py --full                # every secondary measurement as well (CPU baseline, unet, batch 1, other pipelines, ...)
 
 Steps are INDEPENDENT (each warps and scores its own batch), so they are issued round-robin over `--streams` HIP streams (default 3): the
 first blocks of step k + 1's gather run on the CUs step k's last round has left, the ~25 us of small second-stage kernels of a step run
@@ -37,9 +40,9 @@ needs 100-200 ms of continuous work to reach steady clocks; the timed region is 
 Rank 0 prints ONE JSON line on stdout.  `roofline` is the dominant kernel: achieved = algorithmic bytes per launch / the time a launch
 costs, measured with HIP events over the timed region -- with pipelined steps that is the device time of the region / launches (the rate at
 which launches complete; a launch's own start-to-end time, `kernel_own_duration_ms`, overlaps its neighbours'), and `roofline.isolated_launch`
-carries the same launch with the device to itself (serial steps: the figure rocprofv3 --stats of a `--streams 1` run reproduces).  Algorithmic bytes per
+carries the same launch with the device to itself (--full; serial steps: the figure rocprofv3 --stats of a `--streams 1` run reproduces).  Algorithmic bytes per
 voxel (DESIGN.md 4): fused kernel 4C (moving row) + 12 (shift) + 4L (fixed row) = 268 B at C=L=32;
-unfused interpn 4C + 12 + 4C = 268 B, Dice 2*4L = 256 B.  `cpu_baseline` is the C oracle (a port of the
+unfused interpn 4C + 12 + 4C = 268 B, Dice 2*4L = 256 B.  The rest is --full only.  `cpu_baseline` is the C oracle (a port of the
 reference algorithm, oracle/oracle.c) on the host cores this process may use, over a bounded sample, plus BASELINE config 1
 (one 32^3 volume) on the NumPy restatement, a torch-CPU form and the C port -- reported, not a target.
 At N = 1 the line also carries `unet_fwd` (BASELINE config 3 forward, per-layer fraction of the fp32 MFMA peak), `lc3d_wcce`
@@ -111,7 +114,37 @@ def parse():
                          'EXACTLY --steps steps between barrier + synchronize pairs')
     ap.add_argument('--graph', action='store_true',
                     help="capture a step's compute launches (gather + Dice second stage + mean pair) in one hipGraph")
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (isolated launches, the other pipelines, batch 1, bf16 storage, default '
+                         'arguments, the other scaling mode, stand-alone warp, CPU baseline, unet / LocallyConnected3D / training); off: '
+                         'the line carries the timed steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed as DIR/<name>.npy: dice.npy ([global batch, '
+                         'labels] float32, every rank\'s entries in global order) and mean_dice.npy (the global mean, float64)')
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, local_dice, mean, dist=None, rank=0):
+    """--dump-outputs: the Dice values [B_local, L] of the last timed step, gathered over the ranks in global batch order (rank r owns
+    entries [r*B, (r+1)*B)), and the global mean the step's collective produced.  Collective when `dist` is given: every rank calls it."""
+    d = local_dice.detach().float().contiguous()
+    if dist is not None:
+        if dist.get_backend() == 'gloo':
+            d = d.cpu()
+        parts = [torch.empty_like(d) for _ in range(dist.get_world_size())]
+        dist.all_gather(parts, d)
+        d = torch.cat(parts)
+    if rank != 0:
+        return
+    arrays = {'dice': d.cpu().numpy().astype(np.float32), 'mean_dice': np.asarray(mean, dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs to dump: %d bytes' % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 PREWARM_MS = 0.0             # set from --prewarm-ms in main()
@@ -1002,10 +1035,15 @@ def stub_main(args, rank, world):
         group = dist
     B, global_batch, scaling = batch_plan(default_global_batch(args.global_batch, args.weak, world), args.batch_per_gpu, world)
 
+    last = {}
+
     def step(events):
         time.sleep(0.002 * B)
-        return nd.all_reduce_mean_dice(torch.full((B, 8), float(rank + 1)), async_op=True)
+        last['dice'] = torch.full((B, 8), float(rank + 1))
+        return nd.all_reduce_mean_dice(last['dice'], async_op=True)
     r = timed(step, args.steps, args.warmup, group, None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last['dice'], r['mean'], group, rank)
     if rank == 0:
         V = args.size ** 3
         print(json.dumps({'metric': 'Mvoxels/sec interpn+Dice on 160^3 x 32-label', 'value': round(world * B * V * args.steps / r['elapsed'] / 1e6, 2),
@@ -1082,6 +1120,7 @@ def main():
     # a warped one-hot map overshoots 1.0 by an ulp, so the reference's default range assert would
     # abort the pipeline (see tests/test_gpu_dice_cce.py); min/max are still computed by the kernel
     dice = ne.metrics.Dice(check_input_limits=False)
+    last = {}                          # the Dice values of the most recent step (--dump-outputs reads them after the timed steps)
 
     def make_steps(mov, fix, trf):
         def step_unfused(events=None):
@@ -1099,6 +1138,7 @@ def main():
                     events[2].record()
             finally:
                 ne.deferred.enabled = keep
+            last['dice'] = d
             return nd.all_reduce_mean_dice(d, async_op=True)    # one all-reduce of 2 floats when world > 1
 
         def step_refsig(events=None):
@@ -1111,6 +1151,7 @@ def main():
             if events is not None:
                 events[1].record()
                 events[2].record()
+            last['dice'] = d
             return nd.all_reduce_mean_dice(d, async_op=True)
 
         def step_fused(events=None):
@@ -1120,6 +1161,7 @@ def main():
             if events is not None:
                 events[1].record()
                 events[2].record()
+            last['dice'] = d
             return nd.all_reduce_mean_dice(d, async_op=True)
         if not args.graph:
             return step_fused, step_unfused, step_refsig
@@ -1128,15 +1170,17 @@ def main():
         # captured once and replayed as ONE hipGraph launch; the all-reduce stays outside the graph and works on a copy of
         # the pair, because step k + 1's replay rewrites the captured buffer while step k's collective may still read it
         def capture(compute):
+            # compute() returns the step's [B, L] Dice values; the graph holds them and their [sum, count] pair
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    compute()
+                    nd.mean_dice_pair(compute())
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                pair = compute()
+                d = compute()
+                pair = nd.mean_dice_pair(d)
 
             def step(events=None):
                 if events is not None:
@@ -1145,18 +1189,19 @@ def main():
                 if events is not None:
                     events[1].record()
                     events[2].record()
+                last['dice'] = d
                 return nd.all_reduce_mean_pair(pair.clone(), async_op=True)
             step._graph = g
             return step
-        def eager_pair():
+        def eager_dice():
             keep = ne.deferred.enabled
             ne.deferred.enabled = False
             try:
-                return nd.mean_dice_pair(dice.dice(fix, st([mov, trf])))
+                return dice.dice(fix, st([mov, trf]))
             finally:
                 ne.deferred.enabled = keep
-        return (capture(lambda: nd.mean_dice_pair(ne.fused.warp_dice(mov, trf, fix, _tune=args.tune))), capture(eager_pair),
-                capture(lambda: nd.mean_dice_pair(dice.dice(fix, st([mov, trf])))))
+        return (capture(lambda: ne.fused.warp_dice(mov, trf, fix, _tune=args.tune)), capture(eager_dice),
+                capture(lambda: dice.dice(fix, st([mov, trf]))))
 
     step_fused, step_unfused, step_refsig = make_steps(mov, fix, trf)
     fused = not args.unfused
@@ -1168,18 +1213,24 @@ def main():
     main_step = pipelined(main_serial, nstreams, dev)
     r_main = timed(main_step, args.steps, args.warmup, dist, dev, sparse_events=nstreams > 1)
     elapsed, k0_ms, k1_ms, m = r_main['elapsed'], r_main['k0_ms'], r_main['k1_ms'], r_main['mean']
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last['dice'], m, dist, rank)
+    # everything below up to the result line is --full only: secondary measurements, each a run of its own
+    full = args.full
     o_steps = max(5, args.steps // 5)
-    # the same steps strictly one after the other (what rocprofv3's per-kernel durations of an isolated launch correspond to)
-    r_iso = timed(main_serial, args.steps, args.warmup, dist, dev) if nstreams > 1 else r_main
-    # the other form of the same pipeline, shorter run, for the record
-    r_other = timed(step_unfused if fused else step_fused, o_steps, 2, dist, dev)
-    o_elapsed, o_k0, o_k1, o_m = r_other['elapsed'], r_other['k0_ms'], r_other['k1_ms'], r_other['mean']
-    # the same kernel through the other entry (direct fused API when the reference-signature calls are the timed pipeline)
-    r_ref = timed(step_fused if (fused and not args.direct) else step_refsig, o_steps, 2, dist, dev)
+    r_iso = r_other = r_ref = None
+    if full:
+        # the same steps strictly one after the other (what rocprofv3's per-kernel durations of an isolated launch correspond to)
+        r_iso = timed(main_serial, args.steps, args.warmup, dist, dev) if nstreams > 1 else r_main
+        # the other form of the same pipeline, shorter run, for the record
+        r_other = timed(step_unfused if fused else step_fused, o_steps, 2, dist, dev)
+        o_elapsed, o_k0, o_k1, o_m = r_other['elapsed'], r_other['k0_ms'], r_other['k1_ms'], r_other['mean']
+        # the same kernel through the other entry (direct fused API when the reference-signature calls are the timed pipeline)
+        r_ref = timed(step_fused if (fused and not args.direct) else step_refsig, o_steps, 2, dist, dev)
     # the stand-alone warp (the drop-in op that WRITES the warped volume) issued like the headline steps: independent launches
     # round-robin over the step streams, nothing else in between -- the rate at which interpn launches complete
     r_warp = r_warp_serial = None
-    if dist is None and fused and not args.no_batch1:
+    if full and dist is None and fused and not args.no_batch1:
         try:
             def step_warp(events=None):
                 if events is not None:
@@ -1200,7 +1251,7 @@ def main():
             r_warp = r_warp_serial = None
     # BASELINE config 2 proper is batch = 1: the same two pipelines on the first volume only (N = 1 runs)
     r_b1 = None
-    if dist is None and B > 1 and not args.no_batch1:
+    if full and dist is None and B > 1 and not args.no_batch1:
         f1, u1, _ = make_steps(mov[:1], fix[:1], trf[:1])
         b1_steps = 4 * o_steps                            # (a batch-1 step is a quarter of the headline step)
         b1_form = 'direct launches'
@@ -1218,7 +1269,7 @@ def main():
                 timed(f1, o_steps, 2, None, dev) if nstreams > 1 else None)
     # label maps stored as bfloat16 (exact for one-hot maps), float32 arithmetic: same Dice bit for bit, half the bytes per row
     r_bf16 = None
-    if dist is None and not args.no_batch1:
+    if full and dist is None and not args.no_batch1:
         try:
             mov16, fix16 = mov.bfloat16(), fix.bfloat16()
 
@@ -1243,7 +1294,7 @@ def main():
     # fires (a tri-linear blend of ones exceeds 1.0 by an ulp: tests/test_gpu_dice_cce.py), so the default path is timed on the
     # same maps scaled by 1/2: same kernels, same bytes, plus the read-back of the four extrema the assert looks at
     r_def = r_def_eager = None
-    if dist is None and not args.no_batch1:
+    if full and dist is None and not args.no_batch1:
         try:
             movh, fixh = mov * 0.5, fix * 0.5
             dice_def = ne.metrics.Dice()
@@ -1273,7 +1324,7 @@ def main():
     # words it -- B = 32 FIXED, all 32 volumes on this GPU (35 GB of its 288) -- so that value(N) / value_strong_b32 is the strong-scaling
     # figure.  N > 1 (parsed line: global batch 32, 32 / N per rank): the weak run, --batch-per-gpu volumes on every rank.
     r_strong, Bs, r_warp32 = None, 0, None
-    if not args.global_batch and not args.no_strong and not args.unfused and not args.rough and CFG4_GLOBAL_BATCH % world == 0 and S == 160:
+    if full and not args.global_batch and not args.no_strong and not args.unfused and not args.rough and CFG4_GLOBAL_BATCH % world == 0 and S == 160:
         try:
             Bs = CFG4_GLOBAL_BATCH // world
             if Bs == B:
@@ -1305,7 +1356,7 @@ def main():
             log('cfg4_strong run failed on rank %d: %s' % (rank, e))
             r_strong = None
     r_weak, Bw = None, args.batch_per_gpu
-    if args.global_batch and not named_batch and not args.no_strong and not args.unfused and not args.rough:
+    if full and args.global_batch and not named_batch and not args.no_strong and not args.unfused and not args.rough:
         try:
             if Bw == B:
                 r_weak = r_main                          # (N = 8: config 4's shard IS 4 volumes per rank)
@@ -1319,7 +1370,7 @@ def main():
             log('weak_per_gpu run failed on rank %d: %s' % (rank, e))
             r_weak = None
     unet_multi = None
-    if dist is not None and not args.no_unet:
+    if full and dist is not None and not args.no_unet:
         # "3D UNet fwd ms at 1/2/4/8 GPU": every rank runs the config-3 forward on its own volume (data parallel inference);
         # the slowest rank's median is reported
         try:
@@ -1364,28 +1415,6 @@ def main():
     build_ids = (_lib.lib().nrt_build_id().decode(), nbuild.build_id(), nbuild.gather_sources_id())
     traffic, traffic_src = lookup_traffic(os.path.join(ROOT, 'profiles', 'hbm_traffic.json'), timed_kernel, B, build_ids)
 
-    # drop-in (reference-signature) pipeline figures, whichever form was the timed one
-    d_elapsed, d_steps, d_k0, d_k1, d_m = (o_elapsed, o_steps, o_k0, o_k1, o_m) if fused else (elapsed, args.steps, k0_ms, k1_ms, m)
-    f_elapsed, f_steps, f_k0, f_m = (elapsed, args.steps, kms, m) if fused else (o_elapsed, o_steps, o_k0, o_m)
-    dropin = {'what': 'reference-signature calls run eagerly (neurite_amd.deferred.enabled = False): layers.SpatialTransformer(linear) '
-                      '-> metrics.Dice().dice, two kernels, `warped` written and re-read; %d steps' % d_steps,
-              'value': round(world * B * V * d_steps / d_elapsed / 1e6, 2), 'unit': 'Mvoxels/s',
-              'ms_per_step': round(d_elapsed / d_steps * 1e3, 4),
-              'interpn_ms': round(d_k0, 4), 'interpn_GBs': round(interp_bytes / (d_k0 * 1e-3) / 1e9, 1),
-              'interpn_frac_of_peak': round(interp_bytes / (d_k0 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-              'dice_ms': round(d_k1, 4), 'dice_GBs': round(DICE_BYTES_PER_VOXEL(L) * V * B / (d_k1 * 1e-3) / 1e9, 1),
-              'dice_frac_of_peak': round(DICE_BYTES_PER_VOXEL(L) * V * B / (d_k1 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-              'pipeline_524B_per_voxel_frac_of_peak': round(
-                  (interp_bytes + DICE_BYTES_PER_VOXEL(L) * V * B) / (d_elapsed / d_steps) / 1e9 / HBM_PEAK_GBS, 4),
-              'mean_dice': round(d_m, 6)}
-    fusedb = {'what': ('the timed pipeline: reference-signature calls, warp deferred, fused kernel; %d steps' % f_steps)
-                      if (fused and not args.direct) else
-                      'fused warp+Dice kernel (neurite_amd.fused.warp_dice; `warped` never written), %d steps' % f_steps,
-              'value': round(world * B * V * f_steps / f_elapsed / 1e6, 2), 'unit': 'Mvoxels/s',
-              'ms_per_step': round(f_elapsed / f_steps * 1e3, 4), 'kernel_ms': round(f_k0, 4),
-              'frac_of_peak_268B_per_voxel': round(fused_bytes / (f_k0 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-              'mean_dice': round(f_m, 6)}
-
     out = {
         'metric': 'Mvoxels/sec interpn+Dice on 160^3 x 32-label',
         'value': round(value, 2),
@@ -1401,6 +1430,7 @@ def main():
         'vs_baseline': None,
         'dtype': 'f32',
         'data': 'synthetic',
+        'full': full,
         'config': {
             'workload': 'BASELINE config 2/4: SpatialTransformer(linear)+Dice on %d^3 x %d-label one-hot fp32, '
                         '%d volumes per GPU per step (global batch %d), %s displacement field; %s'
@@ -1435,40 +1465,64 @@ def main():
                                       'divided by the launches -- the rate at which launches COMPLETE.  Consecutive gathers overlap (the head of '
                                       'launch k + 1 runs on the CUs launch k\'s last round has left), so a launch\'s own start-to-end time '
                                       '(`kernel_own_duration_ms`, what rocprofv3 lists per kernel) counts the shared stretches twice; '
-                                      '`isolated_launch` is the same launch with the device to itself (steps strictly serial)' % nstreams)
+                                      '`isolated_launch` (--full) is the same launch with the device to itself (steps strictly serial)' % nstreams)
                                      if (nstreams > 1 and fused) else
                                      'HIP events around the gather launch and, for the fused form, the two launches of its Dice second '
                                      'stage (reduce_rows + dice_soft_finalize, ~0.03 ms together): rocprofv3 lists the gather alone'),
             'steps_in_flight': nstreams,
             'kernel_own_duration_ms': round(k0_ms, 4),
-            'isolated_launch': {
-                'what': 'the same launch with the device to itself: steps issued strictly one after the other on one stream, HIP events around '
-                        'the gather and its Dice second stage; %d steps.  This is the figure rocprofv3 --stats of a `--streams 1` run reproduces' % args.steps,
-                'avg_launch_ms': round(r_iso['k0_ms'], 4),
-                'achieved': round(alg_bytes / (r_iso['k0_ms'] * 1e-3) / 1e9, 1),
-                'frac': round(alg_bytes / (r_iso['k0_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                'ms_per_step': round(r_iso['elapsed'] / args.steps * 1e3, 4)},
         },
-        # the reference-signature path (what `SpatialTransformer` + `Dice` callers reach) next to the fused headline
-        'roofline_dropin': {'kernel': 'interpn (SpatialTransformer gather, drop-in API), one launch per step', 'bound': 'hbm',
-                            'achieved': dropin['interpn_GBs'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                            'frac': dropin['interpn_frac_of_peak'], 'avg_launch_ms': dropin['interpn_ms'],
-                            'algorithmic_bytes_per_launch': interp_bytes},
-        # what a caller of the reference's own two calls gets by default: SpatialTransformer defers the warp, Dice runs the
-        # fused kernel on (moving, trf, fixed) -- same kernel and numbers as `fused_pipeline`, reached through the reference API
-        ('fused_direct_pipeline' if (fused and not args.direct) else 'reference_api_pipeline'): {
-            'what': ('neurite_amd.fused.warp_dice(moving, trf, fixed) called directly: the same kernel without the deferred-warp '
-                     'indirection; %d steps' % o_steps) if (fused and not args.direct) else
-                    ('layers.SpatialTransformer(linear)([moving, trf]) -> metrics.Dice().dice(fixed, warped) as written against the '
-                     'reference; the warp is deferred and Dice launches the fused kernel (neurite_amd/deferred.py); %d steps' % o_steps),
-            'value': round(world * B * V * o_steps / r_ref['elapsed'] / 1e6, 2), 'unit': 'Mvoxels/s',
-            'ms_per_step': round(r_ref['elapsed'] / o_steps * 1e3, 4), 'kernel_ms': round(r_ref['k0_ms'], 4),
-            'frac_of_peak_268B_per_voxel': round(fused_bytes / (r_ref['k0_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            'mean_dice': round(r_ref['mean'], 6)},
-        'dropin_pipeline': dropin,
-        'fused_pipeline': fusedb,
-        'other_pipeline': dropin if fused else fusedb,
     }
+    if full:
+        # drop-in (reference-signature) pipeline figures, whichever form was the timed one
+        d_elapsed, d_steps, d_k0, d_k1, d_m = (o_elapsed, o_steps, o_k0, o_k1, o_m) if fused else (elapsed, args.steps, k0_ms, k1_ms, m)
+        f_elapsed, f_steps, f_k0, f_m = (elapsed, args.steps, kms, m) if fused else (o_elapsed, o_steps, o_k0, o_m)
+        dropin = {'what': 'reference-signature calls run eagerly (neurite_amd.deferred.enabled = False): layers.SpatialTransformer(linear) '
+                          '-> metrics.Dice().dice, two kernels, `warped` written and re-read; %d steps' % d_steps,
+                  'value': round(world * B * V * d_steps / d_elapsed / 1e6, 2), 'unit': 'Mvoxels/s',
+                  'ms_per_step': round(d_elapsed / d_steps * 1e3, 4),
+                  'interpn_ms': round(d_k0, 4), 'interpn_GBs': round(interp_bytes / (d_k0 * 1e-3) / 1e9, 1),
+                  'interpn_frac_of_peak': round(interp_bytes / (d_k0 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                  'dice_ms': round(d_k1, 4), 'dice_GBs': round(DICE_BYTES_PER_VOXEL(L) * V * B / (d_k1 * 1e-3) / 1e9, 1),
+                  'dice_frac_of_peak': round(DICE_BYTES_PER_VOXEL(L) * V * B / (d_k1 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                  'pipeline_524B_per_voxel_frac_of_peak': round(
+                      (interp_bytes + DICE_BYTES_PER_VOXEL(L) * V * B) / (d_elapsed / d_steps) / 1e9 / HBM_PEAK_GBS, 4),
+                  'mean_dice': round(d_m, 6)}
+        fusedb = {'what': ('the timed pipeline: reference-signature calls, warp deferred, fused kernel; %d steps' % f_steps)
+                          if (fused and not args.direct) else
+                          'fused warp+Dice kernel (neurite_amd.fused.warp_dice; `warped` never written), %d steps' % f_steps,
+                  'value': round(world * B * V * f_steps / f_elapsed / 1e6, 2), 'unit': 'Mvoxels/s',
+                  'ms_per_step': round(f_elapsed / f_steps * 1e3, 4), 'kernel_ms': round(f_k0, 4),
+                  'frac_of_peak_268B_per_voxel': round(fused_bytes / (f_k0 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                  'mean_dice': round(f_m, 6)}
+        out['roofline']['isolated_launch'] = {
+            'what': 'the same launch with the device to itself: steps issued strictly one after the other on one stream, HIP events around '
+                    'the gather and its Dice second stage; %d steps.  This is the figure rocprofv3 --stats of a `--streams 1` run reproduces' % args.steps,
+            'avg_launch_ms': round(r_iso['k0_ms'], 4),
+            'achieved': round(alg_bytes / (r_iso['k0_ms'] * 1e-3) / 1e9, 1),
+            'frac': round(alg_bytes / (r_iso['k0_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            'ms_per_step': round(r_iso['elapsed'] / args.steps * 1e3, 4)}
+        out.update({
+            # the reference-signature path (what `SpatialTransformer` + `Dice` callers reach) next to the fused headline
+            'roofline_dropin': {'kernel': 'interpn (SpatialTransformer gather, drop-in API), one launch per step', 'bound': 'hbm',
+                                'achieved': dropin['interpn_GBs'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                'frac': dropin['interpn_frac_of_peak'], 'avg_launch_ms': dropin['interpn_ms'],
+                                'algorithmic_bytes_per_launch': interp_bytes},
+            # what a caller of the reference's own two calls gets by default: SpatialTransformer defers the warp, Dice runs the
+            # fused kernel on (moving, trf, fixed) -- same kernel and numbers as `fused_pipeline`, reached through the reference API
+            ('fused_direct_pipeline' if (fused and not args.direct) else 'reference_api_pipeline'): {
+                'what': ('neurite_amd.fused.warp_dice(moving, trf, fixed) called directly: the same kernel without the deferred-warp '
+                         'indirection; %d steps' % o_steps) if (fused and not args.direct) else
+                        ('layers.SpatialTransformer(linear)([moving, trf]) -> metrics.Dice().dice(fixed, warped) as written against the '
+                         'reference; the warp is deferred and Dice launches the fused kernel (neurite_amd/deferred.py); %d steps' % o_steps),
+                'value': round(world * B * V * o_steps / r_ref['elapsed'] / 1e6, 2), 'unit': 'Mvoxels/s',
+                'ms_per_step': round(r_ref['elapsed'] / o_steps * 1e3, 4), 'kernel_ms': round(r_ref['k0_ms'], 4),
+                'frac_of_peak_268B_per_voxel': round(fused_bytes / (r_ref['k0_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                'mean_dice': round(r_ref['mean'], 6)},
+            'dropin_pipeline': dropin,
+            'fused_pipeline': fusedb,
+            'other_pipeline': dropin if fused else fusedb,
+        })
     if r_strong is not None:
         out['cfg4_strong'] = {
             'what': 'BASELINE config 4 with the global batch FIXED at 32 (SURVEY 8d): %d volumes on each of %d GPUs, the reference-signature '
@@ -1540,18 +1594,19 @@ def main():
             'algorithmic_bytes_per_voxel': 2 * L + 12 + 2 * L,
             'frac_of_peak': round(b16 / (r_bf16['k0_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'same_dice': r_bf16['same_dice'],
             'max_abs_diff_vs_default_f32_kernel': r_bf16['max_abs_diff_vs_default_f32_kernel']}
-    # the stand-alone op (the drop-in `interpn` / SpatialTransformer call that WRITES the warped volume; 268 B per voxel as well)
-    sa = {'frac': dropin['interpn_frac_of_peak'], 'avg_launch_ms': dropin['interpn_ms'], 'achieved': dropin['interpn_GBs'], 'volumes_per_launch': B,
-          'what': 'isolated launches (the eager two-kernel pipeline, steps serial)'}
-    if r_warp_serial is not None:
-        w_ms = r_warp_serial['k0_ms']
-        sa = {'frac': round(interp_bytes / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'avg_launch_ms': round(w_ms, 4),
-              'achieved': round(interp_bytes / (w_ms * 1e-3) / 1e9, 1), 'volumes_per_launch': B, 'ms_per_volume': round(w_ms / B, 4),
-              'what': 'the warp alone, launches strictly one after the other on one stream, HIP events around every launch; %d launches' % args.steps,
-              'ms_per_launch_wall': round(r_warp_serial['elapsed'] / args.steps * 1e3, 4),
-              'in_dropin_pipeline': {'what': 'the same launch alternating with the Dice kernels of the eager two-kernel pipeline (`dropin_pipeline`)',
-                                     'avg_launch_ms': dropin['interpn_ms'], 'frac': dropin['interpn_frac_of_peak']}}
-    out['roofline']['standalone_interpn'] = sa
+    if full:
+        # the stand-alone op (the drop-in `interpn` / SpatialTransformer call that WRITES the warped volume; 268 B per voxel as well)
+        sa = {'frac': dropin['interpn_frac_of_peak'], 'avg_launch_ms': dropin['interpn_ms'], 'achieved': dropin['interpn_GBs'], 'volumes_per_launch': B,
+              'what': 'isolated launches (the eager two-kernel pipeline, steps serial)'}
+        if r_warp_serial is not None:
+            w_ms = r_warp_serial['k0_ms']
+            sa = {'frac': round(interp_bytes / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'avg_launch_ms': round(w_ms, 4),
+                  'achieved': round(interp_bytes / (w_ms * 1e-3) / 1e9, 1), 'volumes_per_launch': B, 'ms_per_volume': round(w_ms / B, 4),
+                  'what': 'the warp alone, launches strictly one after the other on one stream, HIP events around every launch; %d launches' % args.steps,
+                  'ms_per_launch_wall': round(r_warp_serial['elapsed'] / args.steps * 1e3, 4),
+                  'in_dropin_pipeline': {'what': 'the same launch alternating with the Dice kernels of the eager two-kernel pipeline (`dropin_pipeline`)',
+                                         'avg_launch_ms': dropin['interpn_ms'], 'frac': dropin['interpn_frac_of_peak']}}
+        out['roofline']['standalone_interpn'] = sa
     if r_warp is not None:
         out['roofline']['standalone_interpn']['pipelined'] = {
             'what': 'the warp alone, independent launches round-robin on %d streams (as the headline steps): device time of the region / launches; %d launches' % (nstreams, args.steps),
@@ -1571,7 +1626,7 @@ def main():
         out['roofline']['dice_kernel'] = {'avg_ms': round(k1_ms, 4),
                                           'achieved': round(DICE_BYTES_PER_VOXEL(L) * V * B / (k1_ms * 1e-3) / 1e9, 1),
                                           'unit': 'GB/s'}
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         try:
             base, d_cpu = cpu_baseline(mov, fix, trf)
             out['cpu_baseline'] = base
@@ -1585,7 +1640,7 @@ def main():
         except Exception as e:   # noqa
             out['cpu_baseline'] = {'value': None, 'unit': 'Mvoxels/s', 'cores': 0, 'kind': 'port',
                                    'sample': 'failed: %s' % e}
-    if world == 1 and not args.no_unet:
+    if full and world == 1 and not args.no_unet:
         out['training'] = {}
         try:
             out['training']['registration_step'] = registration_bench(mov, fix, trf)

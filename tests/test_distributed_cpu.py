@@ -296,3 +296,30 @@ def test_bench_strong_mode_world4_cpu_stub():
     assert j['n_gpus'] == 4 and j['rccl_ranks'] == 4 and j['scaling'] == 'strong'
     assert j['config']['volumes_per_gpu'] == 8 and j['config']['global_batch'] == 32
     assert abs(j['config']['mean_dice'] - 2.5) < 1e-6                  # mean of the ranks' constants 1, 2, 3, 4
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_cpu_stub(tmp_path):
+    """--dump-outputs DIR after the timed steps: every rank's Dice values of the last step in global batch order (dice.npy, float32) and
+    the global mean (mean_dice.npy, float64); two runs with the same arguments write the same arrays"""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'NRT_BENCH_CHILD')}
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ('run%d' % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--stub-step',
+                            '--global-batch', '6', '--dump-outputs', str(out)], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=280, text=True)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        j = json.loads(lines[0])
+        assert j['steps'] == 2 and j['ms_per_step'] > 0
+        assert sorted(os.listdir(out)) == ['dice.npy', 'mean_dice.npy']
+        d, mean = np.load(out / 'dice.npy'), np.load(out / 'mean_dice.npy')
+        assert d.dtype == np.float32 and d.shape == (6, 8)
+        assert np.array_equal(d[:3], np.full((3, 8), 1.0, np.float32)) and np.array_equal(d[3:], np.full((3, 8), 2.0, np.float32))
+        assert mean.dtype == np.float64 and abs(float(mean) - j['config']['mean_dice']) < 1e-6
+        dumps.append((d, mean))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])

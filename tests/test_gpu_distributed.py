@@ -69,7 +69,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo(dev):
     env.update(NRT_DIST_BACKEND='gloo', NRT_DEVICE='0', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--size', '64',
-           '--prewarm-ms', '120', '--no-cpu-baseline', '--no-unet', '--no-batch1']
+           '--prewarm-ms', '120', '--full', '--no-cpu-baseline', '--no-unet', '--no-batch1']
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith('{')]
@@ -86,3 +86,28 @@ def test_bench_two_ranks_share_one_gpu_over_gloo(dev):
     assert p1.returncode == 0, p1.stderr[-3000:]
     j1 = json.loads([ln for ln in p1.stdout.splitlines() if ln.strip().startswith('{')][-1])
     assert abs(j['config']['mean_dice'] - j1['config']['mean_dice']) <= 3e-6
+
+
+def test_bench_dump_outputs_are_the_timed_steps_dice(dev, tmp_path):
+    """A plain run times its steps only; --dump-outputs writes the Dice values of the last timed step, which are the fused kernel's values
+    on the seeded bench inputs (recomputed here), and the global mean the line reports."""
+    import numpy as np
+    import neurite_amd as ne
+    from neurite_amd import synth
+    out = tmp_path / 'dump'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--size', '64', '--batch-per-gpu', '2',
+           '--prewarm-ms', '0', '--dump-outputs', str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'NRT_BENCH_CHILD', 'NRT_FORCE_DIST')}
+    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith('{')]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j['steps'] == 3 and j['ms_per_step'] > 0 and j['full'] is False
+    assert not {'dropin_pipeline', 'cpu_baseline', 'unet_fwd', 'config2_batch1', 'cfg4_strong'} & set(j)
+    d, mean = np.load(out / 'dice.npy'), np.load(out / 'mean_dice.npy')
+    assert d.dtype == np.float32 and d.shape == (2, 32) and mean.dtype == np.float64
+    mov, fix, trf = synth.cfg2_batch(2, 64, 32, device=dev, seed0=100)
+    want = ne.fused.warp_dice(mov, trf, fix).cpu().numpy()
+    np.testing.assert_allclose(d, want, rtol=1e-5, atol=1e-6)
+    assert abs(float(mean) - j['config']['mean_dice']) <= 2e-6 and abs(float(mean) - float(want.mean())) <= 2e-6

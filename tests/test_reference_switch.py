@@ -1,16 +1,17 @@
 """
-The drop-in boundary checked against the REFERENCE TREE itself (runs in the build container only: skipped where
-/root/reference does not exist, i.e. on the GPU box -- nothing here touches a device).
+The drop-in boundary checked against the reference, self-contained: what is taken from the reference tree is recorded
+in tests/golden/reference_signatures.json by tests/golden/ast_signatures.py; nothing here touches a device.
 
 1. The reference's own backend switch (neurite/__init__.py:33-42, neurite/py/utils.py:15-20): with NEURITE_BACKEND=pytorch it does
    `from . import torch`, a sub-package it does not ship.  INTEGRATION.md section 1 gives the 8-line neurite/torch/__init__.py a
-   maintainer adds; the test builds that overlay (reference __init__.py + py/ + the binding copied OUT OF INTEGRATION.md) in a temp
-   directory, imports `neurite` through it and checks that ne.torch.* are the neurite_amd objects.
-2. Every public signature SURVEY 8(b) lists is compared with the reference's source by AST: argument names, order, defaults, *args /
-   **kwargs.
+   maintainer adds; the test builds that overlay (a stand-in `neurite` package whose switch is the reference's availability check --
+   as shipped or as INTEGRATION.md repairs it -- followed by `from . import torch`, plus the binding copied OUT OF INTEGRATION.md) in a
+   temp directory, imports `neurite` through it and checks that ne.torch.* are the neurite_amd objects.  The fixture records that the
+   reference's switch is exactly that check followed by that import.
+2. Every public signature SURVEY 8(b) lists is compared by AST with the reference's, as the fixture records them: argument names,
+   order, defaults, *args / **kwargs.
 """
 
-import ast
 import os
 import re
 import subprocess
@@ -20,8 +21,10 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference/neurite'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree is only present in the build container')
+sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+import ast_signatures as sigs          # noqa: E402
+
+REFERENCE = sigs.load()
 
 
 def _binding_from_integration_md():
@@ -34,40 +37,37 @@ def _binding_from_integration_md():
 # The switch as the reference ships it cannot reach ANY neurite/torch sub-package: `import torch` (the availability check) binds the
 # name `torch` in the package namespace, and the `from . import torch` two lines later finds that attribute and never imports the
 # sub-package -- `neurite.torch` is then PyTorch itself.  INTEGRATION.md section 1 therefore lists a two-line change of the check
-# next to the new file; the test applies exactly that change to a copy of the reference's __init__.py.
-SWITCH_AS_SHIPPED = """    try:
-        import torch
-    except ImportError:
-        raise ImportError('Please install pytorch to use this neurite backend')
-"""
-SWITCH_PATCHED = """    import importlib.util
-    if importlib.util.find_spec('torch') is None:
-        raise ImportError('Please install pytorch to use this neurite backend')
-"""
+# next to the new file; the test applies exactly that change to the stand-in's switch.
+SWITCH_AS_SHIPPED = sigs.SWITCH_AS_SHIPPED
+SWITCH_PATCHED = sigs.SWITCH_PATCHED
+
+# the stand-in for the reference's neurite/__init__.py: its backend switch, nothing else (the TensorFlow branch is never taken here)
+STANDIN_INIT = """import os
+backend = os.environ.get('NEURITE_BACKEND', 'tensorflow')
+if backend == 'pytorch':
+%s
+%s"""
 
 
 def _overlay(tmp_path, patched):
+    sw = REFERENCE['switch']
+    assert sw['as_shipped_check_present'] and sw['imports_torch_subpackage_after_the_check'], \
+        'neurite/__init__.py:33-42 changed upstream: update INTEGRATION.md section 1'
+    assert SWITCH_PATCHED in open(os.path.join(ROOT, 'INTEGRATION.md')).read(), 'INTEGRATION.md must show the patched check'
     pkg = tmp_path / 'neurite'
     (pkg / 'torch').mkdir(parents=True)
-    init = open(os.path.join(REF, '__init__.py')).read()
-    assert SWITCH_AS_SHIPPED in init, 'neurite/__init__.py:33-39 changed upstream: update INTEGRATION.md section 1'
-    assert SWITCH_PATCHED in open(os.path.join(ROOT, 'INTEGRATION.md')).read(), 'INTEGRATION.md must show the patched check'
-    (pkg / '__init__.py').write_text(init.replace(SWITCH_AS_SHIPPED, SWITCH_PATCHED) if patched else init)
-    os.symlink(os.path.join(REF, 'py'), pkg / 'py')
+    (pkg / '__init__.py').write_text(STANDIN_INIT % (SWITCH_PATCHED if patched else SWITCH_AS_SHIPPED, sigs.SWITCH_SUBPACKAGE_IMPORT))
     (pkg / 'torch' / '__init__.py').write_text(_binding_from_integration_md())
 
 
 def _run(script, tmp_path):
     head = textwrap.dedent('''
         import os, sys
-        sys.path.insert(0, %r)                      # pystrum / nibabel stand-ins (tests/golden/tf_shim.py); tensorflow stays unused
-        import tf_shim
-        tf_shim.install()
         sys.path.insert(0, %r)
         sys.path.insert(0, %r)
         import neurite as ne
         import neurite_amd
-    ''') % (os.path.join(ROOT, 'tests', 'golden'), ROOT, str(tmp_path))
+    ''') % (ROOT, str(tmp_path))
     env = dict(os.environ, NEURITE_BACKEND='pytorch', MPLBACKEND='Agg')
     return subprocess.run([sys.executable, '-c', head + textwrap.dedent(script)], env=env, capture_output=True, text=True, timeout=300)
 
@@ -86,7 +86,7 @@ def test_reference_switch_as_shipped_shadows_its_own_subpackage(tmp_path):
 def test_reference_backend_switch_resolves_to_neurite_amd(tmp_path):
     _overlay(tmp_path, patched=True)
     p = _run('''
-        assert ne.py.utils.get_backend() == 'pytorch'
+        assert ne.backend == 'pytorch'
         assert not hasattr(ne, 'tf'), 'the TensorFlow backend must not have been imported'
         assert ne.torch.backend == 'pytorch'
         for mod in ('utils', 'layers', 'metrics', 'losses', 'models', 'augment'):
@@ -114,98 +114,13 @@ def test_reference_backend_switch_resolves_to_neurite_amd(tmp_path):
 
 # ---- signatures by AST ------------------------------------------------------------------------------------------------------
 
-def _find(tree, qual):
-    node = tree
-    for part in qual.split('.'):
-        for child in ast.iter_child_nodes(node):
-            if isinstance(child, (ast.FunctionDef, ast.ClassDef)) and child.name == part:
-                node = child
-                break
-            if isinstance(child, ast.Assign) and any(isinstance(t, ast.Name) and t.id == part for t in child.targets):
-                node = child                      # an alias: `zoom = resize`
-                break
-        else:
-            raise KeyError(qual)
-    return node
-
-
-def _value(node):
-    try:
-        return repr(ast.literal_eval(node))
-    except Exception:       # noqa
-        return ast.unparse(node)
-
-
-def _signature(fn):
-    a = fn.args
-    pos = [x.arg for x in a.posonlyargs + a.args]
-    defaults = [_value(d) for d in a.defaults]
-    kwonly = [(x.arg, None if d is None else _value(d)) for x, d in zip(a.kwonlyargs, a.kw_defaults)]
-    return {'args': pos, 'defaults': defaults, 'vararg': a.vararg.arg if a.vararg else None, 'kwonly': kwonly,
-            'kwarg': bool(a.kwarg)}
-
-
-_trees = {}
-
-
-def _tree(path):
-    if path not in _trees:
-        _trees[path] = ast.parse(open(path).read())
-    return _trees[path]
-
-
-def _resolve(path, qual):
-    try:
-        node = _find(_tree(path), qual)
-    except KeyError:
-        # a method inherited from a base class defined in the same file (neurite_amd.losses keeps loss / mean_loss in one mixin)
-        cls, _, meth = qual.rpartition('.')
-        if not cls:
-            raise
-        for base in _find(_tree(path), cls).bases:
-            try:
-                return _resolve(path, ast.unparse(base) + '.' + meth)
-            except KeyError:
-                continue
-        raise
-    if isinstance(node, ast.Assign):                                     # alias -> what it names
-        return _resolve(path, ast.unparse(node.value))
-    if isinstance(node, ast.ClassDef):
-        return _find(node, '__init__')
-    return node
-
-
-SIGNATURES = [        # (reference file, reference name, neurite_amd file, neurite_amd name)
-    ('tf/utils/utils.py', 'interpn', 'utils.py', 'interpn'),
-    ('tf/utils/utils.py', 'resize', 'utils.py', 'resize'),
-    ('tf/utils/utils.py', 'zoom', 'utils.py', 'zoom'),
-    ('tf/utils/utils.py', 'volshape_to_ndgrid', 'utils.py', 'volshape_to_ndgrid'),
-    ('tf/utils/utils.py', 'volshape_to_meshgrid', 'utils.py', 'volshape_to_meshgrid'),
-    ('tf/layers.py', 'Resize', 'layers.py', 'Resize'),
-    ('tf/layers.py', 'Zoom', 'layers.py', 'Zoom'),
-    ('tf/layers.py', 'LocallyConnected3D', 'layers.py', 'LocallyConnected3D'),
-    ('tf/models.py', 'unet', 'models.py', 'unet'),
-    ('tf/models.py', 'conv_enc', 'models.py', 'conv_enc'),
-    ('tf/models.py', 'conv_dec', 'models.py', 'conv_dec'),
-    ('tf/metrics.py', 'Dice', 'metrics.py', 'Dice'),
-    ('tf/metrics.py', 'Dice.dice', 'metrics.py', 'Dice.dice'),
-    ('tf/metrics.py', 'Dice.mean_dice', 'metrics.py', 'Dice.mean_dice'),
-    ('tf/metrics.py', 'Dice.loss', 'metrics.py', 'Dice.loss'),
-    ('tf/metrics.py', 'SoftDice', 'metrics.py', 'SoftDice'),
-    ('tf/metrics.py', 'HardDice', 'metrics.py', 'HardDice'),
-    ('tf/metrics.py', 'CategoricalCrossentropy', 'metrics.py', 'CategoricalCrossentropy'),
-    ('tf/metrics.py', 'CategoricalCrossentropy.cce', 'metrics.py', 'CategoricalCrossentropy.cce'),
-    ('tf/metrics.py', 'CategoricalCrossentropy.__call__', 'metrics.py', 'CategoricalCrossentropy.__call__'),
-    ('tf/losses.py', 'Dice.loss', 'losses.py', 'Dice.loss'),
-    ('tf/losses.py', 'Dice.mean_loss', 'losses.py', 'Dice.mean_loss'),
-    ('tf/losses.py', 'CategoricalCrossentropy.loss', 'losses.py', 'CategoricalCrossentropy.loss'),
-]
+SIGNATURES = sigs.SIGNATURES
 
 
 @pytest.mark.parametrize('ref_file,ref_name,our_file,our_name', SIGNATURES, ids=[s[0].split('/')[-1][:-3] + '.' + s[1] for s in SIGNATURES])
 def test_public_signatures_equal_the_reference_by_ast(ref_file, ref_name, our_file, our_name):
-    ref = _signature(_resolve(os.path.join(REF, ref_file), ref_name))
-    ours = _signature(_resolve(os.path.join(ROOT, 'neurite_amd', our_file), our_name))
+    ref = REFERENCE['signatures'][sigs.key(ref_file, ref_name)]
+    ours = sigs.signature(os.path.join(ROOT, 'neurite_amd', our_file), our_name)
     # keyword-only arguments whose names start with an underscore are this package's private tuning knobs (_variant, _tune): they
     # cannot collide with a reference call
     ours['kwonly'] = [kv for kv in ours['kwonly'] if not kv[0].startswith('_')]

@@ -58,7 +58,7 @@ if os.environ.get('FUSED_FETCH'):
             print(json.dumps({'variant': k, 'fetch_error': str(e)[-300:]}), flush=True)
 for k in VARIANTS * REPS:
     env = dict(os.environ, NEURITE_AMD_LIB=os.path.join(LAB, 'libnrt_fused_%s.so' % k.replace('=', '').replace(',', '_')))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', STEPS, '--warmup', '10', '--no-cpu-baseline', '--no-batch1', '--no-unet'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', STEPS, '--warmup', '10', '--full', '--no-cpu-baseline', '--no-batch1', '--no-unet'],
                        env=env, capture_output=True, text=True)
     try:
         j = json.loads(r.stdout.strip().splitlines()[-1])

@@ -43,11 +43,11 @@ sweep)
   ;;
 bench)
   stage bench
-  timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"; echo "bench rc=$?" | tee -a "$OUT/session.log"
+  timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"; echo "bench rc=$?" | tee -a "$OUT/session.log"
   cat "$OUT/bench.json" | tee -a "$OUT/session.log"
-  timeout 600 python bench.py --unfused --no-cpu-baseline > "$OUT/bench_unfused.json" 2>> "$OUT/bench.log"
-  timeout 600 python bench.py --batch-per-gpu 1 --no-cpu-baseline > "$OUT/bench_b1.json" 2>> "$OUT/bench.log"
-  timeout 600 python bench.py --rough --no-cpu-baseline > "$OUT/bench_rough.json" 2>> "$OUT/bench.log"
+  timeout 600 python bench.py --full --unfused --no-cpu-baseline > "$OUT/bench_unfused.json" 2>> "$OUT/bench.log"
+  timeout 600 python bench.py --full --batch-per-gpu 1 --no-cpu-baseline > "$OUT/bench_b1.json" 2>> "$OUT/bench.log"
+  timeout 600 python bench.py --full --rough --no-cpu-baseline > "$OUT/bench_rough.json" 2>> "$OUT/bench.log"
   cat "$OUT/bench_unfused.json" "$OUT/bench_b1.json" "$OUT/bench_rough.json" | tee -a "$OUT/session.log"
   ;;
 prof)
