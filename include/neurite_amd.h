@@ -98,6 +98,7 @@ int nrt_interpn_f32(const float *vol, const float *loc, float *out,
  *   8 few-channel kernel: one voxel per lane, z corners of a row by one load (ndim 3, C<=4; the auto choice there)
  *   10 wave-private LDS row cache on the x-march schedule (ndim 3, C==32, linear; the auto choice for displacement fields and
  *      absolute locations since round 5: at least as fast as variant 3 on every field measured)
+ *   any other value: NRT_ERR_INVALID_ARG
  * tune: variant-specific knob (variant 3: z-chunk length | order | patch | region bits; variant 5: tile geometry). */
 int nrt_interpn_f32_ex(const float *vol, const float *loc, float *out,
                        int ndim, const int *vol_shape, const int *out_shape, int channels,

@@ -15,8 +15,6 @@
 // Float atomics (global_atomic_add_f32) make grad_vol's summation order non-deterministic, like TF's own
 // scatter-add on GPU; everything else is deterministic.
 
-#include <stdlib.h>
-
 #include "interpn_core.h"
 #include "wc.h"
 
@@ -824,156 +822,10 @@ __global__ __launch_bounds__(256, 3) void warp_dice_bwd_xm(InterpBwdArgs ba, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// d out / d vol at C = 32 with the duplicate rows merged on chip before they reach L2.
-//
-// The scatter of interpn_bwd_rows sends 8 row-atomics (32 float atomics each) per voxel to L2, whose atomic units are the
-// bottleneck: 3.6 ms per 160^3 x 32 volume (~67 clk of CU time per row).  Neighbouring voxels hit the same rows again and
-// again -- 64 voxels of two x-planes of a 4 x 8 patch touch ~196 distinct rows with their 512 corner references, and the
-// next planes re-touch most of them.  Here a block keeps an LDS table of 1024 row accumulators (128 KB; the x-march
-// schedule runs one block per CU anyway): a (row, weight) pair claims or finds its row's slot with one `ds_cmpswap` probe
-// sequence, its 32 weighted gradient values are added with LDS float atomics, and only when the table fills up (or the
-// block ends) are the live rows flushed to global memory, one row-atomic each.  Pairs that find no slot in 8 probes go to
-// global memory directly.  Summation order differs from the plain scatter (float atomics already made it unordered).
-// G = 8 (C = 32), x-march schedule; computes d vol only (d loc has its own pass in interpn_bwd_rows).
-//
-// MEASURED (round 2, one 160^3 x 32 volume, tools/bwd_vol_bench.py with phases switched off one at a time): the merge works --
-// the flushes' global atomics cost 0.06 ms in total -- but the LDS float atomics that feed the table take 5.8 ms, the slot
-// search 1.0 ms, everything else 0.75 ms: 7.6 ms against 3.6 ms for the plain scatter.  ds_add_f32 retires about one lane
-// every 3.4 clk per CU (0.3 lane-atomics per clk), SLOWER than the L2 atomic units serve the same CU (0.47 per clk at 3.6 ms).
-// An on-chip merge therefore has to accumulate without LDS atomics (owner-computes over per-row chains, or a sort); this kernel
-// is kept as the correct, selectable experiment (env NRT_BWD_VOL_DEDUP=1); interpn_bwd_vol_sort below is the merge that pays.
-constexpr int BV_SLOTS = 1024;           // power of two
+// Constants of the counting-sort merges of d vol below.  They merge with integer LDS atomics only: ds_add_f32 retires fewer lane-atomics
+// per clock than the L2 atomic units serve a CU, so a merge through LDS float atomics is slower than the plain scatter.
 constexpr int BV_NG = 32;                // lane-groups (voxels) per x-plane of the block's 4 x 8 patch
-constexpr int BV_U = 2;                  // x-planes per iteration
 constexpr unsigned BV_EMPTY = 0xffffffffu;
-
-template <int MODE>
-__global__ __launch_bounds__(256) void interpn_bwd_vol_dedup(InterpBwdArgs ba) {
-    constexpr int G = 8, C = 32, NPAIR = BV_NG * BV_U * 8;
-    const InterpArgs &a = ba.f;
-    int b = 0, x0 = 0, y0 = 0, z0 = 0, xlen = 0;
-    unsigned prow;
-    if (!xmarch_block(ba.tg, a.O[0], b, prow, x0, y0, z0, xlen)) return;
-    extern __shared__ __attribute__((aligned(16))) float bv_lds[];
-    float *acc = bv_lds;                                   // [BV_SLOTS][C]
-    unsigned *tag = (unsigned *)(acc + BV_SLOTS * C);      // [BV_SLOTS]
-    float *s_g = (float *)(tag + BV_SLOTS);                // [BV_NG * BV_U][C]
-    unsigned *s_idx = (unsigned *)(s_g + BV_NG * BV_U * C);   // [NPAIR]
-    float *s_wt = (float *)(s_idx + NPAIR);                // [NPAIR]
-    unsigned *s_slot = (unsigned *)(s_wt + NPAIR);         // [NPAIR]
-    __shared__ unsigned live_rows;
-    const float *locb = a.loc ? a.loc + (long long)b * a.loc_bs : nullptr;
-    const nrt_f4 *go = (const nrt_f4 *)(ba.gout + (long long)b * a.out_bs);
-    float *gv = ba.gvol + (long long)b * a.vol_bs;
-    const int lg = threadIdx.x % G;
-    const unsigned g = threadIdx.x / G;
-    const unsigned Y = (unsigned)a.S[1], Z = (unsigned)a.S[2];
-    for (int i = threadIdx.x; i < BV_SLOTS * C; i += 256) acc[i] = 0.0f;
-    for (int i = threadIdx.x; i < BV_SLOTS; i += 256) tag[i] = BV_EMPTY;
-    if (threadIdx.x == 0) live_rows = 0;
-    __syncthreads();
-
-    auto flush = [&]() {
-        // every live row goes out as one 128-byte row of float atomics (a wave covers two rows per instruction)
-        for (unsigned i = threadIdx.x; i < (unsigned)(BV_SLOTS * C); i += 256) {
-            const unsigned slot = i / C, ch = i % C;
-            const unsigned row = tag[slot];
-            if (row != BV_EMPTY) {
-                const float v = acc[i];
-                if (v != 0.0f) atomic_add_f32(gv + (size_t)row * C + ch, v);
-                acc[i] = 0.0f;
-            }
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < BV_SLOTS; i += 256) tag[i] = BV_EMPTY;
-        if (threadIdx.x == 0) live_rows = 0;
-        __syncthreads();
-    };
-
-    const unsigned niter = ((unsigned)xlen + BV_U - 1) / BV_U;
-    // the location and the gradient row of the next iteration's voxels are requested before this iteration's table work
-    float pre_p[BV_U][3];
-    nrt_f4 pre_g[BV_U];
-    bool pre_in[BV_U];
-    auto prefetch = [&](unsigned it) {
-#pragma unroll
-        for (int u = 0; u < BV_U; ++u) {
-            const int x = x0 + (int)(it * BV_U + u), y = y0 + (int)(g >> ba.tg.ltz), z = z0 + (int)(g & ((1u << ba.tg.ltz) - 1u));
-            pre_in[u] = x < x0 + xlen && y < a.O[1] && z < a.O[2];
-            const unsigned q = pre_in[u] ? ((unsigned)x * (unsigned)a.O[1] + (unsigned)y) * (unsigned)a.O[2] + (unsigned)z : a.nout - 1;
-            int qd[NRT_MAXD];
-            float p[NRT_MAXD];
-            decode<3>(a, q, qd);
-            load_loc<3, MODE>(a, locb, q, qd, p);
-            pre_p[u][0] = p[0]; pre_p[u][1] = p[1]; pre_p[u][2] = p[2];
-            pre_g[u] = go[(long long)q * G + lg];
-        }
-    };
-    prefetch(0);
-    for (unsigned it = 0; it < niter; ++it) {
-        // ---- file the iteration's (row, weight) pairs and gradient rows ------------------------------------------------
-#pragma unroll
-        for (int u = 0; u < BV_U; ++u) {
-            float p[NRT_MAXD] = {pre_p[u][0], pre_p[u][1], pre_p[u][2]};
-            const bool oob = a.has_fill ? out_of_bounds<3>(a, p) : false;
-            int i0[3], i1[3];
-            float w0[3], w1[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) corner_1d(p[d], a.S[d], i0[d], i1[d], w0[d], w1[d]);
-            nrt_f4 gq = pre_g[u];
-            const bool dead = !pre_in[u] || oob;
-            if (dead) gq = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
-            const unsigned slot = (unsigned)u * BV_NG + g;
-            ((nrt_f4 *)s_g)[slot * G + lg] = gq;
-            const int bx = (lg >> 2) & 1, by = (lg >> 1) & 1, bz = lg & 1;       // lane lg files corner lg
-            const unsigned ix = bx ? i1[0] : i0[0], iy = by ? i1[1] : i0[1], iz = bz ? i1[2] : i0[2];
-            s_idx[slot * 8 + lg] = (ix * Y + iy) * Z + iz;
-            s_wt[slot * 8 + lg] = dead ? 0.0f : (bx ? w1[0] : w0[0]) * (by ? w1[1] : w0[1]) * (bz ? w1[2] : w0[2]);
-        }
-        __syncthreads();
-        if (it + 1 < niter) prefetch(it + 1);
-        // ---- every pair finds (or claims) the accumulator of its row --------------------------------------------------
-        for (unsigned pi = threadIdx.x; pi < (unsigned)NPAIR; pi += 256) {
-            unsigned found = BV_EMPTY;                          // BV_EMPTY = no slot: straight to global memory
-            if (s_wt[pi] != 0.0f) {
-                const unsigned row = s_idx[pi];
-                unsigned h = (row * 2654435761u) >> 22;         // multiplicative hash, top 10 bits
-#pragma unroll 1
-                for (int probe = 0; probe < 8; ++probe) {
-                    const unsigned old = atomicCAS(&tag[h], BV_EMPTY, row);
-                    if (old == BV_EMPTY) { atomicAdd(&live_rows, 1u); found = h; break; }
-                    if (old == row) { found = h; break; }
-                    h = (h + 1u) & (BV_SLOTS - 1u);
-                }
-            }
-            s_slot[pi] = found;
-        }
-        __syncthreads();
-        // ---- accumulate: a lane-group takes one pair, a lane 4 channels of its gradient row (one 16-byte LDS read, four LDS
-        // float atomics); the 16 passes are independent and issue back to back ------------------------------------------
-#pragma unroll
-        for (int pass = 0; pass < NPAIR / 32; ++pass) {
-            const unsigned r = (unsigned)pass * 32u + g;
-            const float wt = s_wt[r];
-            const unsigned slot = s_slot[r];
-            const nrt_f4 gr = ((const nrt_f4 *)s_g)[(r >> 3) * G + lg];
-            if (wt != 0.0f) {
-                if (slot != BV_EMPTY) {
-                    float *dst = acc + slot * C + 4 * lg;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) atomicAdd(dst + c, wt * gr[c]);
-                } else {
-                    float *dst = gv + (size_t)s_idx[r] * C + 4 * lg;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) atomic_add_f32(dst + c, wt * gr[c]);
-                }
-            }
-        }
-        __syncthreads();
-        if (live_rows > (unsigned)(BV_SLOTS * 5 / 8)) flush();   // uniform: live_rows is read after the barrier by everyone
-    }
-    flush();
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // d out / d vol at C = 32, duplicate rows merged by a counting sort (no LDS float atomics).
@@ -1280,11 +1132,8 @@ __global__ __launch_bounds__(256) void interpn_nearest_bwd(InterpBwdArgs ba) {
 
 }  // namespace
 
-// NRT_BWD_WC=0: d loc by the register-pipelined kernel (warp_dice_bwd_xm) instead of the wave-cache gather (A/B runs, tests)
-static bool nrt_bwd_wc() {
-    const char *e = getenv("NRT_BWD_WC");         // read per call: the tests run both kernels in one process
-    return !(e && e[0] == '0');
-}
+// NRT_BWD_WC=0: d loc by the register-pipelined kernel (warp_dice_bwd_xm) instead of the wave-cache gather (nrt_common.h)
+static bool nrt_bwd_wc() { return nrt_env_int("NRT_BWD_WC", 1) != 0; }
 
 extern "C" int nrt_interpn_bwd_f32(const float *vol, const float *loc, const float *grad_out, float *grad_vol,
                                    float *grad_loc, int ndim, const int *vol_shape, const int *out_shape, int channels,
@@ -1322,12 +1171,10 @@ extern "C" int nrt_interpn_bwd_f32(const float *vol, const float *loc, const flo
             tile_geometry(out_shape, G, t, t, ba.tg, nt);
             const unsigned per_batch = xmarch_setup(out_shape, batch, t, ba.tg);
             grid = dim3(nrt_xcd_grid(per_batch * (unsigned)batch), 1);
-            { const char *e = getenv("NRT_BWD_SYNC"); ba.tg.depth_sync = e ? atoi(e) : 8; }
-            const char *dedup_env = getenv("NRT_BWD_VOL_DEDUP");          // read per call: tests switch it
-            const int use_dedup = dedup_env ? atoi(dedup_env) : 2;       // 0 plain scatter, 1 LDS accumulator table, 2 counting-sort merge
+            ba.tg.depth_sync = 8;
             unsigned long long rows = 1;
             for (int d = 0; d < 3; ++d) rows *= (unsigned long long)vol_shape[d];
-            if (grad_vol && use_dedup == 2 && rows < 0xffffffffull) {
+            if (grad_vol && nrt_env_int("NRT_BWD_VOL_DEDUP", 1) != 0 && rows < 0xffffffffull) {
                 // d vol by the sort-merge kernel (duplicate rows merged before L2), d loc by the rows kernel
                 InterpBwdArgs bv = ba;
                 bv.gloc = nullptr;
@@ -1336,25 +1183,6 @@ extern "C" int nrt_interpn_bwd_f32(const float *vol, const float *loc, const flo
                     case NRT_LOC_SHIFT: hipLaunchKernelGGL((interpn_bwd_vol_sort<NRT_LOC_SHIFT>), grid, dim3(BS_NT), 0, st, bv); break;
                     default: hipLaunchKernelGGL((interpn_bwd_vol_sort<NRT_LOC_LINSPACE>), grid, dim3(BS_NT), 0, st, bv); break;
                 }
-                NRT_CHECK_LAUNCH();
-                if (!grad_loc) return NRT_OK;
-                ba.gvol = nullptr;
-            } else if (grad_vol && use_dedup && rows < 0xffffffffull) {
-                // d vol through the LDS row-accumulator table (duplicate rows merged before L2), d loc by the rows kernel
-                const size_t dyn = (size_t)BV_SLOTS * 32 * 4 + BV_SLOTS * 4 + (size_t)BV_NG * BV_U * 32 * 4 + 3 * (size_t)BV_NG * BV_U * 8 * 4;
-                InterpBwdArgs bv = ba;
-                bv.gloc = nullptr;
-#define NRT_BV(MODE)                                                                                                         \
-    do {                                                                                                                     \
-        (void)hipFuncSetAttribute((const void *)interpn_bwd_vol_dedup<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
-        hipLaunchKernelGGL((interpn_bwd_vol_dedup<MODE>), grid, dim3(256), dyn, st, bv);                                     \
-    } while (0)
-                switch (loc_mode) {
-                    case NRT_LOC_ABSOLUTE: NRT_BV(NRT_LOC_ABSOLUTE); break;
-                    case NRT_LOC_SHIFT: NRT_BV(NRT_LOC_SHIFT); break;
-                    default: NRT_BV(NRT_LOC_LINSPACE); break;
-                }
-#undef NRT_BV
                 NRT_CHECK_LAUNCH();
                 if (!grad_loc) return NRT_OK;
                 ba.gvol = nullptr;
@@ -1385,8 +1213,7 @@ extern "C" int nrt_interpn_bwd_f32(const float *vol, const float *loc, const flo
     } else {
         unsigned long long grows = 1;
         for (int d = 0; d < ndim; ++d) grows *= (unsigned long long)vol_shape[d];
-        const char *sa = getenv("NRT_BWD_VOL_SORT_ANY");               // 0: the per-element scatter below for every channel count
-        if (grad_vol && ndim == 3 && channels <= BG_CMAX && grows < 0xffffffffull && !(sa && sa[0] == '0')) {
+        if (grad_vol && ndim == 3 && channels <= BG_CMAX && grows < 0xffffffffull && nrt_env_int("NRT_BWD_VOL_SORT_ANY", 1) != 0) {
             // few channels, 3-D: duplicate rows merged on chip (counting sort), d loc by the per-voxel kernel
             const unsigned nTx = (unsigned)(out_shape[0] + 3) / 4, nTy = (unsigned)(out_shape[1] + 3) / 4, nTz = (unsigned)(out_shape[2] + 7) / 8;
             const unsigned ntiles = nTx * nTy * nTz;
@@ -1581,7 +1408,7 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
         tile_geometry(out_shape, G, t, t, ba.tg, nt);
         const unsigned per_batch = xmarch_setup(out_shape, batch, t, ba.tg);
         grid = dim3(nrt_xcd_grid(per_batch * (unsigned)batch), 1);
-        { const char *e = getenv("NRT_BWD_SYNC"); ba.tg.depth_sync = e ? atoi(e) : 8; }
+        ba.tg.depth_sync = 8;
     }
 #define NRT_WDB(GG)                                                                                              \
     if (loc_mode == NRT_LOC_SHIFT)                                                                               \
@@ -1592,22 +1419,14 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
                            grad_dice, laplace_smoothing);
     if (G == 8 && ba.tg.x_march && nrt_bwd_wc() && nrt_wc_interpn_supported(&ba.f, batch))
         return nrt_wc_bwd_launch(&ba.f, batch, loc_mode, fixed, sums, grad_dice, laplace_smoothing, grad_loc, stream);
-    static int xm_pipe = -1;                       // NRT_BWD_XM=0: the un-pipelined kernel on the same schedule (A/B runs)
-    if (xm_pipe < 0) { const char *e = getenv("NRT_BWD_XM"); xm_pipe = e ? atoi(e) : 1; }
     // the pipelined kernel forms 32-bit byte offsets of rows and locations
     const bool xm_fits = (unsigned long long)nin * nlabels * 4ull < (1ull << 32) &&
                          (unsigned long long)ba.f.nout * nlabels * 4ull < (1ull << 32);
-    if (G == 8 && ba.tg.x_march && xm_pipe && xm_fits) {
-        static int lds_kb = -1;                    // NRT_BWD_LDS_KB (experiments): unused dynamic LDS per block caps the blocks per CU
-        if (lds_kb < 0) { const char *e = getenv("NRT_BWD_LDS_KB"); lds_kb = e ? atoi(e) : 0; }
-        const unsigned dyn = (unsigned)lds_kb * 1024u;
-        if (loc_mode == NRT_LOC_SHIFT) {
-            if (dyn > 48 * 1024) (void)hipFuncSetAttribute((const void *)warp_dice_bwd_xm<NRT_LOC_SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            hipLaunchKernelGGL((warp_dice_bwd_xm<NRT_LOC_SHIFT>), grid, dim3(256), dyn, st, ba, fixed, sums, grad_dice, laplace_smoothing);
-        } else {
-            if (dyn > 48 * 1024) (void)hipFuncSetAttribute((const void *)warp_dice_bwd_xm<NRT_LOC_ABSOLUTE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            hipLaunchKernelGGL((warp_dice_bwd_xm<NRT_LOC_ABSOLUTE>), grid, dim3(256), dyn, st, ba, fixed, sums, grad_dice, laplace_smoothing);
-        }
+    if (G == 8 && ba.tg.x_march && xm_fits) {
+        if (loc_mode == NRT_LOC_SHIFT)
+            hipLaunchKernelGGL((warp_dice_bwd_xm<NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, grad_dice, laplace_smoothing);
+        else
+            hipLaunchKernelGGL((warp_dice_bwd_xm<NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed, sums, grad_dice, laplace_smoothing);
         NRT_CHECK_LAUNCH();
         return NRT_OK;
     }

@@ -1043,9 +1043,7 @@ extern "C" int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre
     // all 8 parity groups per block when the staging's assumptions hold (quad-aligned channels, 32-bit offsets, 24-bit strides)
     const bool foldall = cin % 4 == 0 && group % 4 == 0 && (long long)a.X * a.Y * a.Z * cin < (1ll << 31) &&
                          (long long)a.Y * a.Z * cin < (1ll << 24) && ((((uintptr_t)x_lo) | ((uintptr_t)grad_pre_s2d)) & 15) == 0;
-    static int kfold = -1;
-    if (kfold < 0) { const char *e = getenv("NRT_WGRAD_FOLDALL"); kfold = e ? atoi(e) : 1; }
-    if (foldall && kfold) return cin <= 16 ? launch_wgrad_fold<1>(a, st) : launch_wgrad_fold<2>(a, st);
+    if (foldall) return cin <= 16 ? launch_wgrad_fold<1>(a, st) : launch_wgrad_fold<2>(a, st);
     const int na = cin <= 16 ? 1 : (cin <= 32 ? 2 : 3), nb = group <= 16 ? 1 : 2;
     if (na == 1) return nb == 1 ? launch_wgrad<1, 1>(a, st) : launch_wgrad<1, 2>(a, st);
     if (na == 2) return nb == 1 ? launch_wgrad<2, 1>(a, st) : launch_wgrad<2, 2>(a, st);

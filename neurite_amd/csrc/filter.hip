@@ -10,7 +10,6 @@
 // [outer, R, inner]; the extrema are order-independent, so they are reduced with integer atomics on a monotone
 // encoding of the floats (deterministic), then applied in a second pass.
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "nrt_common.h"
@@ -453,8 +452,7 @@ extern "C" int nrt_conv1d_axis_f32(const float *x, const float *kernel, float *y
     a.dil = dilation; a.pad = pad_before; a.inner = inner;
     hipStream_t st = nrt_stream(stream);
     const bool vec = inner % 4 == 0 && ((((uintptr_t)x | (uintptr_t)y) & 15) == 0);
-    const char *ge = getenv("NRT_CONV1D_GENERIC");                // tests: the plain kernels only
-    const bool fast = !(ge && ge[0] == '1') && stride == 1 && dilation == 1 && width <= 256 && out_len >= 8;
+    const bool fast = nrt_env_int("NRT_CONV1D_GENERIC", 0) != 1 && stride == 1 && dilation == 1 && width <= 256 && out_len >= 8;
     constexpr int R = 8;
     if (fast && inner == 1 && outer >= 8 && (((uintptr_t)y & 15) == 0)) {
         const CiGeom g = ci_geometry(out_len, width);

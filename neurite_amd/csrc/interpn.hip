@@ -616,8 +616,7 @@ void launch_zrun_w(const InterpArgs &a, int batch, int mode, int LZ, int zc_oute
 // tune = LZ | zc_outer << 12 | patch << 16 | lreg << 20 | lds_kb << 24
 //   patch 0: 4x8, 1: 8x8, 2: 8x16, 3: 4x16 columns per block; lreg > 0: region order (2^lreg x 2^lreg patches per
 //   region); lds_kb: unused dynamic LDS per block, caps the blocks per CU so that an XCD's L2 holds one region's rows
-void launch_zrun(const InterpArgs &a, int batch, int mode, int variant, int tune, hipStream_t st) {
-    (void)variant;
+void launch_zrun(const InterpArgs &a, int batch, int mode, int tune, hipStream_t st) {
     int LZ = tune & 0xfff;
     const int zc_outer = (tune >> 12) & 1, patch = (tune >> 16) & 3, lreg = (tune >> 20) & 7;
     const unsigned dyn = (unsigned)((tune >> 24) & 0x7f) * 1024u;
@@ -682,7 +681,6 @@ extern "C" int nrt_interpn_f32_ex(const float *vol, const float *loc, float *out
                           vol_bytes < (1ull << 32);
     const bool can_lean = (method == NRT_INTERP_LINEAR ? (loc_mode == NRT_LOC_LINSPACE || loc) : (loc_mode != NRT_LOC_LINSPACE && loc)) &&
                           nrt_lean_supported(a.S, a.O, channels, ndim, vol, loc, out, vol_batch_stride, loc_batch_stride);
-    const bool variant_was_auto = variant == 0;
     if (variant == 0) {
         if (can_zrun) {
             // Displacement fields and absolute locations: the wave-cache kernel (variant 10, fused_wc.h) since its round-5 schedule --
@@ -708,7 +706,7 @@ extern "C" int nrt_interpn_f32_ex(const float *vol, const float *loc, float *out
         }
         else variant = 1;
     }
-    if ((variant == 3 || variant == 4) && !can_zrun) return NRT_ERR_UNSUPPORTED;
+    if (variant == 3 && !can_zrun) return NRT_ERR_UNSUPPORTED;
     const bool can_tile = can_rows && method == NRT_INTERP_LINEAR && vol_bytes < (1ull << 32);
     if (variant == 5 && !can_tile) return NRT_ERR_UNSUPPORTED;
     if (variant == 2 && !can_rows) return NRT_ERR_UNSUPPORTED;
@@ -718,15 +716,11 @@ extern "C" int nrt_interpn_f32_ex(const float *vol, const float *loc, float *out
             else launch_generic<NRT_INTERP_NEAREST, float>(a, ndim, batch, loc_mode, st);
             break;
         case 2: launch_rows_any(a, batch, loc_mode, method, tune, st); break;
-        case 3:
-        case 4: launch_zrun(a, batch, loc_mode, variant, tune, st); break;
+        case 3: launch_zrun(a, batch, loc_mode, tune, st); break;
         case 5: launch_tile_any(a, batch, loc_mode, tune, st); break;
         case 8:                             // few channels: tile form (one voxel per lane, corners through the texture unit)
             if (!can_lean) return NRT_ERR_UNSUPPORTED;
-            return nrt_lean_launch(&a, batch, loc_mode, method == NRT_INTERP_NEAREST ? 1 : 0, st, variant_was_auto ? NRT_LEAN_FORM_AUTO : NRT_LEAN_FORM_TILE);
-        case 11:                            // few channels, per-voxel locations, linear: box form (source box of a tile staged in LDS)
-            if (!can_lean || method != NRT_INTERP_LINEAR || loc_mode == NRT_LOC_LINSPACE) return NRT_ERR_UNSUPPORTED;
-            return nrt_lean_launch(&a, batch, loc_mode, 0, st, NRT_LEAN_FORM_BOX);
+            return nrt_lean_launch(&a, batch, loc_mode, method == NRT_INTERP_NEAREST ? 1 : 0, st);
         case 10:                            // wave-private LDS row cache (fused_wc.h) without the Dice half
             if (!can_zrun || !nrt_wc_interpn_supported(&a, batch)) return NRT_ERR_UNSUPPORTED;
             return nrt_wc_interpn_launch(&a, batch, loc_mode, st);

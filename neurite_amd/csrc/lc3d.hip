@@ -15,8 +15,6 @@
 // took the kernel from 171 to 98 VGPRs = 5 waves per SIMD, and 0.51 -> 0.72 of the HBM roof at BASELINE config 5.
 // F order (kr, kc, kz, cin) row-major (layers.py:1179-1186), positions row-major (:1172-1173).
 
-#include <stdlib.h>
-
 #include "nrt_common.h"
 #include "activations.h"
 
@@ -749,17 +747,12 @@ __global__ __launch_bounds__(256, 2) void lc3d_fwd_mfma_blk(LcArgs a, int b0, in
 
 template <typename T, int CPL>
 bool launch_mfma(const LcArgs &a, hipStream_t st) {
-    // experiment knob: NRT_LC_MFMA = 0 keeps the vector kernel for every batch size
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("NRT_LC_MFMA"); on = e ? atoi(e) : 1; }
     constexpr int NCMAX = CPL * (int)sizeof(T) == 8 ? 27 : 28;          // chunks of 16 weight rows a position may have (ring geometry of the kernel)
     const int F = a.kr * a.kc * a.kz * a.Cin;
-    if (!on || a.B < 3 || a.Cout != 4 * CPL || F % 16 || F / 16 > NCMAX || a.stage_chunks < 1 || a.stage_chunks > 128) return false;
+    if (nrt_env_int("NRT_LC_MFMA", 1) == 0 || a.B < 3 || a.Cout != 4 * CPL || F % 16 || F / 16 > NCMAX || a.stage_chunks < 1 || a.stage_chunks > 128) return false;
     if ((size_t)a.stage_chunks * 16 != (size_t)F * sizeof(T)) return false;      // the staged pieces are exactly the patch
     if ((((uintptr_t)a.k) & 15) || (((uintptr_t)a.y) & 15) || (a.bias && (((uintptr_t)a.bias) & 15))) return false;
     if ((long long)a.R * a.C * a.Z * a.Cin * (long long)sizeof(T) * 8 >= (1ll << 31)) return false;      // 8 volumes behind one descriptor
-    static int kblocks = -1;
-    if (kblocks < 0) { const char *e = getenv("NRT_LC_BLOCKS"); kblocks = e ? atoi(e) : 0; }
     const long long O = (long long)a.orr * a.occ * a.ozz;
     const size_t pb = (size_t)(NCMAX + 1) * 16 * sizeof(T);
     const bool two = a.stage_chunks > 64;
@@ -773,14 +766,12 @@ bool launch_mfma(const LcArgs &a, hipStream_t st) {
         int &per_cu = per_cu_dev[dev];
         if (per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, shm) != hipSuccess || per_cu < 1)) per_cu = 2;
         unsigned blocks = nrt_xcd_grid((unsigned)((O + 3) / 4));
-        const unsigned cap = nrt_xcd_grid(kblocks > 0 ? (unsigned)kblocks : (unsigned)per_cu * (unsigned)nrt_num_cus());
+        const unsigned cap = nrt_xcd_grid((unsigned)per_cu * (unsigned)nrt_num_cus());
         if (blocks > cap) blocks = cap;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shm, st, a, b0, nb);
     };
     // the block-staged form: 3 taps along z over exactly 16 input channels, unit z stride, <= 9 (kr, kc) runs
-    static int kblk = -1;
-    if (kblk < 0) { const char *e = getenv("NRT_LC_BLK"); kblk = e ? atoi(e) : 1; }
-    const bool blk_ok = kblk && a.kz == 3 && a.Cin == 16 && a.sz == 1 && a.kr * a.kc <= 9 && (((uintptr_t)a.x) & 15) == 0;
+    const bool blk_ok = a.kz == 3 && a.Cin == 16 && a.sz == 1 && a.kr * a.kc <= 9 && (((uintptr_t)a.x) & 15) == 0;
     constexpr size_t CINB = 16 * sizeof(T), PBB = 9 * 6 * CINB + 5 * CINB;
     auto run_blk = [&](auto kernel, int sets, int b0, int nb) {
         const size_t shm = (size_t)2 * 4 * sets * PBB;
@@ -793,7 +784,7 @@ bool launch_mfma(const LcArgs &a, hipStream_t st) {
         if (per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, shm) != hipSuccess || per_cu < 1)) per_cu = 2;
         const long long ngrp = (long long)a.orr * a.occ * ((a.ozz + 3) / 4);
         unsigned blocks = nrt_xcd_grid((unsigned)ngrp);
-        const unsigned cap = nrt_xcd_grid(kblocks > 0 ? (unsigned)kblocks : (unsigned)per_cu * (unsigned)nrt_num_cus());
+        const unsigned cap = nrt_xcd_grid((unsigned)per_cu * (unsigned)nrt_num_cus());
         if (blocks > cap) blocks = cap;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shm, st, a, b0, nb);
         return true;
@@ -858,12 +849,9 @@ void launch_vec_st(const LcArgs &a, unsigned blocks, hipStream_t st) {
 
 template <typename T, int MAXIT, int SPLIT = 1>
 void launch_vec(const LcArgs &a, hipStream_t st) {
-    // experiment knob: NRT_LC_BLOCKS (grid size)
-    static int kblocks = -1;
-    if (kblocks < 0) { const char *e = getenv("NRT_LC_BLOCKS"); kblocks = e ? atoi(e) : 0; }
     const long long O = (long long)a.orr * a.occ * a.ozz;
     unsigned blocks = (unsigned)((O + 4 / SPLIT - 1) / (4 / SPLIT));
-    const unsigned cap = kblocks > 0 ? (unsigned)kblocks : 256u * 20u;     // 5 resident blocks per CU x 4 rounds (profiles/)
+    const unsigned cap = 256u * 20u;     // 5 resident blocks per CU x 4 rounds (profiles/)
     if (blocks > cap) blocks = cap;
     if (a.stage_chunks > 0) launch_vec_st<T, MAXIT, true, SPLIT>(a, blocks, st);
     else launch_vec_st<T, MAXIT, false, SPLIT>(a, blocks, st);
@@ -887,9 +875,7 @@ int launch_any(const LcArgs &a_in, int variant, hipStream_t st) {
         LcArgs a = a_in;
         // stage the patch through LDS when its kr * kc runs (kz * Cin contiguous elements) are whole 16-byte pieces
         const long long runb = (long long)a.kz * a.Cin * (long long)sizeof(T), chunks = runb / 16 * a.kr * a.kc;
-        static int kstage = -1;
-        if (kstage < 0) { const char *e = getenv("NRT_LC_STAGE"); kstage = e ? atoi(e) : 1; }
-        a.stage_chunks = (kstage && runb % 16 == 0 && ((long long)a.Cin * (long long)sizeof(T)) % 16 == 0 && chunks <= 128 &&
+        a.stage_chunks = (runb % 16 == 0 && ((long long)a.Cin * (long long)sizeof(T)) % 16 == 0 && chunks <= 128 &&
                           (((uintptr_t)a.x) & 15) == 0 && chunks * 16 * 4 * 4 <= 48 * 1024) ? (int)chunks : 0;
         bool done = false;
         if constexpr (sizeof(T) == 2) done = a.Cout == 16 ? launch_mfma<T, 4>(a, st) : (a.Cout == 32 ? launch_mfma<T, 8>(a, st) : false);

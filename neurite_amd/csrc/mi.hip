@@ -10,8 +10,6 @@
 // floats per item.  The [items, nb, nb]-sized arithmetic that follows (normalisation, log, sum) is host-side glue.
 // The backward recomputes the weights: dL/dx_v = sum_i (sum_j G_ij wy_j(v) + gx_i) * wx_i(v) * (-2 alpha (x_v - c_i)).
 
-#include <cstdlib>
-
 #include "nrt_common.h"
 
 namespace {
@@ -395,8 +393,7 @@ extern "C" int nrt_mi_joint_bwd_f32(const float *x, const float *y, const float 
     MiArgs a;
     a.x = x; a.y = y; a.cx = centers_x; a.cy = centers_y; a.alpha = alpha; a.lo = min_clip; a.hi = max_clip;
     a.V = nvox; a.C = channels; a.nb = nb_bins; a.items = batch * channels; a.joint = nullptr; a.sx = nullptr; a.sy = nullptr;
-    const char *sc = getenv("NRT_MI_BWD_SCALAR");                 // tests: the one-thread-per-voxel kernel
-    if (sc && sc[0] == '1') {
+    if (nrt_env_int("NRT_MI_BWD_SCALAR", 0) == 1) {                // test hook (nrt_common.h): the one-thread-per-voxel kernel
         const size_t shm = (size_t)(nb_bins * nb_bins + 4 * nb_bins) * sizeof(float);
         hipLaunchKernelGGL(mi_joint_bwd, dim3(mblocks(nvox, 256), (unsigned)a.items), dim3(256), shm, nrt_stream(stream), a, grad_joint,
                            grad_sum_x, grad_sum_y, grad_x, grad_y);

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/neurite_amd.h"
 
@@ -70,6 +71,19 @@ static inline unsigned nrt_xcd_grid(unsigned nblocks) {
 }
 
 static inline hipStream_t nrt_stream(void *s) { return (hipStream_t)s; }
+
+// Test hooks: the only environment variables the library reads, each on every call, each selecting a reference kernel that the tests
+// compare the default against (bit for bit, or both against the oracle).  Unset: the default kernel.
+//   NRT_BWD_WC=0            interpn / Dice backward, C = 32 x-march: the register-pipelined kernel instead of the wave-cache gather
+//   NRT_BWD_VOL_DEDUP=0     interpn backward d vol, C = 32 x-march: the plain scatter instead of the counting-sort merge
+//   NRT_BWD_VOL_SORT_ANY=0  interpn backward d vol, 3-D, up to 8 channels: the per-element scatter instead of the counting-sort merge
+//   NRT_MI_BWD_SCALAR=1     mutual-information backward: the one-thread-per-voxel kernel instead of the matrix-core one
+//   NRT_CONV1D_GENERIC=1    separable 1-D convolution: the plain kernels only
+//   NRT_LC_MFMA=0           locally connected 3-D: the vector kernel for every batch size instead of the matrix-core one
+static inline int nrt_env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // Zero fill on a stream by a KERNEL.  hipMemsetAsync is not used on paths that may run inside a captured hipGraph: the memset node of the
 // persistent gather's work counters did not take effect between replays (ROCm 7.2; tools/graph_fused_probe.py, fused_wc.h).

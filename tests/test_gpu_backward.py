@@ -560,13 +560,12 @@ def test_grad_vol_few_channels(dev, C, mode, monkeypatch):
 
 
 @pytest.mark.parametrize('fill', [None, 0.0])
-@pytest.mark.parametrize('dedup', ['0', '1', '2'])
+@pytest.mark.parametrize('dedup', ['0', '2'])
 def test_grad_vol_row_accumulator_kernel(dev, fill, dedup, monkeypatch):
-    """d out / d vol at 32 channels under the x-march schedule: the plain scatter (NRT_BWD_VOL_DEDUP=0), the experimental LDS row-accumulator
-    table (interpn_bwd_vol_dedup, env NRT_BWD_VOL_DEDUP=1): duplicate rows merged on chip, rows that find no slot go to memory
-    directly, the table is flushed when it fills; and the counting-sort merge (interpn_bwd_vol_sort, NRT_BWD_VOL_DEDUP=2, the default) -- against
-    the float64 oracle; smooth field (heavy re-use), rough field (every
-    pair its own row: the direct path and many flushes)"""
+    """d out / d vol at 32 channels under the x-march schedule, both ways a row's contributions are accumulated: the plain scatter
+    (NRT_BWD_VOL_DEDUP=0, one row of float atomics per corner) and the counting-sort merge (interpn_bwd_vol_sort, the default; any
+    other value) that sums the duplicate rows of a block on chip and sends each distinct row once -- against the float64 oracle;
+    smooth field (heavy re-use), rough field (every pair its own row)"""
     monkeypatch.setenv('NRT_BWD_VOL_DEDUP', dedup)
     rng = np.random.default_rng(37)
     B, S, L = 3, (18, 47, 60), 32

@@ -117,8 +117,7 @@ def test_lc3d_many_filters_batch(dev, batch):
                                                (16, 32, (2, 1, 3), (2, 1, 1), (6, 4, 8))])
 def test_lc3d_matrix_core_batches(dev, batch, cin, cout, ks, st, S, monkeypatch):
     """3 .. 8 batch entries per weight pass on v_mfma_f32_4x4x1 (csrc/lc3d.hip: lc3d_fwd_mfma; 9 entries = 8 + 1): against the oracle
-    and against the vector kernel (NRT_LC_MFMA=0 is read once per process, so the comparison kernel is asked for per entry pair:
-    batches of 2 never take the matrix form)"""
+    and against the vector kernel, asked for per entry pair: batches of 2 never take the matrix form"""
     rng = np.random.default_rng(batch * 100 + cin + cout)
     osh = tuple((S[d] - ks[d]) // st[d] + 1 for d in range(3))
     O, Fd = int(np.prod(osh)), int(np.prod(ks)) * cin

@@ -1,5 +1,5 @@
 """d out / d vol of the linear warp at 160^3 x 32 (one volume), bench field and worst-case field: NRT_BWD_VOL_DEDUP = 0 plain
-scatter, 1 LDS row-accumulator table, 2 counting-sort merge; the time includes the zero fill of the gradient (524 MB)"""
+scatter, unset the counting-sort merge (the default); the time includes the zero fill of the gradient (524 MB)"""
 import json, os, sys, torch
 sys.path.insert(0, '.')
 import neurite_amd as ne

@@ -90,9 +90,12 @@ pmcsweep)
 pmc)
   stage pmc
   for c in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp && timeout -k 5 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -o bench -- \
-        python "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-batch1 --no-unet --no-strong > /dev/null 2> "$OUT/pmc_$c.log" < /dev/null )
-    echo "pmc $c rc=$?" | tee -a "$OUT/session.log"
+    # --full: the default run launches neither dice_soft_vec (the calibration of tools/update_hbm_traffic.py) nor the stand-alone warp
+    ( cd /tmp && timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -o bench -- \
+        python "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-batch1 --no-unet --no-strong > /dev/null 2> "$OUT/pmc_$c.log" < /dev/null )
+    rc=$?
+    echo "pmc $c rc=$rc" | tee -a "$OUT/session.log"
+    [ $rc -eq 0 ] || break                 # a failed pass (fault, time limit) ends the GPU work of the stage
   done
   python tools/summarize_pmc.py "$OUT" 2>&1 | tee -a "$OUT/session.log"
   # which binary the counters belong to: the id of the library that ran and of the gather's sources (tools/update_hbm_traffic.py)

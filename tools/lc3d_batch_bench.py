@@ -34,4 +34,4 @@ for S, cin, filters, dtype in CASES:
         wbytes = layer.kernel.numel() * layer.kernel.element_size()
         print(json.dumps({'op': 'LocallyConnected3D %d^3 x %d -> %d filters, %s' % (S, cin, filters, str(dtype).split('.')[-1]), 'batch': B,
                           'weights_GB': round(wbytes / 1e9, 3), 'fwd_ms': round(ms, 3),
-                          'weight_stream_frac_of_8TBs': round(wbytes / ms / 1e6 / 8000, 3), 'mfma': os.environ.get('NRT_LC_MFMA', '1'), 'blocks': os.environ.get('NRT_LC_BLOCKS', 'auto')}), flush=True)
+                          'weight_stream_frac_of_8TBs': round(wbytes / ms / 1e6 / 8000, 3), 'mfma': os.environ.get('NRT_LC_MFMA', '1')}), flush=True)
