@@ -394,6 +394,35 @@ int nrt_add_act_affine_f32(const float *a, const float *b, const float *scale, c
                            float *y, long long n, int channels, int activation, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * bfloat16 inference forms of the conv stack (csrc/conv_bf16.hip; models.ConvNet with bf16 parameters).  Tensors are bf16,
+ * channels-last, as the float32 entry points above; biases, BatchNorm scale / shift are float32.  Every kernel computes in
+ * float32 from the stored bf16 values and rounds its result to bf16 once, round-to-nearest-even.
+ *   nrt_conv3d_packed_weight_bytes_bf16  size of the packed weights (bytes)
+ *   nrt_conv3d_pack_weights_bf16         Keras-layout weights [kx,ky,kz,cin,cout] of `dtype` (NRT_DT_F32: rounded to bf16, or
+ *                                        NRT_DT_BF16) -> the A-operand order of v_mfma_f32_16x16x32_bf16, K zero-padded to 32
+ *   nrt_conv3d_bf16                      semantics of nrt_conv3d_f32 (nearest up-sampling + concatenate of src1, any kernel size
+ *                                        and dilation, SAME / VALID; none / ELU / RELU fused, NRT_ERR_INVALID_ARG for other
+ *                                        codes): exact bf16 products, float32 accumulation, bias and activation in float32.
+ *                                        out 8-byte aligned.
+ *   nrt_conv1x1_softmax_bf16             weights bf16 [cin, cout], cout <= 64
+ *   nrt_softmax_lastdim_bf16, nrt_maxpool3d_bf16, nrt_upsample_concat_bf16, nrt_add_act_affine_bf16: as the float32 forms
+ *   (pooling and up-sampling are exact).  No atomics: results are run-to-run bit-identical. */
+size_t nrt_conv3d_packed_weight_bytes_bf16(const int *ksize, int cin, int cout);
+int nrt_conv3d_pack_weights_bf16(const void *weights, int dtype, const int *ksize, int cin, int cout, void *packed, void *stream);
+int nrt_conv3d_bf16(const void *src0, int c0, const void *src1, int c1, const int *up, const void *packed_weights,
+                    const float *bias, void *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
+                    int padding_same, int activation, void *stream);
+int nrt_conv1x1_softmax_bf16(const void *x, const void *weights, const float *bias, void *y, long long nvox, int cin, int cout,
+                             int softmax, int activation, void *stream);
+int nrt_softmax_lastdim_bf16(const void *x, void *y, long long n, int channels, void *stream);
+int nrt_maxpool3d_bf16(const void *x, void *y, int batch, const int *shape, int channels, const int *pool, int padding_same,
+                       void *stream);
+int nrt_upsample_concat_bf16(const void *skip, int c0, const void *lo, int c1, void *y, int batch, const int *shape,
+                             const int *up, void *stream);
+int nrt_add_act_affine_bf16(const void *a, const void *b, const float *scale, const float *shift, void *y, long long n,
+                            int channels, int activation, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of the conv stack (what tf.GradientTape derives for neurite/tf/models.py:1345-1347, 1385, 1438,
  * 1506-1508, 1531, 1604; float32, channels-last, stride 1)
  *   nrt_act_bwd_f32        grad_pre = grad_out * act'(y), from the layer OUTPUT y (ELU: y > 0 ? 1 : y + 1)

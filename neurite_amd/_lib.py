@@ -82,6 +82,14 @@ _SIGNATURES = {
     'nrt_maxpool3d_f32': (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _vp]),
     'nrt_upsample_concat_f32': (_i, [_vp, _i, _vp, _i, _vp, _i, _ip, _ip, _vp]),
     'nrt_add_act_affine_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp]),
+    'nrt_conv3d_packed_weight_bytes_bf16': (_sz, [_ip, _i, _i]),
+    'nrt_conv3d_pack_weights_bf16': (_i, [_vp, _i, _ip, _i, _i, _vp, _vp]),
+    'nrt_conv3d_bf16': (_i, [_vp, _i, _vp, _i, _ip, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _vp]),
+    'nrt_conv1x1_softmax_bf16': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp]),
+    'nrt_softmax_lastdim_bf16': (_i, [_vp, _vp, _ll, _i, _vp]),
+    'nrt_maxpool3d_bf16': (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _vp]),
+    'nrt_upsample_concat_bf16': (_i, [_vp, _i, _vp, _i, _vp, _i, _ip, _ip, _vp]),
+    'nrt_add_act_affine_bf16': (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp]),
     'nrt_act_bwd_f32': (_i, [_vp, _vp, _i, _vp, _ll, _vp]),
     'nrt_conv3d_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _i, _i, _ip, _i, _vp]),
     'nrt_conv3d_wgrad2_f32': (_i, [_vp, _i, _vp, _i, _ip, _vp, _vp, _vp, _i, _ip, _i, _ip, _i, _vp]),

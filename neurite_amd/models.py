@@ -14,6 +14,23 @@ one to one.  Forward runs on the HIP kernels of csrc/conv.hip: Conv3D = MFMA imp
 UpSampling3D + concatenate fused into the following convolution's loader and the final 1x1 conv fused
 with the channel softmax.  1-D / 2-D nets are lifted to 3-D with unit leading dimensions.
 Inference only: Dropout is the identity, BatchNormalization uses its moving statistics.
+
+bfloat16 inference (csrc/conv_bf16.hip): a ConvNet whose parameters and buffers are all torch.bfloat16 (`net.bfloat16()`,
+`net.to(dev, torch.bfloat16)`), in eval mode or with grad disabled, runs on bf16 kernels end to end with the semantics of
+Keras' mixed_bfloat16 compute on bf16 variables.  The input op casts the input to bf16; every tensor between kernels, the
+output and every tensor of `return_tensors` are bf16.  Rounding points -- each kernel computes in float32 from the stored bf16
+values and rounds its result to bf16 once (round-to-nearest-even):
+  Conv3D       exact bf16 products, float32 accumulation (v_mfma_f32_16x16x32_bf16), bias and ELU / ReLU in float32, one rounding;
+               other activations and a softmax activation run as a pass of their own over the rounded output (a second rounding)
+  MaxPooling3D, UpSampling3D, concatenate: exact
+  add, Activation, inference BatchNorm (scale and shift formed in float32 from the bf16 parameters), the prior heads: float32, one
+               rounding
+  likelihood + softmax: float32 logits, float32 softmax, one rounding (fused unless the logits are materialised); a stand-alone
+               softmax reads the bf16 logits
+Limits: inference only (a bf16 model asked to record a training graph raises NotImplementedError); float16 / float64 parameters
+and mixed dtypes raise NotImplementedError; `conv_variant` is ignored; `fold_head = False` materialises every layer; the
+float32 folds (pooling, up-sampled decoder half, head) have no bf16 form -- only the up-sample + concatenate in the convolution's
+loader and the 1x1 + softmax head are fused.  A float32 model is unchanged for any input dtype.
 """
 
 import functools
@@ -46,6 +63,22 @@ def _act_code(activation):
         raise NotImplementedError('activation %r is not implemented by the HIP path (%s are; softmax as a layer activation runs as '
                                   'its own kernel)' % (activation, ', '.join(sorted(str(k) for k in _ACTS))))
     return _ACTS[activation]
+
+
+def _p32(t):
+    """device pointer for a float32 entry point (*_f32): any other dtype is refused -- a bf16 buffer read as float32 would be
+    read past its end"""
+    if t is not None and t.dtype != torch.float32:
+        raise NotImplementedError('a %s tensor cannot go to a float32 kernel (bf16 models run on their own kernels: all '
+                                  'parameters bf16, inference)' % t.dtype)
+    return _lib.ptr(t)
+
+
+def _pbf(t):
+    """device pointer for a bf16 entry point (*_bf16)"""
+    if t is not None and t.dtype != torch.bfloat16:
+        raise NotImplementedError('the bf16 kernels take bfloat16 tensors, got %s' % t.dtype)
+    return _lib.ptr(t)
 
 
 def _triple(v, ndims, what):
@@ -183,6 +216,8 @@ class _Conv(nn.Module):
         self._packed_version = None
         self._packed_up2 = None                      # folded weights of the decoder form (see _run), keyed like _packed + c0
         self._packed_up2_version = None
+        self._packed_bf16 = None                     # bf16 weights in v_mfma_f32_16x16x32_bf16 operand order (run_bf16)
+        self._packed_bf16_version = None
         self.fold_backward = True                    # decoder form: differentiate the up-sampled channels on the low-resolution grid
 
     def invalidate_packed(self):
@@ -194,6 +229,8 @@ class _Conv(nn.Module):
         self._packed_version = None
         self._packed_up2 = None
         self._packed_up2_version = None
+        self._packed_bf16 = None
+        self._packed_bf16_version = None
 
     def train(self, mode=True):
         self.invalidate_packed()
@@ -213,8 +250,8 @@ class _Conv(nn.Module):
             n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(self.ksize3), self.cin, self.cout)
             packed = torch.empty(int(n), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_pack_weights_f32(_lib.ptr(self.kernel.detach().contiguous()), _lib.ints(self.ksize3),
-                                                     self.cin, self.cout, _lib.ptr(packed), _lib.stream_ptr(dev))
+                rc = lib.nrt_conv3d_pack_weights_f32(_p32(self.kernel.detach().contiguous()), _lib.ints(self.ksize3),
+                                                     self.cin, self.cout, _p32(packed), _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
             self._packed, self._packed_version = packed, ver
         return self._packed
@@ -231,14 +268,20 @@ class _Conv(nn.Module):
             n = lib.nrt_conv3d_up2_packed_weight_floats(int(c0), self.cin - int(c0), self.cout)
             packed = torch.empty(int(n), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_up2_pack_weights_f32(_lib.ptr(self.kernel.detach().contiguous()), int(c0), self.cin - int(c0),
-                                                         self.cout, _lib.ptr(packed), _lib.stream_ptr(dev))
+                rc = lib.nrt_conv3d_up2_pack_weights_f32(_p32(self.kernel.detach().contiguous()), int(c0), self.cin - int(c0),
+                                                         self.cout, _p32(packed), _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_up2_pack_weights_f32')
             self._packed_up2, self._packed_up2_version = packed, ver
         return self._packed_up2
 
     def forward(self, x, lo=None, up=None, variant=0):
-        """x [B, X, Y, Z, c0]; optional lo [B, X/up, Y/up, Z/up, c1] is nearest-upsampled and concatenated after x."""
+        """x [B, X, Y, Z, c0]; optional lo [B, X/up, Y/up, Z/up, c1] is nearest-upsampled and concatenated after x.
+        bf16 parameters: the bf16 kernels (inference; `variant` is ignored)."""
+        if self.kernel.dtype == torch.bfloat16:
+            if torch.is_grad_enabled() and (x.requires_grad or (lo is not None and lo.requires_grad)
+                                            or self.kernel.requires_grad or self.bias.requires_grad):
+                raise NotImplementedError('%s: bf16 convolutions run inference only (call under torch.no_grad())' % self.layer_name)
+            return self.run_bf16(x, lo, up)
         if torch.is_grad_enabled() and (x.requires_grad or (lo is not None and lo.requires_grad)
                                         or self.kernel.requires_grad or self.bias.requires_grad):
             y = _ConvFn.apply(x, lo, self.kernel, self.bias, self, up, variant, False)
@@ -270,11 +313,11 @@ class _Conv(nn.Module):
         pooled = torch.empty([B] + [v // 2 for v in S] + [self.cout], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             if self.cin == 1:
-                rc = lib.nrt_conv3d_c1_pool_f32(_lib.ptr(x), _lib.ptr(self.kernel.detach().contiguous()), _lib.ptr(self.bias.detach()),
-                                                _lib.ptr(out), _lib.ptr(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
+                rc = lib.nrt_conv3d_c1_pool_f32(_p32(x), _p32(self.kernel.detach().contiguous()), _p32(self.bias.detach()),
+                                                _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
             else:
-                rc = lib.nrt_conv3d_pool_f32(_lib.ptr(x), self.cin, _lib.ptr(self._packed_weights()), _lib.ptr(self.bias.detach()),
-                                             _lib.ptr(out), _lib.ptr(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
+                rc = lib.nrt_conv3d_pool_f32(_p32(x), self.cin, _p32(self._packed_weights()), _p32(self.bias.detach()),
+                                             _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_c1_pool_f32' if self.cin == 1 else 'nrt_conv3d_pool_f32')
         return out, pooled
 
@@ -286,7 +329,7 @@ class _Conv(nn.Module):
             src = head_kernel.detach().reshape(-1, labels).contiguous()
             packed = torch.empty(16 * labels, dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.nrt_conv3d_up2_head_pack_f32(_lib.ptr(src), labels, _lib.ptr(packed), _lib.stream_ptr(dev)),
+                _lib.check(lib.nrt_conv3d_up2_head_pack_f32(_p32(src), labels, _p32(packed), _lib.stream_ptr(dev)),
                            'nrt_conv3d_up2_head_pack_f32')
             self._head_pack, self._head_pack_key = packed, key
         return self._head_pack
@@ -303,10 +346,59 @@ class _Conv(nn.Module):
         out = torch.empty([B] + S + [labels], dtype=torch.float32, device=dev)
         hw = self._packed_head(head_kernel, labels, dev)
         with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_up2_head_f32(_lib.ptr(x), c0, _lib.ptr(lo), c1, _lib.ptr(self._packed_weights_up2(c0)),
-                                             _lib.ptr(self.bias.detach()), _lib.ptr(hw), _lib.ptr(head_bias.detach()), labels,
-                                             _lib.ptr(out), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
+            rc = lib.nrt_conv3d_up2_head_f32(_p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)),
+                                             _p32(self.bias.detach()), _p32(hw), _p32(head_bias.detach()), labels,
+                                             _p32(out), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_up2_head_f32')
+        return out
+
+    def _packed_weights_bf16(self):
+        """the bf16 kernel in the A-operand order of v_mfma_f32_16x16x32_bf16 (nrt_conv3d_pack_weights_bf16); keyed and dropped
+        like _packed (invalidate_packed), plus the dtype"""
+        ver = (self.kernel._version, self.kernel.data_ptr(), self.kernel.device, self.kernel.dtype)
+        if self.training:
+            self._packed_bf16 = None
+        if self._packed_bf16 is None or self._packed_bf16_version != ver:
+            lib = _lib.lib()
+            dev = self.kernel.device
+            n = lib.nrt_conv3d_packed_weight_bytes_bf16(_lib.ints(self.ksize3), self.cin, self.cout)
+            packed = torch.empty(int(n) // 2, dtype=torch.bfloat16, device=dev)
+            with torch.cuda.device(dev):
+                rc = lib.nrt_conv3d_pack_weights_bf16(_pbf(self.kernel.detach().contiguous()), _lib.DT_BF16, _lib.ints(self.ksize3),
+                                                      self.cin, self.cout, _lib.ptr(packed), _lib.stream_ptr(dev))
+            _lib.check(rc, 'nrt_conv3d_pack_weights_bf16')
+            self._packed_bf16, self._packed_bf16_version = packed, ver
+        return self._packed_bf16
+
+    def run_bf16(self, x, lo=None, up=None):
+        """act(conv(concat(x, upsample(lo)))) on bf16 tensors (nrt_conv3d_bf16): exact products, float32 accumulation, bias and
+        ELU / ReLU in float32, one rounding; any other activation as a pass of its own, a softmax activation as its own kernel"""
+        lib = _lib.lib()
+        dev = _lib.require_device(x, lo, self.kernel)
+        x = x.contiguous()
+        c0 = x.shape[-1]
+        c1 = 0 if lo is None else lo.shape[-1]
+        if c0 + c1 != self.cin:
+            raise ValueError('%s expects %d input channels, got %d' % (self.layer_name, self.cin, c0 + c1))
+        B, S = x.shape[0], list(x.shape[1:4])
+        if lo is not None:
+            lo = lo.contiguous()
+            if [S[d] // up[d] for d in range(3)] != list(lo.shape[1:4]) or any(S[d] % up[d] for d in range(3)):
+                raise ValueError('%s: skip %s and up-sampled %s x %s shapes do not match'
+                                 % (self.layer_name, S, list(lo.shape[1:4]), up))
+        O = S if self.padding == 'same' else [S[d] - (self.ksize3[d] - 1) * self.dilation for d in range(3)]
+        out = torch.empty([B] + O + [self.cout], dtype=torch.bfloat16, device=dev)
+        bias = self.bias.detach().to(torch.float32).contiguous()          # exact: every bf16 value is a float32
+        with torch.cuda.device(dev):
+            rc = lib.nrt_conv3d_bf16(_pbf(x), c0, _pbf(lo), c1, _lib.ints(up) if lo is not None else None,
+                                     _lib.ptr(self._packed_weights_bf16()), _lib.ptr(bias), _lib.ptr(out), B, _lib.ints(S),
+                                     _lib.ints(self.ksize3), self.cout, self.dilation, int(self.padding == 'same'),
+                                     self.act if self.act <= _ACT_LAST_FUSED else 0, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_conv3d_bf16')
+        if self.act > _ACT_LAST_FUSED:
+            out = _elementwise_bf16(out, act=self.act)
+        if self.post_softmax:
+            out = _softmax_bf16(out)
         return out
 
     def _run(self, x, lo=None, up=None, variant=0):
@@ -343,8 +435,8 @@ class _Conv(nn.Module):
             raise NotImplementedError('%s: shapes outside the folded decoder kernel' % self.layer_name)
         if folded:
             with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_up2_f32(_lib.ptr(x), c0, _lib.ptr(lo), c1, _lib.ptr(self._packed_weights_up2(c0)),
-                                            _lib.ptr(self.bias.detach()), _lib.ptr(out), B, _lib.ints(S), self.cout,
+                rc = lib.nrt_conv3d_up2_f32(_p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)),
+                                            _p32(self.bias.detach()), _p32(out), B, _lib.ints(S), self.cout,
                                             self.act if self.act <= _ACT_LAST_FUSED else 0, _lib.stream_ptr(dev))
             if not (rc == _lib.NRT_ERR_UNSUPPORTED and variant == 0):       # auto: anything the folded form declines takes the plain GEMM
                 _lib.check(rc, 'nrt_conv3d_up2_f32')
@@ -352,9 +444,9 @@ class _Conv(nn.Module):
                     out = _elementwise(out, act=self.act)
                 return out
         with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_f32(_lib.ptr(x), c0, _lib.ptr(lo), c1, _lib.ints(up) if lo is not None else None,
-                                    _lib.ptr(w), _lib.ptr(self._packed_weights()), _lib.ptr(self.bias.detach()),
-                                    _lib.ptr(out), B, _lib.ints(S), _lib.ints(self.ksize3), self.cout, self.dilation,
+            rc = lib.nrt_conv3d_f32(_p32(x), c0, _p32(lo), c1, _lib.ints(up) if lo is not None else None,
+                                    _p32(w), _p32(self._packed_weights()), _p32(self.bias.detach()),
+                                    _p32(out), B, _lib.ints(S), _lib.ints(self.ksize3), self.cout, self.dilation,
                                     int(self.padding == 'same'), self.act if self.act <= _ACT_LAST_FUSED else 0, int(variant),
                                     _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_f32')
@@ -389,7 +481,7 @@ def _elementwise(a, b=None, scale=None, shift=None, act=0, mul=False):
     b = None if b is None else b.contiguous()
     y = torch.empty_like(a)
     with torch.cuda.device(dev):
-        rc = lib.nrt_add_act_affine_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y),
+        rc = lib.nrt_add_act_affine_f32(_p32(a), _p32(b), _p32(scale), _p32(shift), _p32(y),
                                         a.numel(), a.shape[-1], int(act), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_add_act_affine_f32')
     return y
@@ -404,7 +496,7 @@ def _maxpool(x, pool3, padding):
     O = [(S[d] + pool3[d] - 1) // pool3[d] if same else S[d] // pool3[d] for d in range(3)]
     y = torch.empty([B] + O + [C], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_maxpool3d_f32(_lib.ptr(x), _lib.ptr(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same),
+        rc = lib.nrt_maxpool3d_f32(_p32(x), _p32(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same),
                                    _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_maxpool3d_f32')
     return y
@@ -423,7 +515,7 @@ def _upsample_concat(skip, lo, up3):
             raise ValueError('concatenate: shapes %s and %s do not match' % (list(skip.shape[1:4]), S))
     y = torch.empty([B] + S + [c0 + c1], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_upsample_concat_f32(_lib.ptr(skip), c0, _lib.ptr(lo), c1, _lib.ptr(y), B, _lib.ints(S),
+        rc = lib.nrt_upsample_concat_f32(_p32(skip), c0, _p32(lo), c1, _p32(y), B, _lib.ints(S),
                                          _lib.ints(up3), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_upsample_concat_f32')
     return y
@@ -440,7 +532,7 @@ def _conv1x1_softmax(x, kernel, bias, softmax, act):
     if softmax and fused != int(act):
         raise NotImplementedError('a 1x1x1 convolution with a non-fused activation followed by the channel softmax')
     with torch.cuda.device(dev):
-        rc = lib.nrt_conv1x1_softmax_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias.detach()), _lib.ptr(y),
+        rc = lib.nrt_conv1x1_softmax_f32(_p32(x), _p32(w), _p32(bias.detach()), _p32(y),
                                          x.numel() // cin, cin, cout, int(softmax), fused, _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_conv1x1_softmax_f32')
     return y if fused == int(act) else _elementwise(y, act=int(act))
@@ -452,9 +544,86 @@ def _softmax(x):
     x = x.contiguous()
     y = torch.empty_like(x)
     with torch.cuda.device(dev):
-        rc = lib.nrt_softmax_lastdim_f32(_lib.ptr(x), _lib.ptr(y), x.numel() // x.shape[-1], x.shape[-1],
+        rc = lib.nrt_softmax_lastdim_f32(_p32(x), _p32(y), x.numel() // x.shape[-1], x.shape[-1],
                                          _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_softmax_lastdim_f32')
+    return y
+
+
+# bf16 forms of the glue layers (csrc/conv_bf16.hip): float32 arithmetic from the bf16 operands, one rounding; pooling and
+# up-sampling exact
+def _elementwise_bf16(a, b=None, scale=None, shift=None, act=0, mul=False):
+    """act(a + b) * scale + shift, or with mul act(a) * b; scale / shift float32"""
+    if mul:
+        act = int(act) | _ACT_MUL_B
+    lib = _lib.lib()
+    dev = _lib.require_device(a, b)
+    a = a.contiguous()
+    b = None if b is None else b.contiguous()
+    y = torch.empty_like(a)
+    with torch.cuda.device(dev):
+        rc = lib.nrt_add_act_affine_bf16(_pbf(a), _pbf(b), _p32(scale), _p32(shift), _pbf(y), a.numel(), a.shape[-1], int(act),
+                                         _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_add_act_affine_bf16')
+    return y
+
+
+def _maxpool_bf16(x, pool3, padding):
+    lib = _lib.lib()
+    dev = _lib.require_device(x)
+    x = x.contiguous()
+    B, S, C = x.shape[0], list(x.shape[1:4]), x.shape[-1]
+    same = padding == 'same'
+    O = [(S[d] + pool3[d] - 1) // pool3[d] if same else S[d] // pool3[d] for d in range(3)]
+    y = torch.empty([B] + O + [C], dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.nrt_maxpool3d_bf16(_pbf(x), _pbf(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same), _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_maxpool3d_bf16')
+    return y
+
+
+def _upsample_concat_bf16(skip, lo, up3):
+    lib = _lib.lib()
+    dev = _lib.require_device(skip, lo)
+    lo = lo.contiguous()
+    B, S1, c1 = lo.shape[0], list(lo.shape[1:4]), lo.shape[-1]
+    S = [S1[d] * up3[d] for d in range(3)]
+    c0 = 0 if skip is None else skip.shape[-1]
+    if skip is not None:
+        skip = skip.contiguous()
+        if list(skip.shape[1:4]) != S:
+            raise ValueError('concatenate: shapes %s and %s do not match' % (list(skip.shape[1:4]), S))
+    y = torch.empty([B] + S + [c0 + c1], dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.nrt_upsample_concat_bf16(_pbf(skip), c0, _pbf(lo), c1, _pbf(y), B, _lib.ints(S), _lib.ints(up3), _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_upsample_concat_bf16')
+    return y
+
+
+def _conv1x1_softmax_bf16(x, kernel, bias, softmax):
+    """the likelihood layer (linear 1x1x1 convolution, cout <= 64) with the channel softmax optionally fused: float32 logits"""
+    lib = _lib.lib()
+    dev = _lib.require_device(x, kernel)
+    x = x.contiguous()
+    cin, cout = kernel.shape[-2], kernel.shape[-1]
+    y = torch.empty(list(x.shape[:-1]) + [cout], dtype=torch.bfloat16, device=dev)
+    w = kernel.detach().reshape(cin, cout).contiguous()
+    b = bias.detach().to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        rc = lib.nrt_conv1x1_softmax_bf16(_pbf(x), _pbf(w), _lib.ptr(b), _pbf(y), x.numel() // cin, cin, cout, int(softmax), 0,
+                                          _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_conv1x1_softmax_bf16')
+    return y
+
+
+def _softmax_bf16(x):
+    lib = _lib.lib()
+    dev = _lib.require_device(x)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        rc = lib.nrt_softmax_lastdim_bf16(_pbf(x), _pbf(y), x.numel() // x.shape[-1], x.shape[-1], _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_softmax_lastdim_bf16')
     return y
 
 
@@ -470,7 +639,7 @@ def _act_bwd(g, y, act):
     g = g.contiguous()
     d = torch.empty_like(g)
     with torch.cuda.device(dev):
-        rc = lib.nrt_act_bwd_f32(_lib.ptr(g), _lib.ptr(y), int(act), _lib.ptr(d), g.numel(), _lib.stream_ptr(dev))
+        rc = lib.nrt_act_bwd_f32(_p32(g), _p32(y), int(act), _p32(d), g.numel(), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_act_bwd_f32')
     return d
 
@@ -483,7 +652,7 @@ def _upsample_sum(g, c_off, c, lo_shape, up3):
     B = g.shape[0]
     d = torch.empty([B] + list(lo_shape) + [c], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_upsample_sum_f32(_lib.ptr(g), g.shape[-1], int(c_off), _lib.ptr(d), int(c), B, _lib.ints(lo_shape),
+        rc = lib.nrt_upsample_sum_f32(_p32(g), g.shape[-1], int(c_off), _p32(d), int(c), B, _lib.ints(lo_shape),
                                       _lib.ints(up3), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_upsample_sum_f32')
     return d
@@ -500,7 +669,7 @@ def _conv_dgrad(dpre, wpart, ksize3, dilation):
         dpre = dpre.contiguous()
         out = torch.empty(list(dpre.shape[:-1]) + [cpart], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = lib.nrt_conv1x1_softmax_f32(_lib.ptr(dpre), _lib.ptr(wt), None, _lib.ptr(out), dpre.numel() // cout, cout, cpart, 0, 0,
+            rc = lib.nrt_conv1x1_softmax_f32(_p32(dpre), _p32(wt), None, _p32(out), dpre.numel() // cout, cout, cpart, 0, 0,
                                              _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv1x1_softmax_f32 (dgrad)')
         return out
@@ -509,9 +678,9 @@ def _conv_dgrad(dpre, wpart, ksize3, dilation):
     B, S = dpre.shape[0], list(dpre.shape[1:4])
     out = torch.empty([B] + S + [cpart], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_pack_weights_f32(_lib.ptr(wt), _lib.ints(ksize3), cout, cpart, _lib.ptr(packed), _lib.stream_ptr(dev))
+        rc = lib.nrt_conv3d_pack_weights_f32(_p32(wt), _lib.ints(ksize3), cout, cpart, _p32(packed), _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-        rc = lib.nrt_conv3d_f32(_lib.ptr(dpre), cout, None, 0, None, _lib.ptr(wt), _lib.ptr(packed), None, _lib.ptr(out), B,
+        rc = lib.nrt_conv3d_f32(_p32(dpre), cout, None, 0, None, _p32(wt), _p32(packed), None, _p32(out), B,
                                 _lib.ints(S), _lib.ints(ksize3), cpart, int(dilation), 1, 0, 0, _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_conv3d_f32 (dgrad)')
     return out
@@ -567,7 +736,7 @@ def _space_to_depth2(dpre):
     B, S, C = dpre.shape[0], list(dpre.shape[1:4]), dpre.shape[-1]
     y = torch.empty([B] + [s // 2 for s in S] + [8 * C], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_space_to_depth2_f32(_lib.ptr(dpre), _lib.ptr(y), B, _lib.ints(S), C, _lib.stream_ptr(dev))
+        rc = lib.nrt_space_to_depth2_f32(_p32(dpre), _p32(y), B, _lib.ints(S), C, _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_space_to_depth2_f32')
     return y
 
@@ -585,9 +754,9 @@ def _conv_dgrad_lo_folded(s2d, k_lo):
     B, S1 = s2d.shape[0], list(s2d.shape[1:4])
     out = torch.empty([B] + S1 + [c1], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_pack_weights_f32(_lib.ptr(wf), _lib.ints(k3), 8 * cout, c1, _lib.ptr(packed), _lib.stream_ptr(dev))
+        rc = lib.nrt_conv3d_pack_weights_f32(_p32(wf), _lib.ints(k3), 8 * cout, c1, _p32(packed), _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-        rc = lib.nrt_conv3d_s2d_taps_f32(_lib.ptr(s2d), cout, _lib.ptr(packed), _lib.ptr(out), B, _lib.ints(S1), c1, _lib.stream_ptr(dev))
+        rc = lib.nrt_conv3d_s2d_taps_f32(_p32(s2d), cout, _p32(packed), _p32(out), B, _lib.ints(S1), c1, _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_conv3d_s2d_taps_f32')
     return out
 
@@ -599,7 +768,7 @@ def _conv_wgrad_lo_folded(lo, s2d, cout):
     c1 = lo.shape[-1]
     dwf = torch.zeros(8, 8, c1, cout, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_wgrad_s2d_f32(_lib.ptr(lo), _lib.ptr(s2d), _lib.ptr(dwf), lo.shape[0], _lib.ints(list(lo.shape[1:4])), c1,
+        rc = lib.nrt_conv3d_wgrad_s2d_f32(_p32(lo), _p32(s2d), _p32(dwf), lo.shape[0], _lib.ints(list(lo.shape[1:4])), c1,
                                           cout, _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_conv3d_wgrad_s2d_f32')
     return _unfold_wgrad(dwf)
@@ -636,7 +805,7 @@ class _ConvFn(torch.autograd.Function):
             padded = torch.empty([dpre.shape[0]] + S + [dpre.shape[-1]], dtype=dpre.dtype, device=dev)
             dpre = dpre.contiguous()
             with torch.cuda.device(dev):
-                rc = lib.nrt_pad3d(_lib.ptr(dpre), _lib.ptr(padded), dpre.shape[0], _lib.ints(list(dpre.shape[1:4])), _lib.ints(pb),
+                rc = lib.nrt_pad3d(_p32(dpre), _p32(padded), dpre.shape[0], _lib.ints(list(dpre.shape[1:4])), _lib.ints(pb),
                                    _lib.ints(S), dpre.shape[-1] * 4, 0, _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_pad3d')
             dpre = padded
@@ -658,7 +827,7 @@ class _ConvFn(torch.autograd.Function):
                 db = torch.zeros(mod.cout, dtype=torch.float32, device=dev)
                 xs = x.contiguous()
                 with torch.cuda.device(dev):
-                    rc = lib.nrt_conv3d_wgrad_f32(_lib.ptr(xs), _lib.ptr(dpre), _lib.ptr(dws), _lib.ptr(db), xs.shape[0],
+                    rc = lib.nrt_conv3d_wgrad_f32(_p32(xs), _p32(dpre), _p32(dws), _p32(db), xs.shape[0],
                                                   _lib.ints(list(xs.shape[1:4])), c0, mod.cout, _lib.ints(mod.ksize3), 1,
                                                   _lib.stream_ptr(dev))
                 _lib.check(rc, 'nrt_conv3d_wgrad_f32')
@@ -674,8 +843,8 @@ class _ConvFn(torch.autograd.Function):
                 xs, lo_c = _upsample_concat(xs, lo_c, up), None          # a channel quad would straddle the two sources
             B, S = xs.shape[0], list(xs.shape[1:4])
             with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_wgrad2_f32(_lib.ptr(xs), xs.shape[-1], _lib.ptr(lo_c), 0 if lo_c is None else lo_c.shape[-1],
-                                               _lib.ints(up) if lo_c is not None else None, _lib.ptr(dpre), _lib.ptr(dw), _lib.ptr(db),
+                rc = lib.nrt_conv3d_wgrad2_f32(_p32(xs), xs.shape[-1], _p32(lo_c), 0 if lo_c is None else lo_c.shape[-1],
+                                               _lib.ints(up) if lo_c is not None else None, _p32(dpre), _p32(dw), _p32(db),
                                                B, _lib.ints(S), mod.cout, _lib.ints(mod.ksize3), mod.dilation, _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_wgrad2_f32')
         k5 = kernel.detach()
@@ -712,7 +881,7 @@ class _MaxPoolFn(torch.autograd.Function):
         g = g.contiguous()
         dx = torch.empty_like(x)
         with torch.cuda.device(dev):
-            rc = lib.nrt_maxpool3d_bwd_f32(_lib.ptr(x), _lib.ptr(g), _lib.ptr(dx), x.shape[0], _lib.ints(list(x.shape[1:4])),
+            rc = lib.nrt_maxpool3d_bwd_f32(_p32(x), _p32(g), _p32(dx), x.shape[0], _lib.ints(list(x.shape[1:4])),
                                            x.shape[-1], _lib.ints(pool3), int(padding == 'same'), _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_maxpool3d_bwd_f32')
         return dx, None, None
@@ -746,7 +915,7 @@ def _head_grads(x, kernel, mod, dz, needs):
         dw = torch.zeros_like(kernel, dtype=torch.float32)
         db = torch.zeros(mod.cout, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_wgrad_f32(_lib.ptr(xin), _lib.ptr(dz), _lib.ptr(dw), _lib.ptr(db), xin.shape[0],
+            rc = lib.nrt_conv3d_wgrad_f32(_p32(xin), _p32(dz), _p32(dw), _p32(db), xin.shape[0],
                                           _lib.ints(list(xin.shape[1:4])), mod.cin, mod.cout, _lib.ints(mod.ksize3), 1,
                                           _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_wgrad_f32')
@@ -811,7 +980,7 @@ class _HeadFn(torch.autograd.Function):
         g = g.contiguous()
         dz = torch.empty_like(y)
         with torch.cuda.device(dev):
-            rc = lib.nrt_softmax_bwd_f32(_lib.ptr(y), _lib.ptr(g), _lib.ptr(dz), y.numel() // y.shape[-1], y.shape[-1],
+            rc = lib.nrt_softmax_bwd_f32(_p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1],
                                          _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_softmax_bwd_f32')
         return _head_grads(x, kernel, ctx.mod, dz, ctx.needs_input_grad) + (None,)
@@ -839,7 +1008,7 @@ class _ChannelScaleFn(torch.autograd.Function):
         zero = torch.zeros(x.shape[-1], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             for b in range(x.shape[0]):
-                rc = lib.nrt_add_act_affine_f32(_lib.ptr(x[b]), None, _lib.ptr(scale[b]), _lib.ptr(zero), _lib.ptr(y[b]), x[b].numel(),
+                rc = lib.nrt_add_act_affine_f32(_p32(x[b]), None, _p32(scale[b]), _p32(zero), _p32(y[b]), x[b].numel(),
                                                 x.shape[-1], 0, _lib.stream_ptr(dev))
                 _lib.check(rc, 'nrt_add_act_affine_f32')
         return y
@@ -899,7 +1068,7 @@ def _channel_sums(a, b=None):
     C = a.shape[-1]
     out = torch.zeros(C, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_channel_sums_f32(_lib.ptr(a), _lib.ptr(b), a.numel() // C, C, _lib.ptr(out), _lib.stream_ptr(dev))
+        rc = lib.nrt_channel_sums_f32(_p32(a), _p32(b), a.numel() // C, C, _p32(out), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_channel_sums_f32')
     return out
 
@@ -945,7 +1114,7 @@ class _BatchNormFn(torch.autograd.Function):
             C0 = (-scale * m1 + scale * inv * m2 * mean).contiguous()
             dx = torch.empty_like(x)
             with torch.cuda.device(dev):
-                rc = lib.nrt_channel_axpby_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(A), _lib.ptr(B), _lib.ptr(C0), _lib.ptr(dx),
+                rc = lib.nrt_channel_axpby_f32(_p32(g), _p32(x), _p32(A), _p32(B), _p32(C0), _p32(dx),
                                                x.numel(), C, _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_channel_axpby_f32')
         return dx, dgamma, dbeta, None
@@ -967,7 +1136,7 @@ class _SoftmaxFn(torch.autograd.Function):
         g = g.contiguous()
         dz = torch.empty_like(y)
         with torch.cuda.device(dev):
-            rc = lib.nrt_softmax_bwd_f32(_lib.ptr(y), _lib.ptr(g), _lib.ptr(dz), y.numel() // y.shape[-1], y.shape[-1],
+            rc = lib.nrt_softmax_bwd_f32(_p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1],
                                          _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_softmax_bwd_f32')
         return dz
@@ -998,7 +1167,7 @@ class ConvNet(nn.Module):
             self.layers_by_name[k] = m
         self.layer_names = [op['name'] for op in ops]
         self.output_shape = ops[-1].get('shape') if ops else None
-        self.conv_variant = 0                       # 0 auto, 1 direct, 2 MFMA (tests / tuning)
+        self.conv_variant = 0                       # 0 auto, 1 direct, 2 MFMA (tests / tuning); float32 only, bf16 ignores it
         self.fold_head = True                       # inference: last decoder convolution + likelihood + soft-max as ONE kernel where it applies
         # {conv layer: the soft-max likelihood that is its ONLY consumer}: candidates for nrt_conv3d_up2_head_f32 (models.py:1545-1605)
         uses = {}
@@ -1285,6 +1454,25 @@ class ConvNet(nn.Module):
         inputs = [op['name'] for op in sorted((o for o in self.ops if o['kind'] == 'input'), key=lambda o: o['index'])]
         return {'name': self.name, 'inputs': inputs, 'outputs': [out], 'layers': [l for l in layers if l['name'] in seen]}
 
+    def _compute_dtype(self):
+        """torch.float32 or torch.bfloat16: the dtype every parameter and floating-point buffer shares.  Any other dtype, or a mix,
+        raises NotImplementedError naming the first layer (graph order) that breaks the rule."""
+        first = None
+        for name in self.layer_names:
+            m = self.layers_by_name[name] if name in self.layers_by_name else None
+            if m is None:
+                continue
+            for t in list(m.parameters(recurse=False)) + [b for b in m.buffers(recurse=False) if b.is_floating_point()]:
+                if t.dtype not in (torch.float32, torch.bfloat16):
+                    raise NotImplementedError('%s: %s parameters are not supported (float32, or bfloat16 for inference)'
+                                              % (name, t.dtype))
+                if first is None:
+                    first = t.dtype
+                elif t.dtype != first:
+                    raise NotImplementedError('%s: %s parameters in a %s network; convert the whole model (net.float() or '
+                                              'net.bfloat16())' % (name, t.dtype, first))
+        return first or torch.float32
+
     def _affine(self, bn):
         scale = bn.gamma.detach() / torch.sqrt(bn.moving_variance + bn.epsilon)
         shift = bn.beta.detach() - bn.moving_mean * scale
@@ -1299,6 +1487,10 @@ class ConvNet(nn.Module):
             xs = [inputs]
         if len(xs) != len(self.input_shapes):
             raise ValueError('%s expects %d input(s), got %d' % (self.name, len(self.input_shapes), len(xs)))
+        bf16 = self._compute_dtype() == torch.bfloat16
+        if bf16 and self.training and torch.is_grad_enabled():
+            raise NotImplementedError('%s: bfloat16 networks run inference only (model.eval() or torch.no_grad()); train in '
+                                      'float32' % self.name)
         for x, shp in zip(xs, self.input_shapes):
             _lib.require_device(x)
             if tuple(x.shape[1:]) != tuple(shp):
@@ -1306,6 +1498,8 @@ class ConvNet(nn.Module):
         nd = self.ndims
         t = {}
         keep = set(return_tensors or [])
+        if bf16:
+            return self._forward_bf16(xs, keep, return_tensors)
         if self.training and torch.is_grad_enabled():
             return self._forward_train(xs, keep, return_tensors)
         with torch.no_grad():
@@ -1373,6 +1567,70 @@ class ConvNet(nn.Module):
             return {k: _unlift(t[k], nd) for k in keep}
         return _unlift(t[self.output_name], nd)
 
+
+    def _forward_bf16(self, xs, keep, return_tensors):
+        """inference of a bf16 network on the bf16 kernels (module docstring: rounding points).  With fold_head every merge whose
+        only reader is the next convolution runs in that convolution's loader and the likelihood + softmax as one kernel; without
+        it every layer is materialised."""
+        nd = self.ndims
+        t = {}
+        fold = self.fold_head
+        with torch.no_grad():
+            for op in self.ops:
+                kind, name = op['kind'], op['name']
+                if kind == 'input':
+                    t[name] = _lift(xs[op['index']].to(torch.bfloat16), nd)
+                elif kind == 'input_concat':
+                    t[name] = torch.cat([t[s] for s in op['src']], -1).contiguous()      # host glue (rare), exact
+                elif kind == 'conv':
+                    m = self.layers_by_name[name]
+                    src, lo = t[op['src']], (t[op['lo']] if op.get('lo') else None)
+                    if lo is not None and t.get(op['merge']) is not None:
+                        src, lo = t[op['merge']], None                                    # the materialised concatenation
+                    t[name] = m.run_bf16(src, lo, op.get('up'))
+                elif kind == 'dropout':
+                    t[name] = t[op['src']]
+                elif kind == 'maxpool':
+                    t[name] = _maxpool_bf16(t[op['src']], op['pool'], op['padding'])
+                elif kind == 'upsample':
+                    t[name] = _upsample_concat_bf16(None, t[op['src']], op['up'])
+                elif kind == 'merge':
+                    if op.get('fused') and fold and name not in keep:
+                        t[name] = None            # read by the next convolution's loader
+                    else:
+                        t[name] = _upsample_concat_bf16(t[op['skip']], t[op['lo']], op['up'])
+                elif kind == 'add':
+                    t[name] = _elementwise_bf16(t[op['a']], t[op['b']])
+                elif kind == 'activation':
+                    t[name] = _elementwise_bf16(t[op['src']], act=_EW_ACTS[op['activation']])
+                elif kind == 'multiply':
+                    t[name] = _elementwise_bf16(t[op['a']], t[op['b']], mul=True)
+                elif kind == 'bn':
+                    bn = self.layers_by_name[name]
+                    scale = bn.gamma.detach().float() / torch.sqrt(bn.moving_variance.float() + bn.epsilon)
+                    shift = bn.beta.detach().float() - bn.moving_mean.float() * scale
+                    t[name] = _elementwise_bf16(t[op['src']], scale=scale.contiguous(), shift=shift.contiguous())
+                elif kind == 'likelihood':
+                    m = self.layers_by_name[name]
+                    if op.get('fuse_softmax') and fold and name not in keep:
+                        t[name] = None
+                        t[op['pred_name']] = _conv1x1_softmax_bf16(t[op['src']], m.kernel, m.bias, True)
+                    elif m.cout <= 64 and tuple(m.ksize3) == (1, 1, 1):
+                        t[name] = _conv1x1_softmax_bf16(t[op['src']], m.kernel, m.bias, False)
+                    else:
+                        t[name] = m.run_bf16(t[op['src']])
+                elif kind == 'prediction':
+                    if name in t and t[name] is not None:
+                        pass                                    # produced by the fused likelihood
+                    elif op['activation'] == 'softmax':
+                        t[name] = _softmax_bf16(t[op['src']])
+                    else:
+                        t[name] = _elementwise_bf16(t[op['src']], act=_act_code(op['activation']))
+                else:
+                    raise RuntimeError('unknown op ' + kind)
+        if return_tensors:
+            return {k: _unlift(t[k], nd) for k in keep}
+        return _unlift(t[self.output_name], nd)
 
     def _forward_train(self, xs, keep, return_tensors):
         """model.train(): the same graph with every op recorded for autograd (csrc/conv_bwd.hip); the likelihood conv
