@@ -220,7 +220,8 @@ int nrt_dice_mean_f32(const float *dice, const float *weights, int nlabels, int 
  *   moving [batch, vol_shape, nlabels], loc [batch, out_shape, 3] (or NULL for NRT_LOC_LINSPACE),
  *   fixed  [batch, out_shape, nlabels];  warped [batch, out_shape, nlabels] or NULL (not written).
  *   sums / dice / minmax as nrt_dice_soft_f32 with y_true = fixed, y_pred = warped.
- * 3-D only, nlabels in {4, 8, 16, 32, 64, 128, 256}.  tune: tile shape knob (0 = default).
+ * 3-D only, nlabels a multiple of 4 in [4, 256] (4 * 2^k labels: lane groups of nlabels / 4 lanes; any other count: lane groups
+ * of the next power of two, the lanes past nlabels / 4 idle).  tune: tile shape knob (0 = default).
  * Size limits (NRT_ERR_UNSUPPORTED beyond them; use nrt_interpn_f32 + nrt_dice_soft_f32): one batch entry of moving /
  * fixed / warped below 4 GiB, shape[0] * shape[1] and shape[2] below 2^24 for both shapes (32-bit row offsets, 24-bit
  * index multiplies).
@@ -244,7 +245,8 @@ int nrt_warp_dice_soft_bf16(const void *moving, const float *loc, const void *fi
                             float *minmax, int tune, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Name of the kernel instantiation nrt_warp_dice_soft_f32 launches for these arguments, as a profiler prints it (e.g.
- * "warp_dice_tile<8, 1, false, 3, float>"); "" for arguments the entry point rejects.  The returned buffer is thread-local.
+ * "warp_dice_tile<8, 1, false, 3, float>", "warp_dice_tile_pad<8, 1, false, 3, float>" for 24 labels); "" for arguments the entry
+ * point rejects.  The returned buffer is thread-local.
  * Measurement plumbing (bench.py joins its timing with the counter passes under profiles/ by this name); no reference counterpart. */
 const char *nrt_warp_dice_kernel_name(const int *out_shape, const int *vol_shape, int nlabels, int batch, int loc_mode, int has_fill,
                                       int store, int want_minmax, int tune);
@@ -530,7 +532,8 @@ int nrt_dice_soft_bwd_norm_f32(const float *y_true, const float *y_pred, const f
  * registers, forms d dice / d warped from `sums` (as returned by the forward) and grad_dice [batch, L], and writes
  * grad_loc [batch, out_shape, 3] only.  `warped` and its gradient never touch HBM.  At 32 float32 labels on volumes that take the
  * forward's x-march schedule it runs on the forward's wave-cache gather (csrc/fused_wc.h, BWD; environment NRT_BWD_WC=0 selects the
- * register-pipelined kernel of rounds 2-4: same bits); the grad_loc of nrt_interpn_bwd_f32 at 32 channels likewise. */
+ * register-pipelined kernel of rounds 2-4: same bits); the grad_loc of nrt_interpn_bwd_f32 at 32 channels likewise.  nlabels: the
+ * forward's counts (a multiple of 4 in [4, 256]); counts that are not 4 * 2^k run on padded lane groups, without atomics. */
 int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, const float *fixed, const float *sums,
                           const float *grad_dice, float *grad_loc, const int *vol_shape, const int *out_shape,
                           int nlabels, int batch, long long loc_batch_stride, int loc_mode, int has_fill,

@@ -666,6 +666,126 @@ __global__ __launch_bounds__(256) void warp_dice_bwd_rows(InterpBwdArgs ba, cons
     }
 }
 
+// warp_dice_bwd_rows for label counts L = 4 Gr that are not 4 * 2^k: lane groups of the next power of two G >= Gr (the forward's
+// warp_dice_tile_pad layout), rows L values apart.  A lane lg >= Gr loads nothing and adds an exact zero to each axis' xor-shuffle
+// sum, so the gradient does not depend on G.  Same voxel schedules (grid-stride, or the x-march for G == 8), no atomics.
+template <int G, int MODE>
+__global__ __launch_bounds__(256) void warp_dice_bwd_rows_pad(InterpBwdArgs ba, const float *__restrict__ fixed,
+                                                              const float *__restrict__ sums,
+                                                              const float *__restrict__ gdice, float eps, int Gr) {
+    constexpr int D = 3;
+    constexpr int NG = 256 / G;
+    const int L = Gr * 4;
+    const InterpArgs &a = ba.f;
+    const bool xm = G == 8 && ba.tg.x_march;
+    int b = blockIdx.y, xm_x0 = 0, xm_y0 = 0, xm_z0 = 0, xm_len = 0;
+    if (xm) {
+        unsigned prow;
+        if (!xmarch_block(ba.tg, a.O[0], b, prow, xm_x0, xm_y0, xm_z0, xm_len)) return;
+    }
+    const nrt_f4 *vol = (const nrt_f4 *)((const float *)a.vol + (long long)b * a.vol_bs);
+    const float *locb = a.loc + (long long)b * a.loc_bs;
+    const nrt_f4 *fix = (const nrt_f4 *)(fixed + (long long)b * a.out_bs);
+    float *gl = ba.gloc + (long long)b * a.nout * D;
+    const int lg = threadIdx.x % G;
+    const unsigned g = threadIdx.x / G;
+    const bool lane_live = lg < Gr;
+    const int Y = a.S[1], Z = a.S[2];
+    float ca[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (lane_live) {
+        const float *s = sums + (long long)b * 3 * L;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int l = lg * 4 + k;
+            const float num = 2.0f * s[l] + eps, den = s[L + l] + s[2 * L + l] + eps;
+            const float gd = gdice[(long long)b * L + l];
+            if (den != 0.0f) { ca[k] = 2.0f * gd / den; cb[k] = -2.0f * gd * num / (den * den); }
+        }
+    }
+    constexpr int U = 2;
+    const unsigned ngroups = gridDim.x * NG;
+    unsigned niter = (a.nout + ngroups * U - 1) / (ngroups * U);
+    if (xm) niter = ((unsigned)xm_len + U - 1) / U;
+    for (unsigned it = 0; it < niter; ++it) {
+        unsigned q[U];
+        bool live[U], oob[U];
+        float w0[U][3], w1[U][3], m[U][3];
+        nrt_f4 t[U], v[U][8];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            unsigned qq;
+            if (xm) {
+                const int x = xm_x0 + (int)(it * U + u), y = xm_y0 + (int)(g >> ba.tg.ltz), z = xm_z0 + (int)(g & ((1u << ba.tg.ltz) - 1u));
+                const bool in = x < xm_x0 + xm_len && y < a.O[1] && z < a.O[2];
+                qq = in ? ((unsigned)x * (unsigned)a.O[1] + (unsigned)y) * (unsigned)a.O[2] + (unsigned)z : 0xffffffffu;
+            } else {
+                qq = blockIdx.x * NG + g + (it * U + u) * ngroups;
+            }
+            live[u] = qq < a.nout;
+            q[u] = live[u] ? qq : a.nout - 1;
+            int qd[NRT_MAXD];
+            float p[NRT_MAXD];
+            decode<D>(a, q[u], qd);
+            load_loc<D, MODE>(a, locb, q[u], qd, p);
+            oob[u] = a.has_fill ? out_of_bounds<D>(a, p) : false;
+            int i0[3], i1[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                corner_1d(p[d], a.S[d], i0[d], i1[d], w0[u][d], w1[u][d]);
+                m[u][d] = (p[d] >= 0.0f && p[d] <= (float)(a.S[d] - 1)) ? 1.0f : 0.0f;
+            }
+            t[u] = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) v[u][corner] = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
+            if (lane_live) {
+                t[u] = fix[(long long)q[u] * Gr + lg];
+#pragma unroll
+                for (int corner = 0; corner < 8; ++corner) {
+                    const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
+                    const long long idx = ((long long)(bx ? i1[0] : i0[0]) * Y + (by ? i1[1] : i0[1])) * Z + (bz ? i1[2] : i0[2]);
+                    v[u][corner] = vol[idx * Gr + lg];
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            nrt_f4 wp = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) {
+                const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
+                const float wt = (bx ? w1[u][0] : w0[u][0]) * (by ? w1[u][1] : w0[u][1]) * (bz ? w1[u][2] : w0[u][2]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) wp[k] += wt * v[u][corner][k];
+            }
+            nrt_f4 gq;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) gq[k] = (oob[u] || !live[u]) ? 0.0f : ca[k] * t[u][k] + cb[k] * wp[k];
+            float gacc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) {
+                const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
+                const float wx = bx ? w1[u][0] : w0[u][0], wy = by ? w1[u][1] : w0[u][1], wz = bz ? w1[u][2] : w0[u][2];
+                const nrt_f4 c = v[u][corner];
+                const float dot = gq[0] * c[0] + gq[1] * c[1] + gq[2] * c[2] + gq[3] * c[3];
+                gacc[0] += dot * (bx ? m[u][0] : -m[u][0]) * wy * wz;
+                gacc[1] += dot * wx * (by ? m[u][1] : -m[u][1]) * wz;
+                gacc[2] += dot * wx * wy * (bz ? m[u][2] : -m[u][2]);
+            }
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                if (!lane_live) gacc[d] = 0.0f;           // exact zeros (a NaN weight times a zero row would not be)
+#pragma unroll
+                for (int off = 1; off < G; off <<= 1) gacc[d] += __shfl_xor(gacc[d], off, 64);
+            }
+            if (live[u] && lg == 0) {
+                float *dst = gl + (long long)q[u] * 3;
+                dst[0] = gacc[0]; dst[1] = gacc[1]; dst[2] = gacc[2];
+            }
+        }
+    }
+}
+
 // The same backward for 32 labels on the x-march schedule, software-pipelined like the fused forward (fused.hip): the rows of
 // x-plane p + 1 are requested before the gradient of plane p is formed, the location of plane p + 2 before those rows, the
 // voxel's position comes from the block's patch (no division), so the queue of the memory pipeline never drains.  The
@@ -1383,8 +1503,10 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
                                      float laplace_smoothing, void *stream) {
     if (!moving || !loc || !fixed || !sums || !grad_dice || !grad_loc) return NRT_ERR_INVALID_ARG;
     if (loc_mode != NRT_LOC_ABSOLUTE && loc_mode != NRT_LOC_SHIFT) return NRT_ERR_INVALID_ARG;
-    const int G = nlabels / 4;
-    if (nlabels % 4 || !(G == 1 || G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64)) return NRT_ERR_UNSUPPORTED;
+    if (nlabels < 4 || nlabels > 256 || nlabels % 4) return NRT_ERR_UNSUPPORTED;
+    const int Gr = nlabels / 4;
+    int G = 1;                                                    // lanes per voxel: the next power of two >= L / 4
+    while (G < Gr) G <<= 1;
     if ((((uintptr_t)moving | (uintptr_t)fixed) & 15) != 0) return NRT_ERR_UNSUPPORTED;
     InterpBwdArgs ba;
     float dummy;
@@ -1417,6 +1539,26 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
     else                                                                                                         \
         hipLaunchKernelGGL((warp_dice_bwd_rows<GG, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed, sums,  \
                            grad_dice, laplace_smoothing);
+    if (Gr != G) {
+#define NRT_WDB_PAD(GG)                                                                                          \
+    if (loc_mode == NRT_LOC_SHIFT)                                                                               \
+        hipLaunchKernelGGL((warp_dice_bwd_rows_pad<GG, NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, \
+                           grad_dice, laplace_smoothing, Gr);                                                    \
+    else                                                                                                         \
+        hipLaunchKernelGGL((warp_dice_bwd_rows_pad<GG, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed,    \
+                           sums, grad_dice, laplace_smoothing, Gr);
+        switch (G) {
+            case 2: NRT_WDB_PAD(2) break;
+            case 4: NRT_WDB_PAD(4) break;
+            case 8: NRT_WDB_PAD(8) break;
+            case 16: NRT_WDB_PAD(16) break;
+            case 32: NRT_WDB_PAD(32) break;
+            default: NRT_WDB_PAD(64) break;
+        }
+#undef NRT_WDB_PAD
+        NRT_CHECK_LAUNCH();
+        return NRT_OK;
+    }
     if (G == 8 && ba.tg.x_march && nrt_bwd_wc() && nrt_wc_interpn_supported(&ba.f, batch))
         return nrt_wc_bwd_launch(&ba.f, batch, loc_mode, fixed, sums, grad_dice, laplace_smoothing, grad_loc, stream);
     // the pipelined kernel forms 32-bit byte offsets of rows and locations

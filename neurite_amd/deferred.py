@@ -11,7 +11,8 @@ computed on first use by ANY torch operation or by any neurite_amd kernel.  `met
 DeferredWarp as one of its arguments and launches the fused warp + Dice kernel on (moving, trf, other map) instead.  Every other
 consumer simply triggers the stand-alone interpn kernel, exactly as an eager call would have.
 
-Deferral happens only for: linear interpolation, float32 3-D volumes with 4 * 2^k labels, dense displacement fields, no
+Deferral happens only for: linear interpolation, float32 3-D volumes whose label count is a multiple of 4 up to 256 (the counts
+the fused kernel takes), dense displacement fields, no
 gradient being recorded (training graphs stay eager: autograd needs the real tensor), not under `torch.inference_mode()` (inference
 tensors have no version counter, see Immutability), and `deferred.enabled` (env NRT_DEFER_WARP, default on).  The values are bit-identical to the eager path whenever they are materialised.
 

@@ -36,7 +36,8 @@ def warp_dice(moving, trf, fixed, indexing='ij', single_transform=False, fill_va
     """
     moving [B, X, Y, Z, L], trf [B, X', Y', Z', 3] (voxel displacements), fixed [B, X', Y', Z', L]; float32 maps (or both maps
     stored as bfloat16: float32 arithmetic on the widened values, exact for one-hot label maps, half the bytes), 3-D,
-    L in {4, 8, 16, 32, 64, 128, 256}.  Linear interpolation.  Returns dice [B, L] (optionally also the warped
+    L a multiple of 4 in [4, 256] (4 * 2^k labels run on lane groups of L / 4 lanes, any other count on the next power of two,
+    the lanes past L / 4 idle).  Linear interpolation.  Returns dice [B, L] (optionally also the warped
     volume and the partial sums [B, 3, L]).  check_input_limits defaults to False because a tri-linearly
     warped one-hot map exceeds 1.0 by an ulp (see tests); pass True for the reference's asserts (one read-back of the extrema per
     call), or 'deferred' for the same asserts without the host round trip: the values come back as a `checked.CheckedTensor`
@@ -56,8 +57,8 @@ def warp_dice(moving, trf, fixed, indexing='ij', single_transform=False, fill_va
     if bf16 and return_warped:
         raise NotImplementedError('warp_dice on bfloat16 maps does not return the warped volume (use layers.SpatialTransformer)')
     B, L = moving.shape[0], moving.shape[-1]
-    if L % 4 or (L // 4) not in (1, 2, 4, 8, 16, 32, 64):
-        raise NotImplementedError('warp_dice: nb_labels must be 4 * 2^k, got %d (use the unfused layers)' % L)
+    if L % 4 or not 4 <= L <= 256:
+        raise NotImplementedError('warp_dice: nb_labels must be a multiple of 4 in [4, 256], got %d (use the unfused layers)' % L)
     if fixed.shape[0] != B or fixed.shape[-1] != L or tuple(fixed.shape[1:-1]) != tuple(trf.shape[1:-1]):
         raise ValueError('fixed must be [B, *trf_spatial, L]')
     if not single_transform and trf.shape[0] != B:
