@@ -465,6 +465,41 @@ int nrt_channel_axpby_f32(const float *a, const float *b, const float *coef_a, c
                           long long n, int channels, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hyper-convolution: a convolution whose kernel and bias ARRIVE WITH THE BATCH, one set per batch entry
+ * replaces: neurite/tf/layers.py:2515-2665 (HyperConv / HyperConv2D / HyperConv3D: call :2571-2590, the per-entry tf.map_fn of
+ * _convolve_batch :2592-2612), :2668-2822 (the FromDense forms, whose dense maps stay host plumbing) and :2825-3033 (HyperDense /
+ * HyperDenseFromDense: the 1x1x1 case with the rows of x[b] as voxels).  float32, channels-last, stride 1.  One launch serves the whole
+ * batch: the kernels of nrt_conv3d_f32 / nrt_conv3d_wgrad_f32 with the weight and bias base advanced by the batch entry.
+ * ------------------------------------------------------------------------------------------ */
+/* neurite/tf/layers.py:2592-2612 has no packing step (tf.nn.convolution takes the Keras layout); the matrix-core kernels read fragments.
+ * weights [batch, kx,ky,kz, cin, cout] -> packed [batch, nrt_conv3d_packed_weight_floats(ksize, cin, cout)], all entries in ONE launch.
+ * transpose_flip != 0: per entry the kernel flipped in space and transposed in its channel axes is packed instead -- the weights of the
+ * input gradient (what tf.GradientTape derives for :2607-2611), a convolution from cout to cin channels: packed
+ * [batch, nrt_conv3d_packed_weight_floats(ksize, cout, cin)]. */
+int nrt_hyperconv3d_pack_weights_f32(const float *weights, int batch, const int *ksize, int cin, int cout, int transpose_flip,
+                                     float *packed, void *stream);
+/* 1 when nrt_hyperconv3d_f32 (variant 0) runs these arguments on the matrix cores and therefore reads `packed_weights` (then `weights`
+ * may be NULL); 0 when it reads `weights` in the Keras layout.  The rule of nrt_conv3d_f32; no reference counterpart. */
+int nrt_hyperconv3d_uses_packed(const int *shape, const int *ksize, int cin, int cout, int dilation, int padding_same);
+/* out[b] = act(conv3d(src[b], W[b]) + bias[b]), cross-correlation, SAME or VALID: neurite/tf/layers.py:2592-2612 with the bias and
+ * activation of call (:2580-2590).
+ *   src [batch, shape, cin]; weights [batch, kx,ky,kz, cin, cout] or NULL; packed_weights from nrt_hyperconv3d_pack_weights_f32 or NULL
+ *   (at least one of the two; the kernel that is chosen must find its form: NRT_ERR_INVALID_ARG / NRT_ERR_UNSUPPORTED otherwise, as
+ *   nrt_conv3d_f32); bias [batch, cout] or NULL; out [batch, out shape, cout].
+ * Kernel choice, variants (0 auto | 1 direct and single-input-channel kernels | 2 MFMA | 5 persistent MFMA), activation codes (none / ELU /
+ * ReLU, NRT_ERR_INVALID_ARG beyond) and limits are those of nrt_conv3d_f32; there is no second source and no pool / head fold.
+ * No atomics: run-to-run bit-identical, and bit-identical to nrt_conv3d_f32 per entry when every entry carries the same set. */
+int nrt_hyperconv3d_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias, float *out,
+                        int batch, const int *shape, const int *ksize, int cout, int dilation, int padding_same, int activation,
+                        int variant, void *stream);
+/* Per-entry weight and bias gradient (what tf.GradientTape derives for neurite/tf/layers.py:2580-2612 with respect to the kernel and
+ * bias inputs): grad_weights [batch, kx,ky,kz, cin, cout] and grad_bias [batch, cout] (or NULL), NOT summed over the batch.  Contract of
+ * nrt_conv3d_wgrad_f32 otherwise: SAME padding, both outputs ZERO-FILLED by the caller (float atomics, one per weight and block: the sums
+ * are not run-to-run bit-identical), ksize entries 1 or 3, dilation <= 2.  A block only accumulates tiles of one batch entry. */
+int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad_weights, float *grad_bias, int batch,
+                              const int *shape, int cin, int cout, const int *ksize, int dilation, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * LocallyConnected3D, implementation 1 ('valid' padding, channels-last)
  * replaces: neurite/tf/layers.py:1126-1197 (local_conv: O slice ops + concat + K.batch_dot) and the
  * bias / activation of :1098-1101.

@@ -94,6 +94,10 @@ _SIGNATURES = {
     'nrt_conv3d_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _i, _i, _ip, _i, _vp]),
     'nrt_conv3d_wgrad2_f32': (_i, [_vp, _i, _vp, _i, _ip, _vp, _vp, _vp, _i, _ip, _i, _ip, _i, _vp]),
     'nrt_conv3d_wgrad_s2d_f32': (_i, [_vp, _vp, _vp, _i, _ip, _i, _i, _vp]),
+    'nrt_hyperconv3d_pack_weights_f32': (_i, [_vp, _i, _ip, _i, _i, _i, _vp, _vp]),
+    'nrt_hyperconv3d_uses_packed': (_i, [_ip, _ip, _i, _i, _i, _i]),
+    'nrt_hyperconv3d_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _i, _vp]),
+    'nrt_hyperconv3d_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _i, _i, _ip, _i, _vp]),
     'nrt_maxpool3d_bwd_f32': (_i, [_vp, _vp, _vp, _i, _ip, _i, _ip, _i, _vp]),
     'nrt_upsample_sum_f32': (_i, [_vp, _i, _i, _vp, _i, _i, _ip, _ip, _vp]),
     'nrt_softmax_bwd_f32': (_i, [_vp, _vp, _vp, _ll, _i, _vp]),

@@ -55,6 +55,9 @@ struct ConvArgs {
     int act;
     int fold;                // > 0: input channels come in 8 parity groups of `fold` (space-to-depth of a 2x finer tensor) and a group
                              // only has the 2 x 2 x 2 taps (e = (p ? 1 : 2) - t per axis) of the folded decoder backward
+    long long wstride;       // hyper-convolution (nrt_hyperconv3d_f32): floats between the weight sets of two batch entries, in whichever
+                             // form the kernel reads them (packed or Keras layout); 0 = one weight set for the whole batch
+    int bstride;             // likewise for the bias: Cout, or 0
 };
 
 // ============================================================================================
@@ -64,13 +67,15 @@ constexpr int CT_X = 4, CT_Y = 4, CT_Z = 16;   // output tile
 constexpr int LDS_ROW = 20;                     // floats per staged voxel row (16 channels + 4 pad)
 
 // FAST: 3x3x3 kernel, dilation 1 -- the tap loop is fully unrolled, every LDS address is base + immediate
-template <int NT, bool FAST, bool FOLD = false>
-__global__ __launch_bounds__(256) void conv3d_mfma(ConvArgs a, const float *__restrict__ wpacked, unsigned nblk,
+// HYPER: one weight set and bias per batch entry (a.wstride / a.bstride apart); the shared-weight instantiations are compiled without it
+template <int NT, bool FAST, bool FOLD = false, bool HYPER = false>
+__global__ __launch_bounds__(256) void conv3d_mfma(ConvArgs a, const float *__restrict__ wshared, unsigned nblk,
                                                    unsigned nbx, unsigned nby, unsigned nbz) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const unsigned lb = nrt_xcd_block(blockIdx.x, gridDim.x);
     if (lb >= nblk) return;
     const int b = blockIdx.y;
+    const float *__restrict__ wpacked = HYPER ? wshared + (long long)b * a.wstride : wshared;     // the batch entry's weight set
     const int bz = lb % nbz, by = (lb / nbz) % nby, bx = lb / (nbz * nby);
     const int x0 = bx * CT_X, y0 = by * CT_Y, z0 = bz * CT_Z;
     const int hx = FAST ? 1 : (a.kx > 1 ? a.dil : 0), hy = FAST ? 1 : (a.ky > 1 ? a.dil : 0),
@@ -297,7 +302,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma(ConvArgs a, const float *__re
             for (int nt = 0; nt < NT; ++nt) {
                 const int co = (nt0 + nt) * 16 + li;
                 if (co >= a.Cout) continue;
-                const float bv = a.bias ? a.bias[co] : 0.0f;
+                const float bv = a.bias ? a.bias[(HYPER ? b * a.bstride : 0) + co] : 0.0f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int z = z0 + kq * 4 + r;
@@ -324,12 +329,38 @@ __global__ void conv3d_pack_weights(const float *__restrict__ w, int ntap, int C
     }
 }
 
+// the same for `gridDim.y` weight sets in one launch (nrt_hyperconv3d_pack_weights_f32): entry b = blockIdx.y reads w + b * ntap * Cin * Cout
+// and writes packed + b * (floats of one packed set).  FLIP: the set that is packed is the kernel flipped in space and transposed in its
+// channel axes, W'[t][co][ci] = W[ntap - 1 - t][ci][co] -- the weights of the input gradient, a convolution from Cout to Cin channels
+// (chunks over Cout, N-tiles over Cin; NT / nchunk are those of that convolution).
+template <bool FLIP>
+__global__ __launch_bounds__(256) void conv3d_pack_weights_batched(const float *__restrict__ w, int ntap, int Cin, int Cout, int NT, int nchunk,
+                                                                   float *__restrict__ packed) {
+    const long long total = (long long)nchunk * ntap * NT * 64 * 4;
+    const float *wb = w + (long long)blockIdx.y * ntap * Cin * Cout;
+    float *pb = packed + (long long)blockIdx.y * total;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const int m = e & 3, lane = (e >> 2) & 63;
+        long long r = e >> 8;
+        const int nt = r % NT; r /= NT;
+        const int t = r % ntap; const int ch = r / ntap;
+        const int ki = ch * 16 + 4 * (lane >> 4) + m, no = nt * 16 + (lane & 15);      // contraction / output channel of the packed set
+        float v = 0.0f;
+        if (FLIP) { if (ki < Cout && no < Cin) v = wb[((long long)(ntap - 1 - t) * Cin + no) * Cout + ki]; }
+        else if (ki < Cin && no < Cout) v = wb[((long long)t * Cin + ki) * Cout + no];
+        pb[e] = v;
+    }
+}
+
 // ============================================================================================
 // direct convolution: one thread per output voxel, 16 output channels per pass
 // ============================================================================================
-__global__ __launch_bounds__(256) void conv3d_direct(ConvArgs a, const float *__restrict__ w) {
+template <bool HYPER = false>
+__global__ __launch_bounds__(256) void conv3d_direct(ConvArgs a, const float *__restrict__ wshared) {
     const int b = blockIdx.y;
     const int Cin = a.c0 + a.c1;
+    const float *__restrict__ w = HYPER ? wshared + (long long)b * a.wstride : wshared;
+    const float *bias = a.bias ? a.bias + (HYPER ? b * a.bstride : 0) : nullptr;
     const float *s0 = a.src0 + (long long)b * a.X * a.Y * a.Z * a.c0;
     const float *s1 = a.src1 ? a.src1 + (long long)b * a.X1 * a.Y1 * a.Z1 * a.c1 : nullptr;
     float *ob = a.out + (long long)b * a.OX * a.OY * a.OZ * a.Cout;
@@ -371,7 +402,7 @@ __global__ __launch_bounds__(256) void conv3d_direct(ConvArgs a, const float *__
             }
 #pragma unroll
             for (int j = 0; j < 16; ++j)
-                if (cb + j < a.Cout) ob[q * a.Cout + cb + j] = activate(acc[j] + (a.bias ? a.bias[cb + j] : 0.0f), a.act);
+                if (cb + j < a.Cout) ob[q * a.Cout + cb + j] = activate(acc[j] + (bias ? bias[cb + j] : 0.0f), a.act);
         }
     }
 }
@@ -568,16 +599,17 @@ __global__ __launch_bounds__(256) void conv1x1_rows(const float *__restrict__ x,
 }
 
 // conv3d_c1_vec: first encoder layer, Cin == 1 (27 taps of a scalar image -> Cout channels), SAME padding.
-template <int G>
-__global__ __launch_bounds__(256) void conv3d_c1_vec(ConvArgs a, const float *__restrict__ w) {
+template <int G, bool HYPER = false>
+__global__ __launch_bounds__(256) void conv3d_c1_vec(ConvArgs a, const float *__restrict__ wshared) {
     constexpr int Cout = 4 * G;
     constexpr int NG = 256 / G;
     extern __shared__ float wl[];          // [ntap][Cout] + [Cout]
     const int ntap = a.kx * a.ky * a.kz;
-    for (int i = threadIdx.x; i < ntap * Cout; i += blockDim.x) wl[i] = w[i];
-    for (int i = threadIdx.x; i < Cout; i += blockDim.x) wl[ntap * Cout + i] = a.bias ? a.bias[i] : 0.0f;
-    __syncthreads();
     const int b = blockIdx.y;
+    const float *__restrict__ w = HYPER ? wshared + (long long)b * a.wstride : wshared;
+    for (int i = threadIdx.x; i < ntap * Cout; i += blockDim.x) wl[i] = w[i];
+    for (int i = threadIdx.x; i < Cout; i += blockDim.x) wl[ntap * Cout + i] = a.bias ? a.bias[(HYPER ? b * a.bstride : 0) + i] : 0.0f;
+    __syncthreads();
     const float *s0 = a.src0 + (long long)b * a.X * a.Y * a.Z;
     float *ob = a.out + (long long)b * a.OX * a.OY * a.OZ * Cout;
     const long long nvox = (long long)a.OX * a.OY * a.OZ;
@@ -616,8 +648,8 @@ __global__ __launch_bounds__(256) void conv3d_c1_vec(ConvArgs a, const float *__
 // it is still in LDS -- the full-resolution output is written as before (the decoder's skip connection reads it), the pooled tensor
 // in addition: 33 MB more to write at 160^3 x 16 instead of a second kernel that reads 262 MB back.  z pairs and y pairs are a wave's
 // own (rows of its LDS tile, consecutive y iterations), x pairs meet in LDS after one block barrier per tile.
-template <int NT, bool POOL = false>
-__global__ __launch_bounds__(256) void conv3d_c1_mfma(ConvArgs a, const float *__restrict__ w, unsigned nby, unsigned nbz,
+template <int NT, bool POOL = false, bool HYPER = false>
+__global__ __launch_bounds__(256) void conv3d_c1_mfma(ConvArgs a, const float *__restrict__ wshared, unsigned nby, unsigned nbz,
                                                       unsigned nblk, float *__restrict__ pool_out) {
     // persistent blocks (round 3): the weights, bias and tap offsets are loaded once per block instead of once per 4x4x16 tile, and the
     // halo of tile i + 1 is fetched into registers while tile i is on the matrix cores (one tile per block paid ~150 instructions of
@@ -627,6 +659,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_mfma(ConvArgs a, const float *_
     __shared__ __attribute__((aligned(16))) float otile[4][16 * 16 * NT];
     __shared__ __attribute__((aligned(16))) float ptile[POOL ? 4 : 1][2][8 * 16 * NT];     // per wave (x): [y pair][z pair][channel]
     const int b = blockIdx.y;
+    const float *__restrict__ w = HYPER ? wshared + (long long)b * a.wstride : wshared;
     const float *s0 = a.src0 + (long long)b * a.X * a.Y * a.Z;
     float *ob = a.out + (long long)b * a.OX * a.OY * a.OZ * a.Cout;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -644,7 +677,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_mfma(ConvArgs a, const float *_
     }
     float bias[NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bias[nt] = a.bias ? a.bias[nt * 16 + l15] : 0.0f;
+    for (int nt = 0; nt < NT; ++nt) bias[nt] = a.bias ? a.bias[(HYPER ? b * a.bstride : 0) + nt * 16 + l15] : 0.0f;
     // the halo elements this thread stages (fixed positions inside the tile)
     int hrx[PH], hry[PH], hrz[PH];
 #pragma unroll
@@ -906,6 +939,8 @@ int conv_args(ConvArgs &a, const float *src0, int c0, const float *src1, int c1,
     }
     a.act = act;
     a.fold = 0;
+    a.wstride = 0;
+    a.bstride = 0;
     return NRT_OK;
 }
 
@@ -925,7 +960,7 @@ size_t mfma_lds_bytes(const ConvArgs &a) {
     return (size_t)(CT_X + 2 * hx) * (CT_Y + 2 * hy) * (CT_Z + 2 * hz) * LDS_ROW * sizeof(float);
 }
 
-template <int NT>
+template <int NT, bool HYPER = false>
 int launch_mfma(const ConvArgs &a, const float *wpacked, int batch, hipStream_t st, int nsplit = 1) {
     const unsigned nbx = (a.OX + CT_X - 1) / CT_X, nby = (a.OY + CT_Y - 1) / CT_Y, nbz = (a.OZ + CT_Z - 1) / CT_Z;
     const unsigned nblk = nbx * nby * nbz;
@@ -934,21 +969,22 @@ int launch_mfma(const ConvArgs &a, const float *wpacked, int batch, hipStream_t 
     const bool fast = a.kx == 3 && a.ky == 3 && a.kz == 3 && a.dil == 1 && (a.c0 & 3) == 0 && (a.c1 & 3) == 0 && pow2 &&
                       (long long)a.X * a.Y * a.Z * a.c0 < (1ll << 31) && (long long)a.Y * a.Z * (a.c0 > a.c1 ? a.c0 : a.c1) < (1ll << 24);
     if (shm > 64 * 1024) {
-        if (hipFuncSetAttribute((const void *)conv3d_mfma<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)conv3d_mfma<NT, false, false, HYPER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NRT_ERR_LAUNCH;
     }
     dim3 grid(nrt_xcd_grid(nblk), batch, nsplit);
     if (a.fold) {
-        if (!fast || a.c1 || a.fold % 16 || a.c0 != 8 * a.fold) return NRT_ERR_UNSUPPORTED;
+        if (!fast || a.c1 || a.fold % 16 || a.c0 != 8 * a.fold || HYPER) return NRT_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((conv3d_mfma<NT, true, true>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz);
-    } else if (fast) hipLaunchKernelGGL((conv3d_mfma<NT, true>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz);
-    else hipLaunchKernelGGL((conv3d_mfma<NT, false>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz);
+    } else if (fast) hipLaunchKernelGGL((conv3d_mfma<NT, true, false, HYPER>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz);
+    else hipLaunchKernelGGL((conv3d_mfma<NT, false, false, HYPER>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz);
     NRT_CHECK_LAUNCH();
     return NRT_OK;
 }
 
 // all N-tiles in one block, or -- when the grid has fewer than two tiles per CU (40^3 layers: 300 tiles on 256 CUs) -- the 16-channel
 // output blocks split over blockIdx.z so that every CU gets several smaller blocks
+template <bool HYPER = false>
 int dispatch_mfma(const ConvArgs &a, const float *wpacked, int batch, hipStream_t st) {
     const int ntt = (a.Cout + 15) / 16;
     const long long tiles = (long long)batch * ((a.OX + CT_X - 1) / CT_X) * ((a.OY + CT_Y - 1) / CT_Y) * ((a.OZ + CT_Z - 1) / CT_Z);
@@ -959,10 +995,10 @@ int dispatch_mfma(const ConvArgs &a, const float *wpacked, int batch, hipStream_
         else split = ntt;                                        // 2 or 3 output blocks: one per block
     }
     switch (ntt / split) {
-        case 1: return launch_mfma<1>(a, wpacked, batch, st, split);
-        case 2: return launch_mfma<2>(a, wpacked, batch, st, split);
-        case 3: return launch_mfma<3>(a, wpacked, batch, st, split);
-        default: return launch_mfma<4>(a, wpacked, batch, st, split);
+        case 1: return launch_mfma<1, HYPER>(a, wpacked, batch, st, split);
+        case 2: return launch_mfma<2, HYPER>(a, wpacked, batch, st, split);
+        case 3: return launch_mfma<3, HYPER>(a, wpacked, batch, st, split);
+        default: return launch_mfma<4, HYPER>(a, wpacked, batch, st, split);
     }
 }
 
@@ -1102,35 +1138,39 @@ extern "C" int nrt_conv3d_s2d_taps_f32(const float *x, int group, const float *p
     return dispatch_mfma(a, packed_weights, batch, st);
 }
 
-extern "C" int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const int *up, const float *weights,
-                              const float *packed_weights, const float *bias, float *out, int batch, const int *shape,
-                              const int *ksize, int cout, int dilation, int padding_same, int activation, int variant,
-                              void *stream) {
-    ConvArgs a;
-    int rc = conv_args(a, src0, c0, src1, c1, up, bias, out, shape, ksize, cout, dilation, padding_same, activation);
-    if (rc != NRT_OK) return rc;
-    if (batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
-    if (activation < ACT_NONE || activation > ACT_LAST_FUSED) return NRT_ERR_INVALID_ARG;
-    hipStream_t st = nrt_stream(stream);
+namespace {
+
+// the kernel choice of nrt_conv3d_f32 / nrt_hyperconv3d_f32.  HYPER: a.wstride / a.bstride are set, `weights` and `packed_weights` hold one
+// set per batch entry; the choices are the same, the persistent schedule runs its per-entry instantiation
+template <bool HYPER>
+int conv3d_dispatch(ConvArgs &a, const float *weights, const float *packed_weights, float *out, int batch, int padding_same,
+                    int variant, hipStream_t st) {
+    const int c0 = a.c0, c1 = a.c1, cout = a.Cout;
     const bool can_mfma = mfma_ok(a, padding_same) && packed_weights != nullptr;
+    if (HYPER) {                                                 // floats per entry of the array the chosen kernel reads
+        const int k3[3] = {a.kx, a.ky, a.kz};
+        const bool packed = variant == 0 ? can_mfma : (variant == 2 || variant == 5);
+        a.wstride = packed ? (long long)nrt_conv3d_packed_weight_floats(k3, c0, cout) : (long long)a.kx * a.ky * a.kz * c0 * cout;
+    }
     // variant 5: the persistent LDS-DMA schedule (conv_p27.h); auto takes it when there is more than one tile per CU
-    const bool can_p27 = can_mfma && p27_ok(a, padding_same, batch);
+    // (per-entry weights: the entry's offset is a 32-bit lane offset there)
+    const bool can_p27 = can_mfma && p27_ok(a, padding_same, batch) && (!HYPER || (long long)batch * a.wstride * 4 < (1ll << 31));
     if (variant == 0 && can_p27 &&
         (long long)batch * ((a.OX + CT_X - 1) / CT_X) * ((a.OY + CT_Y - 1) / CT_Y) * ((a.OZ + CT_Z - 1) / CT_Z) >= 2ll * nrt_num_cus())
         variant = 5;
     if (variant == 5) {
         if (!can_p27) return NRT_ERR_UNSUPPORTED;
         switch ((cout + 15) / 16) {
-            case 1: return launch_p27<1>(a, packed_weights, batch, st);
-            case 2: return launch_p27<2>(a, packed_weights, batch, st);
-            case 3: return launch_p27<3>(a, packed_weights, batch, st);
-            default: return launch_p27<4>(a, packed_weights, batch, st);
+            case 1: return launch_p27<1, false, HYPER>(a, packed_weights, batch, st);
+            case 2: return launch_p27<2, false, HYPER>(a, packed_weights, batch, st);
+            case 3: return launch_p27<3, false, HYPER>(a, packed_weights, batch, st);
+            default: return launch_p27<4, false, HYPER>(a, packed_weights, batch, st);
         }
     }
     if (variant == 0) variant = can_mfma ? 2 : 1;
     if (variant == 2) {
         if (!can_mfma) return NRT_ERR_UNSUPPORTED;
-        return dispatch_mfma(a, packed_weights, batch, st);
+        return dispatch_mfma<HYPER>(a, packed_weights, batch, st);
     }
     if ((variant != 1 && variant != 3) || !weights) return NRT_ERR_INVALID_ARG;
     const long long nvox = (long long)a.OX * a.OY * a.OZ;
@@ -1146,10 +1186,10 @@ extern "C" int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int 
         const unsigned T8c = (nblk + NRT_NXCD - 1) / NRT_NXCD, perx = 8u * (unsigned)nrt_num_cus() / NRT_NXCD;     // 8 persistent blocks per CU
         dim3 grid(NRT_NXCD * (T8c < perx ? T8c : perx), batch);
         switch (cout / 16) {
-            case 1: hipLaunchKernelGGL((conv3d_c1_mfma<1>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
-            case 2: hipLaunchKernelGGL((conv3d_c1_mfma<2>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
-            case 3: hipLaunchKernelGGL((conv3d_c1_mfma<3>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
-            default: hipLaunchKernelGGL((conv3d_c1_mfma<4>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
+            case 1: hipLaunchKernelGGL((conv3d_c1_mfma<1, false, HYPER>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
+            case 2: hipLaunchKernelGGL((conv3d_c1_mfma<2, false, HYPER>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
+            case 3: hipLaunchKernelGGL((conv3d_c1_mfma<3, false, HYPER>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
+            default: hipLaunchKernelGGL((conv3d_c1_mfma<4, false, HYPER>), grid, dim3(256), 0, st, a, weights, nby, nbz, nblk, (float *)nullptr); break;
         }
         NRT_CHECK_LAUNCH();
         return NRT_OK;
@@ -1161,20 +1201,74 @@ extern "C" int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int 
         if (blocks > 256u * 32u) blocks = 256u * 32u;
         dim3 grid(blocks, batch);
         switch (Gc) {
-            case 1: hipLaunchKernelGGL((conv3d_c1_vec<1>), grid, dim3(256), shm, st, a, weights); break;
-            case 2: hipLaunchKernelGGL((conv3d_c1_vec<2>), grid, dim3(256), shm, st, a, weights); break;
-            case 4: hipLaunchKernelGGL((conv3d_c1_vec<4>), grid, dim3(256), shm, st, a, weights); break;
-            case 8: hipLaunchKernelGGL((conv3d_c1_vec<8>), grid, dim3(256), shm, st, a, weights); break;
-            default: hipLaunchKernelGGL((conv3d_c1_vec<16>), grid, dim3(256), shm, st, a, weights); break;
+            case 1: hipLaunchKernelGGL((conv3d_c1_vec<1, HYPER>), grid, dim3(256), shm, st, a, weights); break;
+            case 2: hipLaunchKernelGGL((conv3d_c1_vec<2, HYPER>), grid, dim3(256), shm, st, a, weights); break;
+            case 4: hipLaunchKernelGGL((conv3d_c1_vec<4, HYPER>), grid, dim3(256), shm, st, a, weights); break;
+            case 8: hipLaunchKernelGGL((conv3d_c1_vec<8, HYPER>), grid, dim3(256), shm, st, a, weights); break;
+            default: hipLaunchKernelGGL((conv3d_c1_vec<16, HYPER>), grid, dim3(256), shm, st, a, weights); break;
         }
         NRT_CHECK_LAUNCH();
         return NRT_OK;
     }
     unsigned blocks = (unsigned)((nvox + 255) / 256);
     if (blocks > 256u * 32u) blocks = 256u * 32u;
-    hipLaunchKernelGGL(conv3d_direct, dim3(blocks, batch), dim3(256), 0, st, a, weights);
+    hipLaunchKernelGGL((conv3d_direct<HYPER>), dim3(blocks, batch), dim3(256), 0, st, a, weights);
     NRT_CHECK_LAUNCH();
     return NRT_OK;
+}
+
+}  // namespace
+
+extern "C" int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const int *up, const float *weights,
+                              const float *packed_weights, const float *bias, float *out, int batch, const int *shape,
+                              const int *ksize, int cout, int dilation, int padding_same, int activation, int variant,
+                              void *stream) {
+    ConvArgs a;
+    int rc = conv_args(a, src0, c0, src1, c1, up, bias, out, shape, ksize, cout, dilation, padding_same, activation);
+    if (rc != NRT_OK) return rc;
+    if (batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
+    if (activation < ACT_NONE || activation > ACT_LAST_FUSED) return NRT_ERR_INVALID_ARG;
+    return conv3d_dispatch<false>(a, weights, packed_weights, out, batch, padding_same, variant, nrt_stream(stream));
+}
+
+// ---- hyper-convolution: one weight set and one bias per batch entry (neurite/tf/layers.py:2515-2612) -----------------------------------
+extern "C" int nrt_hyperconv3d_pack_weights_f32(const float *weights, int batch, const int *ksize, int cin, int cout, int transpose_flip,
+                                                float *packed, void *stream) {
+    if (!weights || !packed || !ksize || cin < 1 || cout < 1 || batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
+    if (ksize[0] < 1 || ksize[1] < 1 || ksize[2] < 1) return NRT_ERR_INVALID_ARG;
+    const int ntap = ksize[0] * ksize[1] * ksize[2];
+    const int kin = transpose_flip ? cout : cin, nout = transpose_flip ? cin : cout;      // the packed set's contraction / output channels
+    const int NT = (nout + 15) / 16, nchunk = (kin + 15) / 16;
+    const long long total = (long long)nchunk * ntap * NT * 256;
+    const unsigned bx = (unsigned)((total + 255) / 256 < 64 ? (total + 255) / 256 : 64);
+    hipStream_t st = nrt_stream(stream);
+    if (transpose_flip) hipLaunchKernelGGL((conv3d_pack_weights_batched<true>), dim3(bx, batch), dim3(256), 0, st, weights, ntap, cin, cout, NT, nchunk, packed);
+    else hipLaunchKernelGGL((conv3d_pack_weights_batched<false>), dim3(bx, batch), dim3(256), 0, st, weights, ntap, cin, cout, NT, nchunk, packed);
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+extern "C" int nrt_hyperconv3d_uses_packed(const int *shape, const int *ksize, int cin, int cout, int dilation, int padding_same) {
+    if (!shape || !ksize) return 0;
+    ConvArgs a;
+    float dummy;
+    if (cin < 1 || conv_args(a, &dummy, cin, nullptr, 0, nullptr, nullptr, &dummy, shape, ksize, cout, dilation, padding_same, ACT_NONE) != NRT_OK)
+        return 0;
+    return mfma_ok(a, padding_same) ? 1 : 0;
+}
+
+extern "C" int nrt_hyperconv3d_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias,
+                                   float *out, int batch, const int *shape, const int *ksize, int cout, int dilation, int padding_same,
+                                   int activation, int variant, void *stream) {
+    ConvArgs a;
+    int rc = conv_args(a, src, cin, nullptr, 0, nullptr, bias, out, shape, ksize, cout, dilation, padding_same, activation);
+    if (rc != NRT_OK) return rc;
+    if (batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
+    if (!weights && !packed_weights) return NRT_ERR_INVALID_ARG;
+    if (activation < ACT_NONE || activation > ACT_LAST_FUSED) return NRT_ERR_INVALID_ARG;
+    if (variant != 0 && variant != 1 && variant != 2 && variant != 5) return NRT_ERR_INVALID_ARG;
+    a.bstride = bias ? cout : 0;
+    return conv3d_dispatch<true>(a, weights, packed_weights, out, batch, padding_same, variant, nrt_stream(stream));
 }
 
 // the single-channel first layer + the 2x2x2 max-pooling behind it (models.py:1378-1388, 1436-1438) in one kernel: `out` as nrt_conv3d_f32

@@ -155,6 +155,7 @@ struct WgArgs {
     int fold;                // folded decoder backward: dp is the space-to-depth tensor of the fine gradient (8 parity groups of Cout
                              // channels), blockIdx.z = parity group P, its 8 taps are e = p + t per axis (t in {0,1}), and
                              // dw is [8 groups][8 taps][Cin][Cout]
+    int pe;                  // host side: launch the per-entry instantiation (PE below)
 };
 
 constexpr int WT_X = 4, WT_Y = 4, WT_Z = 8;     // voxel tile: 128 voxels = 32 k-steps of 4
@@ -165,7 +166,9 @@ constexpr int WT_X = 4, WT_Y = 4, WT_Z = 8;     // voxel tile: 128 voxels = 32 k
 // decode (two runtime divisions per 16-byte load) into multiply-shifts
 // KM = 1: 1x1x1 kernel (also the im2col form of the first layer) -- same staging; the four waves split the 32 k-steps
 // instead of the taps and each adds its partial sums at the end
-template <int NA, int NB, int KM, int WG_MAXT = 7>
+// PE: per-entry weight gradient (nrt_hyperconv3d_wgrad_f32) -- blockIdx.z = batch entry; the block walks tiles of that entry only and
+// adds into the entry's slice dw + b * taps * Cin * Cout, db + b * Cout (not with the folded form, whose blockIdx.z is the parity group)
+template <int NA, int NB, int KM, int WG_MAXT = 7, bool PE = false>
 __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
     constexpr bool K3 = KM == 3, K1 = KM == 1, KF = K3 || K1;
     constexpr int HALO = K3 ? 1 : 0;
@@ -207,9 +210,10 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
     }
 
     const long long tiles_per_vol = (long long)a.ntx * a.nty * a.ntz;
-    const long long ntiles = tiles_per_vol * a.B;
+    const int bpe = PE ? (int)blockIdx.z : 0;                   // per-entry form: this block's batch entry
+    const long long ntiles = PE ? tiles_per_vol : tiles_per_vol * a.B;
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int b = (int)(tile / tiles_per_vol);
+        const int b = PE ? bpe : (int)(tile / tiles_per_vol);
         const long long tv = tile % tiles_per_vol;
         const int x0 = (int)(tv / ((long long)a.nty * a.ntz)) * WT_X, y0 = (int)((tv / a.ntz) % a.nty) * WT_Y,
                   z0 = (int)(tv % a.ntz) * WT_Z;
@@ -455,6 +459,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
         }
     }
     // ---- accumulate into global memory: D row = 4 (lane >> 4) + r (ci), col = lane & 15 (co) -----------------------
+    float *dwb = PE ? a.dw + (long long)bpe * ntap * a.Cin * a.Cout : a.dw;      // (the im2col form: ntap = 1, Cin = 27)
 #pragma unroll
     for (int i = 0; i < WG_MAXT; ++i) {
         const int t = K1 ? 0 : wv + 4 * i;
@@ -468,12 +473,13 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
                     for (int r = 0; r < 4; ++r) {
                         const int ci = ci0 + na * 16 + l4 * 4 + r;
                         if (ci < a.Cin && co < a.Cout)
-                            unsafeAtomicAdd(&a.dw[((long long)(P * 8 + t) * a.Cin + ci) * a.Cout + co], acc[i][na][nb][r]);
+                            unsafeAtomicAdd(&dwb[((long long)(P * 8 + t) * a.Cin + ci) * a.Cout + co], acc[i][na][nb][r]);
                     }
                 }
         }
     }
-    if (a.db && cic == 0 && threadIdx.x < CO && co0 + (int)threadIdx.x < a.Cout) unsafeAtomicAdd(&a.db[co0 + threadIdx.x], bsum);
+    if (a.db && cic == 0 && threadIdx.x < CO && co0 + (int)threadIdx.x < a.Cout)
+        unsafeAtomicAdd(&a.db[bpe * a.Cout + co0 + threadIdx.x], bsum);
 }
 
 // Folded weight gradient of a decoder convolution, all 8 parity groups per block (see nrt_conv3d_wgrad_s2d_f32):
@@ -803,6 +809,15 @@ int launch_wgrad(WgArgs &a, hipStream_t st) {
     long long bx = 256ll * per_cu / (a.ncic * a.ncoc);           // about one resident wave of blocks
     if (bx < 64) bx = 64;
     if (bx > ntiles) bx = ntiles;
+    unsigned gz = 1;
+    if (a.pe) {
+        // per-entry form: the same resident wave of blocks, split over the entries (grid.z); a block only sees tiles of its entry
+        const long long tpv = (long long)a.ntx * a.nty * a.ntz;
+        bx = (256ll * per_cu / (a.ncic * a.ncoc) + a.B - 1) / a.B;
+        if (bx < (64 + a.B - 1) / a.B) bx = (64 + a.B - 1) / a.B;
+        if (bx > tpv) bx = tpv;
+        gz = (unsigned)a.B;
+    }
     const bool quads = (a.Cout & 3) == 0 && (a.im2col || ((a.Cin & 3) == 0 &&
                        (!a.x1 || ((a.c0 & 3) == 0 && (a.c1 & 3) == 0 && (a.ux & (a.ux - 1)) == 0 && (a.uy & (a.uy - 1)) == 0 &&
                                   (a.uz & (a.uz - 1)) == 0))));
@@ -812,13 +827,20 @@ int launch_wgrad(WgArgs &a, hipStream_t st) {
                    : (a.kx == 1 && a.ky == 1 && a.kz == 1) ? 1 : 0;
 #define NRT_WG_LAUNCH(KM)                                                                                                   \
     do {                                                                                                                    \
-        if (lds > 48 * 1024)                                                                                                \
-            (void)hipFuncSetAttribute((const void *)conv3d_wgrad<NA, NB, KM>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                      (int)lds);                                                                            \
-        hipLaunchKernelGGL((conv3d_wgrad<NA, NB, KM>), dim3((unsigned)bx, a.ncic * a.ncoc), dim3(256), lds, st, a);         \
+        if (a.pe) {                                                                                                         \
+            if (lds > 48 * 1024)                                                                                            \
+                (void)hipFuncSetAttribute((const void *)conv3d_wgrad<NA, NB, KM, 7, true>,                                  \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
+            hipLaunchKernelGGL((conv3d_wgrad<NA, NB, KM, 7, true>), dim3((unsigned)bx, a.ncic * a.ncoc, gz), dim3(256), lds, st, a); \
+        } else {                                                                                                            \
+            if (lds > 48 * 1024)                                                                                            \
+                (void)hipFuncSetAttribute((const void *)conv3d_wgrad<NA, NB, KM>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                          (int)lds);                                                                        \
+            hipLaunchKernelGGL((conv3d_wgrad<NA, NB, KM>), dim3((unsigned)bx, a.ncic * a.ncoc), dim3(256), lds, st, a);     \
+        }                                                                                                                   \
     } while (0)
     if (a.fold) {
-        if (km != 3) return NRT_ERR_UNSUPPORTED;
+        if (km != 3 || a.pe) return NRT_ERR_UNSUPPORTED;
         bx = 256ll * per_cu / (a.ncic * a.ncoc * 8);
         if (bx < 16) bx = 16;
         if (bx > ntiles) bx = ntiles;
@@ -971,7 +993,7 @@ extern "C" int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, 
     a.kx = ksize[0]; a.ky = ksize[1]; a.kz = ksize[2]; a.dil = dilation;
     a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
     a.im2col = 0;
-    a.dps = cout; a.fold = 0;
+    a.dps = cout; a.fold = 0; a.pe = 0;
     if (cin == 1 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3 && dilation == 1 && cout % 16 == 0 && cout <= 64 &&
         (long long)shape[0] * shape[1] * shape[2] < (1ll << 31)) {
         // the single-channel first layer: gathered straight from the volume (conv3d_c1_wgrad)
@@ -1024,6 +1046,41 @@ extern "C" int nrt_conv3d_wgrad_f32(const float *x, const float *grad_pre, float
                                  stream);
 }
 
+// per-entry weight and bias gradient of the hyper-convolution: the tile kernel with one grid.z slice per batch entry (its im2col form
+// for a single input channel, its streaming 1x1x1 form for a 1x1x1 kernel)
+extern "C" int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad_weights, float *grad_bias, int batch,
+                                         const int *shape, int cin, int cout, const int *ksize, int dilation, void *stream) {
+    if (!x || !grad_pre || !grad_weights || !shape || !ksize) return NRT_ERR_INVALID_ARG;
+    if (batch < 1 || batch > 65535 || cin < 1 || cout < 1 || dilation < 1) return NRT_ERR_INVALID_ARG;
+    for (int d = 0; d < 3; ++d) {
+        if (shape[d] < 1 || ksize[d] < 1) return NRT_ERR_INVALID_ARG;
+        if (ksize[d] != 1 && ksize[d] != 3) return NRT_ERR_UNSUPPORTED;
+    }
+    if (dilation > 2) return NRT_ERR_UNSUPPORTED;
+    WgArgs a;
+    a.x = x; a.dp = grad_pre; a.dw = grad_weights; a.db = grad_bias;
+    a.x1 = nullptr; a.c0 = cin; a.c1 = 0; a.ux = a.uy = a.uz = 1;
+    a.B = batch; a.X = shape[0]; a.Y = shape[1]; a.Z = shape[2]; a.Cin = cin; a.Cout = cout;
+    a.kx = ksize[0]; a.ky = ksize[1]; a.kz = ksize[2]; a.dil = dilation;
+    a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
+    a.im2col = 0; a.dps = cout; a.fold = 0; a.pe = 1;
+    if (cin == 1 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3) {
+        a.im2col = 1; a.Cin = 27; a.kx = a.ky = a.kz = 1;        // [27 taps][1][cout] and [1 tap][27][cout] are the same memory
+        cin = 27;
+    }
+    hipStream_t st = nrt_stream(stream);
+    int na = cin <= 16 ? 1 : (cin <= 32 ? 2 : 3);
+    const int nb = cout <= 16 ? 1 : 2;
+    for (; na >= 1; --na) {                                      // dilated kernels: shrink the cin chunk until the tiles fit the LDS
+        int rc;
+        if (na == 1) rc = nb == 1 ? launch_wgrad<1, 1>(a, st) : launch_wgrad<1, 2>(a, st);
+        else if (na == 2) rc = nb == 1 ? launch_wgrad<2, 1>(a, st) : launch_wgrad<2, 2>(a, st);
+        else rc = nb == 1 ? launch_wgrad<3, 1>(a, st) : launch_wgrad<3, 2>(a, st);
+        if (rc != NRT_ERR_UNSUPPORTED) return rc;
+    }
+    return NRT_ERR_UNSUPPORTED;
+}
+
 extern "C" int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre_s2d, float *grad_folded, int batch, const int *shape,
                                         int cin, int group, void *stream) {
     if (!x_lo || !grad_pre_s2d || !grad_folded || !shape || batch < 1 || cin < 4 || cin % 4 || group < 4 || group % 4)
@@ -1038,7 +1095,7 @@ extern "C" int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre
     a.kx = a.ky = a.kz = 3; a.dil = 1;
     a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
     a.im2col = 0;
-    a.dps = 8 * group; a.fold = 1;
+    a.dps = 8 * group; a.fold = 1; a.pe = 0;
     hipStream_t st = nrt_stream(stream);
     // all 8 parity groups per block when the staging's assumptions hold (quad-aligned channels, 32-bit offsets, 24-bit strides)
     const bool foldall = cin % 4 == 0 && group % 4 == 0 && (long long)a.X * a.Y * a.Z * cin < (1ll << 31) &&

@@ -19,7 +19,21 @@ constexpr int P27_LDS_FLOATS = 2 * P27_BUF_FLOATS;
 // halo buffers, one block barrier per tile, and every wave stores a quarter of the tile's 2 x 2 x 8 pooled voxels.  Whole tiles only.
 constexpr int p27_pool_floats(int NT) { return 4 * 8 * NT * 64; }
 
-template <int NT, bool POOL = false>
+// HYPER (nrt_hyperconv3d_f32): every batch entry has its own weight set and bias (a.wstride / a.bstride floats apart).  A block's tiles
+// cross batch entries, so both are chosen per tile -- the entry's weight offset rides in the lanes' 32-bit VECTOR offset of the fragment
+// loads (the scalar base stays the kernel argument: nothing a VALU instruction wrote becomes an address register of an asm load), and the
+// entry's bias is requested by one more asm load at the top of the tile, in front of all of the tile's fragment loads: vmcnt retires in
+// order, so it has landed when the first fragment wait returns, and an OLDER load in flight only makes the hand-counted waits wait for
+// more than they name.  The shared-weight instantiations are compiled without any of it.
+__device__ __forceinline__ void u2_tie1(float &r) { asm volatile("" : "+v"(r)); }
+__device__ __forceinline__ float p27_ld1(const void *sbase, unsigned voff) {
+    float r;
+    // five wait states in front, as u2_ldw_s: the bias pointer is used once per tile and may come back from a spill lane right here
+    asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase));
+    return r;
+}
+
+template <int NT, bool POOL = false, bool HYPER = false>
 __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const float *__restrict__ wpacked, const float *__restrict__ zeros,
                                                           unsigned ntiles, unsigned nbx, unsigned nby, unsigned nbz, float *__restrict__ pool_out) {
     static_assert(!POOL || NT >= 2, "the pooled form rides the immediate stores of the NT >= 2 instantiations");
@@ -60,11 +74,13 @@ __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const floa
         unsigned pool;               // POOL: float offset of pooled voxel (x0 / 2, y0 / 2, z0 / 2), channel 0
         int x0, y0, z0;
         unsigned full;
+        unsigned b;                  // HYPER: the batch entry
     };
     auto decode = [&](unsigned t) __attribute__((always_inline)) {
         Tile T;
         const int bz = t % nbz, by = (t / nbz) % nby, bx = (t / (nbz * nby)) % nbx, b = t / (nbz * nby * nbx);
         T.x0 = bx * CT_X; T.y0 = by * CT_Y; T.z0 = bz * CT_Z;
+        T.b = HYPER ? (unsigned)b : 0u;
         T.pB = a.src0 + ((long long)b * a.X * a.Y * a.Z + ((long long)T.x0 * a.Y + T.y0) * a.Z + T.z0) * a.c0;
         T.out = (unsigned)((((long long)b * a.OX + T.x0) * a.OY + T.y0) * a.OZ + T.z0) * (unsigned)a.Cout * 4u;
         T.pool = POOL ? (unsigned)((((long long)b * (a.OX / 2) + T.x0 / 2) * (a.OY / 2) + T.y0 / 2) * (a.OZ / 2) + T.z0 / 2) * (unsigned)a.Cout : 0u;
@@ -91,10 +107,15 @@ __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const floa
     };
 
     float bv[NT];
+    if constexpr (HYPER) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bv[nt] = (a.bias && nt * 16 + li < a.Cout) ? a.bias[nt * 16 + li] : 0.0f;
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = 0.0f;                  // per tile: tile_bias()
+    } else {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bv[nt]));      // the only compiler-visible load: settled here
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = (a.bias && nt * 16 + li < a.Cout) ? a.bias[nt * 16 + li] : 0.0f;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bv[nt]));  // the only compiler-visible load: settled here
+    }
 
     f32x4 acc[4][NT];
     float outv[4][NT][4];
@@ -112,7 +133,15 @@ __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const floa
                     u2_store(a.out, outBase + outLane + 2 * (mt & 1) * oX + (2 * r + (mt >> 1)) * (unsigned)a.Cout * 4u + nt * 64u,
                              outv[mt][nt][r]);
     };
-    const unsigned wlane = lane * 16u;
+    unsigned wlane = lane * 16u;                                        // HYPER: + the byte offset of the tile's weight set
+    // HYPER: request the bias of batch entry b (channels past Cout read channel 0 and are never stored)
+    auto tile_bias = [&](unsigned b) __attribute__((always_inline)) {
+        if (a.bias) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                bv[nt] = p27_ld1(a.bias, (b * (unsigned)a.bstride + (nt * 16 + li < a.Cout ? nt * 16 + li : 0)) * 4u);
+        }
+    };
 
     // ---- one chunk of 16 input channels: the 27 taps on the halo in buffer `buf` -----------------------------------------------------
     auto body = [&](int ch, unsigned buf, auto Dc, auto Sc, auto &&issue_next) __attribute__((always_inline)) {
@@ -176,6 +205,10 @@ __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const floa
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (HYPER) {
+            wlane = lane * 16u + cur.b * (unsigned)a.wstride * 4u;       // launch_p27: batch * wstride * 4 fits 31 bits
+            tile_bias(cur.b);
+        }
         for (int ch = 0; ch < nB; ++ch) {
             const bool last = ch + 1 == nB;
             u2_chunk_barrier();                                         // chunk ch has landed; chunk ch - 1 has been read by all waves
@@ -190,6 +223,11 @@ __global__ __launch_bounds__(256, 1) void conv3d_p27_mfma(ConvArgs a, const floa
                 if (ch == 0 && pending) { body(ch, buf, I0{}, IS{}, [&]() {}); pending = false; }
                 else body(ch, buf, I0{}, I0{}, [&]() {});
             }
+        }
+        if constexpr (HYPER) {
+            // behind the tile's last fragment wait (volatile asm statements keep their order): the bias has landed
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) u2_tie1(bv[nt]);
         }
         if (cur.full) {
 #pragma unroll
@@ -270,18 +308,18 @@ bool p27_ok(const ConvArgs &a, int padding_same, int batch) {
            a.fold == 0 && (long long)a.X * a.Y * a.Z * a.c0 < (1ll << 30) && (long long)batch * a.X * a.Y * a.Z * a.Cout < (1ll << 30);
 }
 
-template <int NT, bool POOL = false>
+template <int NT, bool POOL = false, bool HYPER = false>
 int launch_p27(const ConvArgs &a, const float *wpacked, int batch, hipStream_t st, float *pool_out = nullptr) {
     const unsigned nbx = (a.OX + CT_X - 1) / CT_X, nby = (a.OY + CT_Y - 1) / CT_Y, nbz = (a.OZ + CT_Z - 1) / CT_Z;
     const unsigned ntiles = nbx * nby * nbz * (unsigned)batch;
     const int shm = (P27_LDS_FLOATS + (POOL ? p27_pool_floats(NT) : 0)) * 4;
-    if (hipFuncSetAttribute((const void *)conv3d_p27_mfma<NT, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, shm) != hipSuccess)
+    if (hipFuncSetAttribute((const void *)conv3d_p27_mfma<NT, POOL, HYPER>, hipFuncAttributeMaxDynamicSharedMemorySize, shm) != hipSuccess)
         return NRT_ERR_LAUNCH;
     const unsigned T8 = (ntiles + NRT_NXCD - 1) / NRT_NXCD, per_xcd = (unsigned)nrt_num_cus() / NRT_NXCD;
     const unsigned J = T8 < per_xcd ? T8 : per_xcd;
     const float *zeros = p27_zero_block(st);
     if (!zeros) return NRT_ERR_LAUNCH;
-    hipLaunchKernelGGL((conv3d_p27_mfma<NT, POOL>), dim3(NRT_NXCD * J), dim3(256), shm, st, a, wpacked, zeros, ntiles, nbx, nby, nbz, pool_out);
+    hipLaunchKernelGGL((conv3d_p27_mfma<NT, POOL, HYPER>), dim3(NRT_NXCD * J), dim3(256), shm, st, a, wpacked, zeros, ntiles, nbx, nby, nbz, pool_out);
     NRT_CHECK_LAUNCH();
     return NRT_OK;
 }

@@ -4,6 +4,7 @@ neurite_amd.layers -- the layers of neurite's hot path as torch.nn.Modules over 
 Resize / Zoom           neurite/tf/layers.py:91-185
 SpatialTransformer      voxelmorph.layers.SpatialTransformer as the reference calls it
                         (neurite/tf/models.py:806-807 and 1157-1159; not vendored in the reference)
+HyperConv* / HyperDense* neurite/tf/layers.py:2515-3033 (kernel and bias are inputs, one set per batch entry)
 
 Same constructor arguments, defaults, lazy build on first call, get_config() keys and error
 behaviour as the Keras layers.  Tensors are channels-last [B, *spatial, C] on a ROCm device.
@@ -21,7 +22,9 @@ from . import deferred
 from . import utils
 
 __all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LocallyConnected3D', 'VecInt', 'RescaleTransform',
-           'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise']
+           'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise',
+           'HyperConv', 'HyperConv2D', 'HyperConv3D', 'HyperConvFromDense', 'HyperConv2DFromDense', 'HyperConv3DFromDense',
+           'HyperDense', 'HyperDenseFromDense']
 
 
 class _Layer(nn.Module):
@@ -1010,3 +1013,447 @@ class LocallyConnected3D(_Layer):
                 return sm(out.float()).to(out.dtype) if out.dtype != torch.float32 else sm(out)
             out = sm(out.float()).to(out.dtype) if out.dtype != torch.float32 else sm(out)
         return out.permute(0, 4, 1, 2, 3) if self.data_format == 'channels_first' else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Hyper-convolution / hyper-dense layers (neurite/tf/layers.py:2515-3033): the kernel and the bias are INPUTS, one set per batch
+# entry.  The reference maps a single-entry convolution over the batch with tf.map_fn (:2587, :2860); here the whole batch is one
+# launch of the conv kernels with the weight and bias base advanced by the batch entry (csrc/conv.hip: ConvArgs.wstride / bstride,
+# nrt_hyperconv3d_f32), and the per-entry weight gradient one launch of the weight-gradient kernel with a grid slice per entry
+# (nrt_hyperconv3d_wgrad_f32).  No packed-weight cache: the kernels change with every call.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _hyperconv_run(x, kernel, bias, ksize3, dilation, same, kact, flipped=False):
+    """act(conv3d(x[b], W[b]) + bias[b]) for every b in one launch.  x [B, X, Y, Z, cin], kernel [B, kx, ky, kz, cin, cout], bias
+    [B, cout] or None, all float32 and contiguous.  flipped: convolve with the kernels flipped in space and transposed in their
+    channel axes instead (the input gradient: cout -> cin channels)."""
+    lib = _lib.lib()
+    dev = x.device
+    B, S = x.shape[0], list(x.shape[1:4])
+    cin, cout = kernel.shape[-2], kernel.shape[-1]
+    ci, co = (cout, cin) if flipped else (cin, cout)
+    O = S if same else [S[d] - (ksize3[d] - 1) * dilation for d in range(3)]
+    out = torch.empty([B] + O + [co], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        weights = packed = None
+        if lib.nrt_hyperconv3d_uses_packed(_lib.ints(S), _lib.ints(ksize3), ci, co, int(dilation), int(same)) == 1:
+            n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(ksize3), ci, co)
+            packed = torch.empty(B * int(n), dtype=torch.float32, device=dev)
+            rc = lib.nrt_hyperconv3d_pack_weights_f32(_lib.ptr(kernel), B, _lib.ints(ksize3), cin, cout, int(flipped),
+                                                      _lib.ptr(packed), _lib.stream_ptr(dev))
+            _lib.check(rc, 'nrt_hyperconv3d_pack_weights_f32')
+        else:
+            # the direct and single-input-channel kernels read the Keras layout (one batched re-layout for the input gradient)
+            weights = kernel.flip(1, 2, 3).transpose(4, 5).contiguous() if flipped else kernel
+        rc = lib.nrt_hyperconv3d_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
+                                     _lib.ints(S), _lib.ints(ksize3), co, int(dilation), int(same), int(kact), 0,
+                                     _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_hyperconv3d_f32')
+    return out
+
+
+class _HyperConvFn(torch.autograd.Function):
+    """Hyper-convolution with gradients wrt the features, the per-entry kernels and the per-entry biases."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, ksize3, dilation, same, act):
+        from .models import _ACT_LAST_FUSED, _elementwise
+        with torch.no_grad():
+            out = _hyperconv_run(x, kernel, bias, ksize3, dilation, same, act if act <= _ACT_LAST_FUSED else 0)
+            if act > _ACT_LAST_FUSED:             # activations beyond elu / relu: an element-wise pass over the layer output
+                out = _elementwise(out, act=act)
+        ctx.cfg = (tuple(ksize3), int(dilation), bool(same), int(act))
+        ctx.save_for_backward(x, kernel, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .models import _act_bwd
+        x, kernel, out = ctx.saved_tensors
+        ksize3, dilation, same, act = ctx.cfg
+        lib = _lib.lib()
+        dev = g.device
+        dpre = _act_bwd(g, out, act)
+        B, S = x.shape[0], list(x.shape[1:4])
+        cin, cout = kernel.shape[-2], kernel.shape[-1]
+        if not same:
+            # a 'valid' convolution is the 'same' one restricted to the outputs whose window lies inside the volume: its backward
+            # is the 'same' backward of the output gradient embedded in zeros (as models._ConvFn does it)
+            pb = [((ksize3[d] - 1) * dilation) // 2 for d in range(3)]
+            dpre = _pad3d(dpre.contiguous(), tuple(dpre.shape[1:4]), pb, S, crop=False)
+        need_x, need_k, need_b = ctx.needs_input_grad[:3]
+        dx = dk = db = None
+        if need_k or need_b:
+            dk = torch.zeros_like(kernel)
+            db = torch.zeros(B, cout, dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                rc = lib.nrt_hyperconv3d_wgrad_f32(_lib.ptr(x), _lib.ptr(dpre), _lib.ptr(dk), _lib.ptr(db), B, _lib.ints(S), cin,
+                                                   cout, _lib.ints(ksize3), dilation, _lib.stream_ptr(dev))
+            _lib.check(rc, 'nrt_hyperconv3d_wgrad_f32')
+        if need_x:
+            dx = _hyperconv_run(dpre, kernel, None, ksize3, dilation, True, 0, flipped=True)
+        return dx, dk if need_k else None, db if need_b else None, None, None, None, None
+
+
+def _hyperconv(x, kernel, bias, ksize3, dilation, same, act):
+    """x [B, X, Y, Z, cin], kernel [B, kx, ky, kz, cin, cout], bias [B, cout] or None (float32, checked by the callers)."""
+    _lib.require_device(x, kernel, bias)
+    x, kernel = x.contiguous(), kernel.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    if torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad or (bias is not None and bias.requires_grad)):
+        return _HyperConvFn.apply(x, kernel, bias, ksize3, dilation, same, act)
+    return _HyperConvFn.forward(_NoCtx(), x.detach(), kernel.detach(), None if bias is None else bias.detach(), ksize3, dilation,
+                                same, act)
+
+
+class _NoCtx:
+    """stands in for the autograd context when nothing is recorded"""
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
+def _conv_output_length_dilated(n, k, padding, stride, dilation):
+    """keras conv_utils.conv_output_length (neurite/tf/layers.py:2624-2630)"""
+    if n is None:
+        return None
+    dk = k + (k - 1) * (dilation - 1)
+    n = n if padding == 'same' else n - dk + 1
+    return (n + stride - 1) // stride
+
+
+def _keras_activation_name(activation):
+    """what tf.keras.activations.serialize(tf.keras.activations.get(a)) gives for the names the project knows"""
+    return 'linear' if activation is None else activation
+
+
+_TORCH_ACTS = {
+    None: lambda t: t, 'linear': lambda t: t, 'relu': torch.relu, 'elu': nn.functional.elu, 'sigmoid': torch.sigmoid,
+    'tanh': torch.tanh, 'softplus': nn.functional.softplus, 'softsign': nn.functional.softsign, 'selu': torch.selu,
+    'exponential': torch.exp, 'hard_sigmoid': lambda t: torch.clamp(0.2 * t + 0.5, 0.0, 1.0),
+    'leaky_relu': lambda t: nn.functional.leaky_relu(t, 0.2),
+}
+
+
+def _require_f32(what, *tensors):
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise NotImplementedError('%s: the hyper kernels are float32, got a %s tensor (non-float32 tensors are not implemented)'
+                                      % (what, t.dtype))
+
+
+class HyperConv(_Layer):
+    """
+    N-D hyper-convolution (neurite/tf/layers.py:2515-2647): a convolution without weights of its own -- called on
+    [features, kernel, bias] (or [features, kernel] with use_bias=False), features [B, *space, cin], kernel
+    [B, *kernel_size, cin, filters], bias [B, filters]: out[b] = activation(conv(features[b], kernel[b]) + bias[b]).
+    One kernel launch for the whole batch (nrt_hyperconv3d_f32); rank 1 and 2 run on the 3-D kernels with leading singleton axes.
+    Differentiable in all three inputs.  Limits (NotImplementedError): strides other than 1, tensors that are not float32,
+    rank above 3, a dilation rate that differs between the axes.
+    """
+
+    def __init__(self, rank, filters, kernel_size, strides=1, padding='valid', dilation_rate=1, activation=None, use_bias=True,
+                 name=None, **kwargs):
+        super().__init__(name=name, **kwargs)
+        self.rank = rank
+        self.filters = filters
+        self.kernel_size = _normalize_tuple(kernel_size, rank, 'kernel_size')
+        self.strides = _normalize_tuple(strides, rank, 'strides')
+        padding = str(padding).lower()
+        if padding not in ('valid', 'same', 'causal'):
+            raise ValueError('The `padding` argument must be a list/tuple or one of "valid", "same" (or "causal", only for '
+                             '`Conv1D). Received: ' + str(padding))
+        self.padding = padding
+        if self.padding == 'causal':                                                     # layers.py:2558-2559
+            raise ValueError('Causal padding is not supported for HyperConv')
+        self.dilation_rate = _normalize_tuple(dilation_rate, rank, 'dilation_rate')
+        if activation != 'softmax':
+            from .models import _act_code
+            _act_code(activation)                   # NotImplementedError for what the kernels do not know
+        else:
+            raise NotImplementedError('activation softmax is not implemented by the hyper layers')
+        self.activation = activation
+        self.use_bias = use_bias
+
+    def compute_output_shape(self, input_shape):
+        input_shape = list(input_shape[0])                                               # the features' shape
+        space = input_shape[1:-1]
+        new_space = [_conv_output_length_dilated(space[i], self.kernel_size[i], self.padding, self.strides[i], self.dilation_rate[i])
+                     for i in range(len(space))]
+        return tuple([input_shape[0]] + new_space + [self.filters])
+
+    def get_config(self):
+        config = {
+            'rank': self.rank, 'filters': self.filters, 'kernel_size': self.kernel_size, 'strides': self.strides,
+            'padding': self.padding, 'dilation_rate': self.dilation_rate,
+            'activation': _keras_activation_name(self.activation), 'use_bias': self.use_bias,
+        }
+        base_config = super().get_config()
+        return dict(list(base_config.items()) + list(config.items()))
+
+    def _check(self, inputs):
+        """the refusals, on shapes and dtypes alone (nothing here touches a device)"""
+        what = self.__class__.__name__
+        if not isinstance(inputs, (list, tuple)) or len(inputs) < 2:
+            raise ValueError('%s is called on [features, kernel, bias] or [features, kernel]' % what)
+        if self.use_bias and len(inputs) < 3:
+            raise ValueError('%s: use_bias=True needs a bias input: [features, kernel, bias]' % what)
+        x, kernel = inputs[0], inputs[1]
+        bias = inputs[2] if self.use_bias else None
+        if self.rank > 3:
+            raise NotImplementedError('%s: rank %d is not implemented (the conv kernels are 3-D: rank <= 3)' % (what, self.rank))
+        if any(s != 1 for s in self.strides):
+            raise NotImplementedError('%s: strides %s are not implemented (the conv kernels are stride 1)' % (what, (self.strides,)))
+        _require_f32(what, x, kernel, bias)
+        if x.dim() != self.rank + 2:
+            raise ValueError('%s: features must be [batch, %d spatial axes, channels], got shape %s' % (what, self.rank, tuple(x.shape)))
+        B, cin = x.shape[0], x.shape[-1]
+        if kernel.dim() != self.rank + 3 or kernel.shape[0] != B:
+            raise ValueError('%s: the kernel input must be [batch = %d, *kernel_size, channels, filters], got shape %s'
+                             % (what, B, tuple(kernel.shape)))
+        if tuple(kernel.shape[1:1 + self.rank]) != tuple(self.kernel_size):
+            raise ValueError('%s: kernel input of spatial size %s, layer kernel_size %s'
+                             % (what, tuple(kernel.shape[1:1 + self.rank]), self.kernel_size))
+        if kernel.shape[-2] != cin or kernel.shape[-1] != self.filters:
+            raise ValueError('%s: channel mismatch: features have %d channels and the layer %d filters, the kernel input is [.., %d, %d]'
+                             % (what, cin, self.filters, kernel.shape[-2], kernel.shape[-1]))
+        if bias is not None and tuple(bias.shape) != (B, self.filters):
+            raise ValueError('%s: the bias input must be [batch = %d, filters = %d], got shape %s' % (what, B, self.filters, tuple(bias.shape)))
+        dil = [d for d, k in zip(self.dilation_rate, self.kernel_size) if k > 1]
+        if any(d != dil[0] for d in dil):
+            raise NotImplementedError('%s: a dilation rate that differs between the axes %s is not implemented'
+                                      % (what, (self.dilation_rate,)))
+        return x, kernel, bias, (dil[0] if dil else 1)
+
+    def call(self, inputs):
+        from .models import _act_code, _lift, _unlift
+        x, kernel, bias, dilation = self._check(inputs)
+        ksize3 = (1,) * (3 - self.rank) + tuple(self.kernel_size)
+        x5 = _lift(x, self.rank)
+        k6 = kernel
+        for _ in range(3 - self.rank):
+            k6 = k6.unsqueeze(1)
+        out = _hyperconv(x5, k6, bias, ksize3, dilation, self.padding == 'same', _act_code(self.activation))
+        return _unlift(out, self.rank)
+
+
+class HyperConv2D(HyperConv):
+    """2D hyper-convolution layer (neurite/tf/layers.py:2650-2656)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(2, *args, **kwargs)
+
+
+class HyperConv3D(HyperConv):
+    """3D hyper-convolution layer (neurite/tf/layers.py:2659-2665)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(3, *args, **kwargs)
+
+
+class _FromDenseMixin:
+    """The two 'pseudo dense layers' of the FromDense layers (neurite/tf/layers.py:2751-2794, 2980-3023): hyp @ kernel + bias ->
+    activation -> reshape(-1, *target_shape).  A [B, H] x [H, units] product with B of a few entries: host plumbing (torch.addmm),
+    differentiable through torch, so the parameters and `hyp` get their gradients from the layer's per-entry kernel / bias gradients."""
+
+    def _init_from_dense(self, hyperkernel_use_bias, hyperbias_use_bias, hyperkernel_activation, hyperbias_activation):
+        self.hyperkernel_use_bias = hyperkernel_use_bias
+        self.hyperbias_use_bias = hyperbias_use_bias
+        for a in (hyperkernel_activation, hyperbias_activation):
+            if a not in _TORCH_ACTS:
+                raise NotImplementedError('activation %r is not implemented for the hyper mappings (%s are)'
+                                          % (a, ', '.join(sorted(str(k) for k in _TORCH_ACTS))))
+        self.hyperkernel_activation = hyperkernel_activation
+        self.hyperbias_activation = hyperbias_activation
+        self.hyperkernel = self.hyperbias = None
+
+    def _build_dense_pseudo_layer(self, name, last_dim, target_shape, use_bias, activation):
+        target_shape = tuple(int(v) for v in target_shape)
+        units = int(np.prod(target_shape))
+        dev = getattr(self, '_build_device', None)
+        # Keras' add_weight default for floating-point weights is glorot_uniform, for the bias vectors too (the reference passes no
+        # initializer, :2760-2770); fans of a rank-1 shape are (n, n)
+        limit = (6.0 / (last_dim + units)) ** 0.5
+        kernel = nn.Parameter(torch.empty(last_dim, units, dtype=torch.float32, device=dev).uniform_(-limit, limit))
+        setattr(self, '%s_kernel' % name, kernel)
+        bias = None
+        if use_bias:
+            blimit = (6.0 / (2 * units)) ** 0.5
+            bias = nn.Parameter(torch.empty(units, dtype=torch.float32, device=dev).uniform_(-blimit, blimit))
+            setattr(self, '%s_bias' % name, bias)
+        return (kernel, bias, activation, target_shape)
+
+    def _call_dense_pseudo_layer(self, inputs, params):
+        kernel, bias, activation, target_shape = params
+        if inputs.layout != torch.strided:
+            raise NotImplementedError('sparse hyper-network outputs are not implemented')
+        inputs = inputs.to(torch.float32)                                                # tf.cast(inputs, self._compute_dtype)
+        outputs = inputs @ kernel if bias is None else torch.addmm(bias, inputs, kernel)
+        outputs = _TORCH_ACTS[activation](outputs)
+        return outputs.reshape((-1,) + tuple(target_shape))
+
+    def _from_dense_config(self):
+        return {
+            'hyperkernel_use_bias': self.hyperkernel_use_bias, 'hyperbias_use_bias': self.hyperbias_use_bias,
+            'hyperkernel_activation': _keras_activation_name(self.hyperkernel_activation),
+            'hyperbias_activation': _keras_activation_name(self.hyperbias_activation),
+        }
+
+    def _check_from_dense(self, inputs):
+        what = self.__class__.__name__
+        if not isinstance(inputs, (list, tuple)) or len(inputs) != 2:
+            raise ValueError('%s is called on [features, last_hypernetwork_output]' % what)
+        x, hyp = inputs
+        if hyp.dim() != 2 or hyp.shape[0] != x.shape[0]:
+            raise ValueError('%s: the hypernetwork output must be [batch = %d, features], got shape %s' % (what, x.shape[0], tuple(hyp.shape)))
+        return x, hyp
+
+
+class HyperConvFromDense(_FromDenseMixin, HyperConv):
+    """
+    N-D hyper-convolution with the dense mapping from the last hypernetwork layer to the kernel and bias inside
+    (neurite/tf/layers.py:2668-2804).  Called on [features, hyp], hyp [B, H]; parameters (built on the first call):
+    hyperkernel_kernel [H, prod(kernel_size) * cin * filters], hyperkernel_bias, hyperbias_kernel [H, filters], hyperbias_bias.
+    """
+
+    def __init__(self, rank, filters, kernel_size, hyperkernel_use_bias=True, hyperbias_use_bias=True, hyperkernel_activation=None,
+                 hyperbias_activation=None, name=None, **kwargs):
+        super().__init__(rank, filters, kernel_size, name=name, **kwargs)
+        self._init_from_dense(hyperkernel_use_bias, hyperbias_use_bias, hyperkernel_activation, hyperbias_activation)
+
+    def build(self, input_shape):
+        last_dim = int(input_shape[1][-1])
+        kernel_shape = tuple(self.kernel_size) + (int(input_shape[0][-1]), self.filters)
+        self.hyperkernel = self._build_dense_pseudo_layer('hyperkernel', last_dim, kernel_shape, self.hyperkernel_use_bias,
+                                                          self.hyperkernel_activation)
+        if self.use_bias:
+            self.hyperbias = self._build_dense_pseudo_layer('hyperbias', last_dim, [self.filters], self.hyperbias_use_bias,
+                                                            self.hyperbias_activation)
+        self.built = True
+
+    def call(self, inputs):
+        x, hyp = self._check_from_dense(inputs)
+        kernel = self._call_dense_pseudo_layer(hyp, self.hyperkernel)
+        if self.use_bias:
+            return super().call([x, kernel, self._call_dense_pseudo_layer(hyp, self.hyperbias)])
+        return super().call([x, kernel])
+
+    def get_config(self):
+        base_config = super().get_config()
+        return dict(list(base_config.items()) + list(self._from_dense_config().items()))
+
+
+class HyperConv2DFromDense(HyperConvFromDense):
+    """2D hyper-convolution dense wrapping layer (neurite/tf/layers.py:2807-2813)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(2, *args, **kwargs)
+
+
+class HyperConv3DFromDense(HyperConvFromDense):
+    """3D hyper-convolution dense wrapping layer (neurite/tf/layers.py:2816-2822)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(3, *args, **kwargs)
+
+
+class HyperDense(_Layer):
+    """
+    Hyper-dense layer (neurite/tf/layers.py:2825-2903): called on [x, kernel, bias] (or [x, kernel] with use_bias=False), x
+    [B, ..., In] with any number of axes between the batch and the features, kernel [B, In, units], bias [B, units]:
+    out[b] = activation(x[b] @ kernel[b] + bias[b]).  Runs as the 1x1x1 case of the hyper-convolution with the rows of x[b] as voxels,
+    so it shares its kernels and its backward (matrix cores for In >= 8 and units <= 64, the direct kernel otherwise).  Those kernels
+    decline no float32 shape, so there is no torch.baddbmm path; what they do not take is refused: tensors that are not float32 and
+    sparse inputs (NotImplementedError).
+    """
+
+    def __init__(self, units, activation=None, use_bias=True, **kwargs):
+        super().__init__(**kwargs)
+        self.units = int(units) if not isinstance(units, int) else units
+        if activation == 'softmax':
+            raise NotImplementedError('activation softmax is not implemented by the hyper layers')
+        from .models import _act_code
+        _act_code(activation)
+        self.activation = activation
+        self.use_bias = use_bias
+        self.supports_masking = True
+
+    def compute_output_shape(self, input_shape):
+        input_shape = tuple(input_shape[0])
+        if len(input_shape) < 2:
+            raise ValueError('Shape %s must have rank at least 2' % (input_shape,))
+        return input_shape[:-1] + (self.units,)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({'units': self.units, 'activation': _keras_activation_name(self.activation), 'use_bias': self.use_bias})
+        return config
+
+    def _check(self, inputs):
+        what = self.__class__.__name__
+        if not isinstance(inputs, (list, tuple)) or len(inputs) < 2:
+            raise ValueError('%s is called on [x, kernel, bias] or [x, kernel]' % what)
+        if self.use_bias and len(inputs) < 3:
+            raise ValueError('%s: use_bias=True needs a bias input: [x, kernel, bias]' % what)
+        x, kernel = inputs[0], inputs[1]
+        bias = inputs[2] if self.use_bias else None
+        _require_f32(what, x, kernel, bias)
+        if x.layout != torch.strided:
+            raise NotImplementedError('%s: sparse inputs are not implemented' % what)
+        if x.dim() < 2:
+            raise ValueError('%s: x must be [batch, ..., features], got shape %s' % (what, tuple(x.shape)))
+        B, cin = x.shape[0], x.shape[-1]
+        if kernel.dim() != 3 or kernel.shape[0] != B:
+            raise ValueError('%s: the kernel input must be [batch = %d, features, units], got shape %s' % (what, B, tuple(kernel.shape)))
+        if kernel.shape[1] != cin or kernel.shape[2] != self.units:
+            raise ValueError('%s: channel mismatch: x has %d features and the layer %d units, the kernel input is [.., %d, %d]'
+                             % (what, cin, self.units, kernel.shape[1], kernel.shape[2]))
+        if bias is not None and tuple(bias.shape) != (B, self.units):
+            raise ValueError('%s: the bias input must be [batch = %d, units = %d], got shape %s' % (what, B, self.units, tuple(bias.shape)))
+        return x, kernel, bias
+
+    def call(self, inputs):
+        from .models import _act_code
+        x, kernel, bias = self._check(inputs)
+        B, cin = x.shape[0], x.shape[-1]
+        rows = 1
+        for n in x.shape[1:-1]:
+            rows *= int(n)
+        # the rows of x[b] as a volume of whole conv tiles where the row count allows it (a 1x1x1 kernel does not care which)
+        sx = next(a for a in (4, 2, 1) if rows % a == 0)
+        sy = next(a for a in (4, 2, 1) if (rows // sx) % a == 0)
+        x5 = x.reshape(B, sx, sy, rows // (sx * sy), cin)
+        out = _hyperconv(x5, kernel.reshape(B, 1, 1, 1, cin, self.units), bias, (1, 1, 1), 1, True, _act_code(self.activation))
+        return out.reshape(tuple(x.shape[:-1]) + (self.units,))
+
+
+class HyperDenseFromDense(_FromDenseMixin, HyperDense):
+    """
+    Hyper-dense layer with the dense mapping from the last hypernetwork layer to its kernel and bias inside
+    (neurite/tf/layers.py:2906-3033).  Called on [x, hyp]; parameters: hyperkernel_kernel [H, In * units], hyperkernel_bias,
+    hyperbias_kernel [H, units], hyperbias_bias.
+    """
+
+    def __init__(self, units, hyperkernel_use_bias=True, hyperbias_use_bias=True, hyperkernel_activation=None,
+                 hyperbias_activation=None, **kwargs):
+        super().__init__(units, **kwargs)
+        self._init_from_dense(hyperkernel_use_bias, hyperbias_use_bias, hyperkernel_activation, hyperbias_activation)
+
+    def build(self, input_shape):
+        last_dim = int(input_shape[1][-1])
+        self.hyperkernel = self._build_dense_pseudo_layer('hyperkernel', last_dim, [int(input_shape[0][-1]), self.units],
+                                                          self.hyperkernel_use_bias, self.hyperkernel_activation)
+        if self.use_bias:
+            self.hyperbias = self._build_dense_pseudo_layer('hyperbias', last_dim, [self.units], self.hyperbias_use_bias,
+                                                            self.hyperbias_activation)
+        self.built = True
+
+    def call(self, inputs):
+        x, hyp = self._check_from_dense(inputs)
+        kernel = self._call_dense_pseudo_layer(hyp, self.hyperkernel)
+        if self.use_bias:
+            return super().call([x, kernel, self._call_dense_pseudo_layer(hyp, self.hyperbias)])
+        return super().call([x, kernel])
+
+    def get_config(self):
+        base_config = super().get_config()
+        return dict(list(base_config.items()) + list(self._from_dense_config().items()))
