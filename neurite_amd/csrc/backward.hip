@@ -552,15 +552,21 @@ __global__ __launch_bounds__(256) void wcce_bwd_vec(const nrt_f4 *__restrict__ t
 // ---------------------------------------------------------------------------------------------
 // Fused backward of warp + soft Dice wrt the displacement field: the warped row is rebuilt in registers,
 // d dice / d warped is formed on the fly from the saved sums, and only grad_loc (12 B/voxel) is written.
-// G = L/4 lanes per voxel, 3-D.
+// 3-D, G lanes per voxel.  One body, two entry points:
+//   PAD = false (warp_dice_bwd_rows): L = 4 G labels, Gr is the constant G and the lane masks fold away.
+//   PAD = true (warp_dice_bwd_rows_pad): label counts L = 4 Gr that are not 4 * 2^k on the lane groups of the next power of two
+//   G >= Gr (the forward's warp_dice_tile_pad layout), rows L values apart.  A lane lg >= Gr loads nothing and adds an exact zero
+//   to each axis' xor-shuffle sum, so the gradient does not depend on G.
+// Same voxel schedules in both (grid-stride, or the x-march for G == 8), no atomics.
 // ---------------------------------------------------------------------------------------------
-template <int G, int MODE>
-__global__ __launch_bounds__(256) void warp_dice_bwd_rows(InterpBwdArgs ba, const float *__restrict__ fixed,
-                                                          const float *__restrict__ sums,
-                                                          const float *__restrict__ gdice, float eps) {
+template <int G, int MODE, bool PAD>
+__device__ __forceinline__ void warp_dice_bwd_rows_body(const InterpBwdArgs &ba, const float *__restrict__ fixed,
+                                                        const float *__restrict__ sums, const float *__restrict__ gdice,
+                                                        float eps, int Gr_arg) {
     constexpr int D = 3;
     constexpr int NG = 256 / G;
-    constexpr int L = G * 4;
+    const int Gr = PAD ? Gr_arg : G;                           // live lanes per voxel
+    const int L = Gr * 4;
     const InterpArgs &a = ba.f;
     // x-march schedule (G == 8): the block owns a 4 x 8 (y,z) patch of one batch entry and walks x, see interpn_core.h
     const bool xm = G == 8 && ba.tg.x_march;
@@ -575,16 +581,16 @@ __global__ __launch_bounds__(256) void warp_dice_bwd_rows(InterpBwdArgs ba, cons
     float *gl = ba.gloc + (long long)b * a.nout * D;
     const int lg = threadIdx.x % G;
     const unsigned g = threadIdx.x / G;
+    const bool lane_live = !PAD || lg < Gr;
     const int Y = a.S[1], Z = a.S[2];
-    float ca[4], cb[4];
-    {
+    float ca[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (lane_live) {
         const float *s = sums + (long long)b * 3 * L;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int l = lg * 4 + k;
             const float num = 2.0f * s[l] + eps, den = s[L + l] + s[2 * L + l] + eps;
             const float gd = gdice[(long long)b * L + l];
-            ca[k] = 0.0f; cb[k] = 0.0f;
             if (den != 0.0f) { ca[k] = 2.0f * gd / den; cb[k] = -2.0f * gd * num / (den * den); }
         }
     }
@@ -621,119 +627,7 @@ __global__ __launch_bounds__(256) void warp_dice_bwd_rows(InterpBwdArgs ba, cons
                 corner_1d(p[d], a.S[d], i0[d], i1[d], w0[u][d], w1[u][d]);
                 m[u][d] = (p[d] >= 0.0f && p[d] <= (float)(a.S[d] - 1)) ? 1.0f : 0.0f;
             }
-            t[u] = fix[(long long)q[u] * G + lg];
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
-                const long long idx = ((long long)(bx ? i1[0] : i0[0]) * Y + (by ? i1[1] : i0[1])) * Z + (bz ? i1[2] : i0[2]);
-                v[u][corner] = vol[idx * G + lg];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            nrt_f4 wp = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
-                const float wt = (bx ? w1[u][0] : w0[u][0]) * (by ? w1[u][1] : w0[u][1]) * (bz ? w1[u][2] : w0[u][2]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) wp[k] += wt * v[u][corner][k];
-            }
-            nrt_f4 gq;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gq[k] = (oob[u] || !live[u]) ? 0.0f : ca[k] * t[u][k] + cb[k] * wp[k];
-            float gacc[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const int bx = (corner >> 2) & 1, by = (corner >> 1) & 1, bz = corner & 1;
-                const float wx = bx ? w1[u][0] : w0[u][0], wy = by ? w1[u][1] : w0[u][1], wz = bz ? w1[u][2] : w0[u][2];
-                const nrt_f4 c = v[u][corner];
-                const float dot = gq[0] * c[0] + gq[1] * c[1] + gq[2] * c[2] + gq[3] * c[3];
-                gacc[0] += dot * (bx ? m[u][0] : -m[u][0]) * wy * wz;
-                gacc[1] += dot * wx * (by ? m[u][1] : -m[u][1]) * wz;
-                gacc[2] += dot * wx * wy * (bz ? m[u][2] : -m[u][2]);
-            }
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-#pragma unroll
-                for (int off = 1; off < G; off <<= 1) gacc[d] += __shfl_xor(gacc[d], off, 64);
-            if (live[u] && lg == 0) {
-                float *dst = gl + (long long)q[u] * 3;
-                dst[0] = gacc[0]; dst[1] = gacc[1]; dst[2] = gacc[2];
-            }
-        }
-    }
-}
-
-// warp_dice_bwd_rows for label counts L = 4 Gr that are not 4 * 2^k: lane groups of the next power of two G >= Gr (the forward's
-// warp_dice_tile_pad layout), rows L values apart.  A lane lg >= Gr loads nothing and adds an exact zero to each axis' xor-shuffle
-// sum, so the gradient does not depend on G.  Same voxel schedules (grid-stride, or the x-march for G == 8), no atomics.
-template <int G, int MODE>
-__global__ __launch_bounds__(256) void warp_dice_bwd_rows_pad(InterpBwdArgs ba, const float *__restrict__ fixed,
-                                                              const float *__restrict__ sums,
-                                                              const float *__restrict__ gdice, float eps, int Gr) {
-    constexpr int D = 3;
-    constexpr int NG = 256 / G;
-    const int L = Gr * 4;
-    const InterpArgs &a = ba.f;
-    const bool xm = G == 8 && ba.tg.x_march;
-    int b = blockIdx.y, xm_x0 = 0, xm_y0 = 0, xm_z0 = 0, xm_len = 0;
-    if (xm) {
-        unsigned prow;
-        if (!xmarch_block(ba.tg, a.O[0], b, prow, xm_x0, xm_y0, xm_z0, xm_len)) return;
-    }
-    const nrt_f4 *vol = (const nrt_f4 *)((const float *)a.vol + (long long)b * a.vol_bs);
-    const float *locb = a.loc + (long long)b * a.loc_bs;
-    const nrt_f4 *fix = (const nrt_f4 *)(fixed + (long long)b * a.out_bs);
-    float *gl = ba.gloc + (long long)b * a.nout * D;
-    const int lg = threadIdx.x % G;
-    const unsigned g = threadIdx.x / G;
-    const bool lane_live = lg < Gr;
-    const int Y = a.S[1], Z = a.S[2];
-    float ca[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (lane_live) {
-        const float *s = sums + (long long)b * 3 * L;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int l = lg * 4 + k;
-            const float num = 2.0f * s[l] + eps, den = s[L + l] + s[2 * L + l] + eps;
-            const float gd = gdice[(long long)b * L + l];
-            if (den != 0.0f) { ca[k] = 2.0f * gd / den; cb[k] = -2.0f * gd * num / (den * den); }
-        }
-    }
-    constexpr int U = 2;
-    const unsigned ngroups = gridDim.x * NG;
-    unsigned niter = (a.nout + ngroups * U - 1) / (ngroups * U);
-    if (xm) niter = ((unsigned)xm_len + U - 1) / U;
-    for (unsigned it = 0; it < niter; ++it) {
-        unsigned q[U];
-        bool live[U], oob[U];
-        float w0[U][3], w1[U][3], m[U][3];
-        nrt_f4 t[U], v[U][8];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            unsigned qq;
-            if (xm) {
-                const int x = xm_x0 + (int)(it * U + u), y = xm_y0 + (int)(g >> ba.tg.ltz), z = xm_z0 + (int)(g & ((1u << ba.tg.ltz) - 1u));
-                const bool in = x < xm_x0 + xm_len && y < a.O[1] && z < a.O[2];
-                qq = in ? ((unsigned)x * (unsigned)a.O[1] + (unsigned)y) * (unsigned)a.O[2] + (unsigned)z : 0xffffffffu;
-            } else {
-                qq = blockIdx.x * NG + g + (it * U + u) * ngroups;
-            }
-            live[u] = qq < a.nout;
-            q[u] = live[u] ? qq : a.nout - 1;
-            int qd[NRT_MAXD];
-            float p[NRT_MAXD];
-            decode<D>(a, q[u], qd);
-            load_loc<D, MODE>(a, locb, q[u], qd, p);
-            oob[u] = a.has_fill ? out_of_bounds<D>(a, p) : false;
-            int i0[3], i1[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                corner_1d(p[d], a.S[d], i0[d], i1[d], w0[u][d], w1[u][d]);
-                m[u][d] = (p[d] >= 0.0f && p[d] <= (float)(a.S[d] - 1)) ? 1.0f : 0.0f;
-            }
+            // a dead lane keeps exact zero rows
             t[u] = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) v[u][corner] = (nrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -784,6 +678,27 @@ __global__ __launch_bounds__(256) void warp_dice_bwd_rows_pad(InterpBwdArgs ba, 
             }
         }
     }
+}
+
+// Waves per SIMD of the 4 * 2^k entry point.  The wide lane groups on the grid stride lose time with a fourth wave (more rows in
+// flight per CU than L1 holds): forward + backward at 64 / 128 labels 6.33 -> 6.39 and 13.7 -> 14.0 ms, back at 6.30 / 13.7 with
+// three (profiles/refactor_fold_pad/).  These are the instances that took more than 128 registers, hence three waves, while the
+// kernel was its own body; every other instance, and the padded entry point (x-march at G = 8: 11 % faster with four), is left alone.
+constexpr int bwd_rows_max_waves(int G, int mode) { return G >= 16 && (mode == NRT_LOC_SHIFT || G == 64) ? 3 : 8; }
+
+template <int G, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, bwd_rows_max_waves(G, MODE))))
+void warp_dice_bwd_rows(InterpBwdArgs ba, const float *__restrict__ fixed,
+                                                          const float *__restrict__ sums,
+                                                          const float *__restrict__ gdice, float eps) {
+    warp_dice_bwd_rows_body<G, MODE, false>(ba, fixed, sums, gdice, eps, G);
+}
+
+template <int G, int MODE>
+__global__ __launch_bounds__(256) void warp_dice_bwd_rows_pad(InterpBwdArgs ba, const float *__restrict__ fixed,
+                                                              const float *__restrict__ sums,
+                                                              const float *__restrict__ gdice, float eps, int Gr) {
+    warp_dice_bwd_rows_body<G, MODE, true>(ba, fixed, sums, gdice, eps, Gr);
 }
 
 // The same backward for 32 labels on the x-march schedule, software-pipelined like the fused forward (fused.hip): the rows of
@@ -1497,16 +1412,35 @@ extern "C" int nrt_wcce_bwd_f32(const float *y_true, const float *y_pred, const 
     return NRT_OK;
 }
 
+namespace {
+// Gr == G: the 4 * 2^k entry point, else the padded one.  G = 1 has no padded form (Gr == G there)
+template <int G>
+void launch_warp_dice_bwd_rows(dim3 grid, hipStream_t st, const InterpBwdArgs &ba, int loc_mode, const float *fixed, const float *sums,
+                               const float *gdice, float eps, int Gr) {
+    if constexpr (G > 1) {
+        if (Gr != G) {
+            if (loc_mode == NRT_LOC_SHIFT)
+                hipLaunchKernelGGL((warp_dice_bwd_rows_pad<G, NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, gdice, eps, Gr);
+            else
+                hipLaunchKernelGGL((warp_dice_bwd_rows_pad<G, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed, sums, gdice, eps, Gr);
+            return;
+        }
+    }
+    if (loc_mode == NRT_LOC_SHIFT)
+        hipLaunchKernelGGL((warp_dice_bwd_rows<G, NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, gdice, eps);
+    else
+        hipLaunchKernelGGL((warp_dice_bwd_rows<G, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed, sums, gdice, eps);
+}
+}  // namespace
+
 extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, const float *fixed, const float *sums,
                                      const float *grad_dice, float *grad_loc, const int *vol_shape, const int *out_shape,
                                      int nlabels, int batch, long long loc_batch_stride, int loc_mode, int has_fill,
                                      float laplace_smoothing, void *stream) {
     if (!moving || !loc || !fixed || !sums || !grad_dice || !grad_loc) return NRT_ERR_INVALID_ARG;
     if (loc_mode != NRT_LOC_ABSOLUTE && loc_mode != NRT_LOC_SHIFT) return NRT_ERR_INVALID_ARG;
-    if (nlabels < 4 || nlabels > 256 || nlabels % 4) return NRT_ERR_UNSUPPORTED;
-    const int Gr = nlabels / 4;
-    int G = 1;                                                    // lanes per voxel: the next power of two >= L / 4
-    while (G < Gr) G <<= 1;
+    const int G = fused_group(nlabels), Gr = nlabels / 4;         // lanes per voxel, live lanes (interpn_core.h)
+    if (!G) return NRT_ERR_UNSUPPORTED;
     if ((((uintptr_t)moving | (uintptr_t)fixed) & 15) != 0) return NRT_ERR_UNSUPPORTED;
     InterpBwdArgs ba;
     float dummy;
@@ -1532,39 +1466,15 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
         grid = dim3(nrt_xcd_grid(per_batch * (unsigned)batch), 1);
         ba.tg.depth_sync = 8;
     }
-#define NRT_WDB(GG)                                                                                              \
-    if (loc_mode == NRT_LOC_SHIFT)                                                                               \
-        hipLaunchKernelGGL((warp_dice_bwd_rows<GG, NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums,     \
-                           grad_dice, laplace_smoothing);                                                        \
-    else                                                                                                         \
-        hipLaunchKernelGGL((warp_dice_bwd_rows<GG, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed, sums,  \
-                           grad_dice, laplace_smoothing);
-    if (Gr != G) {
-#define NRT_WDB_PAD(GG)                                                                                          \
-    if (loc_mode == NRT_LOC_SHIFT)                                                                               \
-        hipLaunchKernelGGL((warp_dice_bwd_rows_pad<GG, NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, \
-                           grad_dice, laplace_smoothing, Gr);                                                    \
-    else                                                                                                         \
-        hipLaunchKernelGGL((warp_dice_bwd_rows_pad<GG, NRT_LOC_ABSOLUTE>), grid, dim3(256), 0, st, ba, fixed,    \
-                           sums, grad_dice, laplace_smoothing, Gr);
-        switch (G) {
-            case 2: NRT_WDB_PAD(2) break;
-            case 4: NRT_WDB_PAD(4) break;
-            case 8: NRT_WDB_PAD(8) break;
-            case 16: NRT_WDB_PAD(16) break;
-            case 32: NRT_WDB_PAD(32) break;
-            default: NRT_WDB_PAD(64) break;
-        }
-#undef NRT_WDB_PAD
-        NRT_CHECK_LAUNCH();
-        return NRT_OK;
-    }
-    if (G == 8 && ba.tg.x_march && nrt_bwd_wc() && nrt_wc_interpn_supported(&ba.f, batch))
+    // exactly 32 labels on the x-march: the wave-cache gather, or the pipelined kernel (24 and 28 labels share G = 8 and the
+    // schedule, and run warp_dice_bwd_rows_pad on it)
+    const bool xm32 = Gr == 8 && ba.tg.x_march;
+    if (xm32 && nrt_bwd_wc() && nrt_wc_interpn_supported(&ba.f, batch))
         return nrt_wc_bwd_launch(&ba.f, batch, loc_mode, fixed, sums, grad_dice, laplace_smoothing, grad_loc, stream);
     // the pipelined kernel forms 32-bit byte offsets of rows and locations
     const bool xm_fits = (unsigned long long)nin * nlabels * 4ull < (1ull << 32) &&
                          (unsigned long long)ba.f.nout * nlabels * 4ull < (1ull << 32);
-    if (G == 8 && ba.tg.x_march && xm_fits) {
+    if (xm32 && xm_fits) {
         if (loc_mode == NRT_LOC_SHIFT)
             hipLaunchKernelGGL((warp_dice_bwd_xm<NRT_LOC_SHIFT>), grid, dim3(256), 0, st, ba, fixed, sums, grad_dice, laplace_smoothing);
         else
@@ -1572,6 +1482,7 @@ extern "C" int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, cons
         NRT_CHECK_LAUNCH();
         return NRT_OK;
     }
+#define NRT_WDB(GG) launch_warp_dice_bwd_rows<GG>(grid, st, ba, loc_mode, fixed, sums, grad_dice, laplace_smoothing, Gr);
     switch (G) {
         case 1: NRT_WDB(1) break;
         case 2: NRT_WDB(2) break;

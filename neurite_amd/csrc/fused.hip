@@ -59,13 +59,35 @@ constexpr int FUSED_SYNC = 8;
 // 1.158 -> 1.140 ms (two alternating repeats, profiles/archive/r03_lab/fused_occupancy_depth.jsonl)
 constexpr int FUSED_MINW = 3;
 
-template <int G, int MODE, bool STORE, int MINW, typename ST = float>
-__global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGeom tg, const void *__restrict__ fixed,
-                                                      float *__restrict__ fpart, float *__restrict__ mpart) {
+// The body of both entry points below.  PAD = false (warp_dice_tile): L = 4 G labels, G a power of two, every lane of a group of G
+// owns labels 4 lg .. 4 lg + 3 of its voxel; Gr is the constant G and every `PAD ? ... : ...` folds away.
+//
+// PAD = true (warp_dice_tile_pad): label counts L = 4 Gr that are not 4 * 2^k (12, 20, 24, 36, ...) on the lane groups of the next
+// power of two G >= Gr (dice.hip's layout), so the tile schedule, the xor-shuffle tree and the x-march are the same.  Lane lg < Gr owns
+// labels 4 lg .. 4 lg + 3 of rows L values apart; a lane lg >= Gr stores nothing, adds +0 to the sums and +-inf to the extrema, and
+// loads the pieces of lane Gr - 1 (the same 16 or 8 bytes as that lane, so no extra traffic: loads under a lane mask would break the
+// counted waits of the two-deep pipeline -- with them the compiler drained every load before each blend).  Row offsets are the
+// corner-000 row times the row's bytes (one 32-bit multiply: Gr is not a power of two) plus uniform x / y / z steps for the corners that
+// differ from it.  The blend and the Dice terms are the same operation for operation, and the partial rows hold exactly 3 L sums, so
+// dice_finalize_soft reduces them unchanged.
+//
+// How the body receives the kernel's two argument structs decides the scalar set-up the compiler emits, and these kernels sit at the
+// 106-SGPR ceiling.  By reference is the form whose registers and occupancy are the two-copy kernels' in all 312 instantiations (both
+// by value: 16 cross the 128-register line).  Two groups need another form to keep their time (profiles/refactor_fold_pad/):
+// padded, identity-grid locations, `warped` stored: by reference about 30 scalars are parked in VGPR lanes and read back inside the
+// pipelined loop (+2 %); with InterpArgs by value none are.  Padded bf16 storage: TileGeom by value.
+template <bool BY_VALUE, typename T> using BodyArg = std::conditional_t<BY_VALUE, const T, const T &>;
+template <int G, int MODE, bool STORE, typename ST, bool PAD>
+__device__ __forceinline__ void warp_dice_tile_body(BodyArg<PAD && MODE == NRT_LOC_LINSPACE && STORE, InterpArgs> a,
+                                                    BodyArg<PAD && !std::is_same<ST, float>::value, TileGeom> tg,
+                                                    const void *__restrict__ fixed,
+                                                    float *__restrict__ fpart, float *__restrict__ mpart, int Gr_arg) {
     typedef typename RowT<ST>::T Row;
     constexpr unsigned RB = RowT<ST>::BYTES;
     constexpr int NG = 256 / G;
-    constexpr int L = 4 * G;
+    constexpr int LP = 4 * G;                                  // the (padded) count: sizes the LDS of the block reduction
+    const int Gr = PAD ? Gr_arg : G;                           // live lanes per voxel
+    const int L = 4 * Gr;
     // persistent blocks: block (k = XCD, jb) walks the tiles jb, jb + nb, jb + 2 nb ... of XCD k's slab and
     // writes ONE partial at the end (gridDim.x <= 2048 keeps the second stage short)
     const unsigned k = blockIdx.x % NRT_NXCD, jb = blockIdx.x / NRT_NXCD;
@@ -82,12 +104,16 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGe
 
     const char *volb = (const char *)a.vol + (long long)b * a.vol_bs * (long long)sizeof(ST);
     const float *locb = a.loc ? a.loc + (long long)b * a.loc_bs : nullptr;
-    nrt_f4 *out = (nrt_f4 *)((float *)a.out + (long long)b * a.out_bs);
+    char *out = (char *)((float *)a.out + (long long)b * a.out_bs);
     const char *fix = (const char *)fixed + (long long)b * a.out_bs * (long long)sizeof(ST);
     const int lg = threadIdx.x % G;
     const int g = threadIdx.x / G;
+    const bool live = !PAD || lg < Gr;
+    const int lgl = PAD ? min(lg, Gr - 1) : lg;                // the piece a lane loads
     int npass = tg.plane_major ? tg.tz : (1 << (tg.ltx + tg.lty + tg.ltz)) / NG;
     const unsigned SY = (unsigned)a.S[1], SZ = (unsigned)a.S[2];
+    // PAD: bytes of one row and the steps between corner rows (all < 2^32: the C entry bounds the volume's bytes)
+    const unsigned rowB = (unsigned)Gr * RB, zB = rowB, yB = SZ * rowB, xB = SY * SZ * rowB, lgB = (unsigned)lgl * RB;
 
     // sums as float2 halves: the blend and the Dice accumulation run on v_pk_mul_f32 / v_pk_add_f32 (two IEEE fp32 operations
     // per issue slot, no fusion -> bit-identical to the scalar sequence); the kernel is bound by VALU issue, not by memory
@@ -133,14 +159,14 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGe
             }
         };
         // the per-voxel state that travels from prepare() to finish() is passed as separate scalars: as members of one struct
-        // the three lower weights were re-loaded pairwise, which kept the struct in memory (= in LDS, 24 B per thread)
-        struct FM { float w0x, w0y, w0z, w1x, w1y, w1z; unsigned q; bool oob, valid; };
+        // the three lower weights were re-loaded pairwise, which kept the struct in memory (= in LDS, 24 B per thread).  The upper
+        // weights do not travel: finish() recomputes them.  Q is the voxel's row index, PAD: the byte offset of the lane's piece of
+        // the voxel's `fixed` (and `warped`) row
         auto prepare = [&](int pass, const float (&praw)[NRT_MAXD], float &W0x, float &W0y, float &W0z, unsigned &Q, bool &VALID,
                            bool &OOB, unsigned (&off)[8]) {
-            FM m;
             int qd[NRT_MAXD];
-            voxel(pass, qd, m.valid);
-            m.q = nrt_mad24(nrt_mad24((unsigned)qd[0], (unsigned)a.O[1], (unsigned)qd[1]), (unsigned)a.O[2], (unsigned)qd[2]);
+            voxel(pass, qd, VALID);
+            const unsigned q = nrt_mad24(nrt_mad24((unsigned)qd[0], (unsigned)a.O[1], (unsigned)qd[1]), (unsigned)a.O[2], (unsigned)qd[2]);
             float p[NRT_MAXD];
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
@@ -150,35 +176,44 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGe
                           : ((qd[d] == a.O[d] - 1) ? (float)(a.S[d] - 1) : nrt_mul(a.delta[d], (float)qd[d]));
             }
             int i0x, i1x, i0y, i1y, i0z, i1z;              // scalars, not arrays: an array here ends up in LDS
-            corner_1d(p[0], a.S[0], i0x, i1x, m.w0x, m.w1x);
-            corner_1d(p[1], a.S[1], i0y, i1y, m.w0y, m.w1y);
-            corner_1d(p[2], a.S[2], i0z, i1z, m.w0z, m.w1z);
-            m.oob = a.has_fill ? out_of_bounds<3>(a, p) : false;
+            float w1;
+            corner_1d(p[0], a.S[0], i0x, i1x, W0x, w1);
+            corner_1d(p[1], a.S[1], i0y, i1y, W0y, w1);
+            corner_1d(p[2], a.S[2], i0z, i1z, W0z, w1);
+            OOB = a.has_fill ? out_of_bounds<3>(a, p) : false;
+            if constexpr (PAD) {
+                // corner_1d clips i1 to [i0, i0 + 1]: a corner's row is the corner-000 row plus the steps of the axes it moves along
+                const unsigned base = nrt_mad24(nrt_mad24((unsigned)i0x, SY, (unsigned)i0y), SZ, (unsigned)i0z) * rowB + lgB;
+                const unsigned dx = i1x != i0x ? xB : 0u, dy = i1y != i0y ? yB : 0u, dz = i1z != i0z ? zB : 0u;
+                off[0] = base; off[1] = base + dz; off[2] = base + dy; off[3] = off[2] + dz;
+                off[4] = base + dx; off[5] = off[4] + dz; off[6] = off[4] + dy; off[7] = off[6] + dz;
+                Q = q * rowB + lgB;
+            } else {
 #pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const unsigned ix = (corner & 4) ? i1x : i0x;
-                const unsigned iy = (corner & 2) ? i1y : i0y;
-                const unsigned iz = (corner & 1) ? i1z : i0z;
-                off[corner] = (nrt_mad24(nrt_mad24(ix, SY, iy), SZ, iz) * (unsigned)G + (unsigned)lg) * RB;
+                for (int corner = 0; corner < 8; ++corner) {
+                    const unsigned ix = (corner & 4) ? i1x : i0x;
+                    const unsigned iy = (corner & 2) ? i1y : i0y;
+                    const unsigned iz = (corner & 1) ? i1z : i0z;
+                    off[corner] = (nrt_mad24(nrt_mad24(ix, SY, iy), SZ, iz) * (unsigned)G + (unsigned)lg) * RB;
+                }
+                Q = q;
             }
-            W0x = m.w0x; W0y = m.w0y; W0z = m.w0z; Q = m.q; VALID = m.valid; OOB = m.oob;
         };
-        auto load_rows = [&](const unsigned (&off)[8], unsigned q, Row (&R)[8], Row &T) {
+        // never under a lane mask: the counted waits of the pipeline need every lane to issue every load
+        auto load_rows = [&](const unsigned (&off)[8], unsigned Q, Row (&R)[8], Row &T) {
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) R[corner] = *(const Row *)(volb + (size_t)off[corner]);
-            T = __builtin_nontemporal_load((const Row *)(fix + (size_t)((q * (unsigned)G + (unsigned)lg) * RB)));
+            T = __builtin_nontemporal_load((const Row *)(fix + (size_t)(PAD ? Q : (Q * (unsigned)G + (unsigned)lg) * RB)));
         };
         auto finish = [&](float W0x, float W0y, float W0z, unsigned Q, bool VALID, bool OOB, const Row (&Rraw)[8], const Row &Traw) {
             nrt_f4 R[8];
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) R[corner] = RowT<ST>::widen(Rraw[corner]);
             const nrt_f4 T = RowT<ST>::widen(Traw);
-            FM m;
-            m.w0x = W0x; m.w0y = W0y; m.w0z = W0z; m.q = Q; m.valid = VALID; m.oob = OOB;
-            m.w1x = nrt_sub(1.0f, W0x); m.w1y = nrt_sub(1.0f, W0y); m.w1z = nrt_sub(1.0f, W0z);      // corner_1d's w1
+            const float W1x = nrt_sub(1.0f, W0x), W1y = nrt_sub(1.0f, W0y), W1z = nrt_sub(1.0f, W0z);       // corner_1d's w1
             // corner weights (wx * wy) * wz in the reference's order, two corners per packed multiply
-            const nrt_f2 wy2 = {m.w0y, m.w1y}, wz2 = {m.w0z, m.w1z};
-            const nrt_f2 wxy0 = (nrt_f2){m.w0x, m.w0x} * wy2, wxy1 = (nrt_f2){m.w1x, m.w1x} * wy2;
+            const nrt_f2 wy2 = {W0y, W1y}, wz2 = {W0z, W1z};
+            const nrt_f2 wxy0 = (nrt_f2){W0x, W0x} * wy2, wxy1 = (nrt_f2){W1x, W1x} * wy2;
             nrt_f2 wt2[4];
             wt2[0] = (nrt_f2){wxy0[0], wxy0[0]} * wz2;          // corners 0, 1
             wt2[1] = (nrt_f2){wxy0[1], wxy0[1]} * wz2;          // corners 2, 3
@@ -195,10 +230,10 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGe
             nrt_f4 acc = {al[0], al[1], ah[0], ah[1]};
             if (a.has_fill) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) acc[c] = apply_fill(acc[c], m.oob, a.fill_f);
+                for (int c = 0; c < 4; ++c) acc[c] = apply_fill(acc[c], OOB, a.fill_f);
             }
-            if (m.valid) {
-                if (STORE) __builtin_nontemporal_store(acc, (nrt_f4 *)((char *)out + (size_t)((m.q * (unsigned)G + (unsigned)lg) * 16u)));
+            if (VALID && live) {
+                if (STORE) __builtin_nontemporal_store(acc, (nrt_f4 *)(out + (size_t)(PAD ? Q : (Q * (unsigned)G + (unsigned)lg) * 16u)));
                 const nrt_f2 pl = {acc[0], acc[1]}, ph = {acc[2], acc[3]}, tl = {T[0], T[1]}, th = {T[2], T[3]};
                 stp_l = stp_l + tl * pl; stp_h = stp_h + th * ph;
                 stt_l = stt_l + tl * tl; stt_h = stt_h + th * th;
@@ -258,230 +293,6 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGe
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
     }
-    __shared__ float red[4][3 * L + 4];
-    const int lane = threadIdx.x & (NRT_WAVE - 1), wv = threadIdx.x / NRT_WAVE;
-    if (lane < G) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            red[wv][0 * L + 4 * lane + c] = stp[c];
-            red[wv][1 * L + 4 * lane + c] = stt[c];
-            red[wv][2 * L + 4 * lane + c] = spp[c];
-        }
-    }
-    if (lane == 0) { red[wv][3 * L + 0] = mnt; red[wv][3 * L + 1] = mxt; red[wv][3 * L + 2] = mnp; red[wv][3 * L + 3] = mxp; }
-    __syncthreads();
-    const long long pbase = tg.x_march ? ((long long)b * tg.prows + prow) : ((long long)b * gridDim.x + blockIdx.x);
-    for (int i = threadIdx.x; i < 3 * L; i += 256) {
-        float s = red[0][i];
-#pragma unroll
-        for (int w2 = 1; w2 < 4; ++w2) s += red[w2][i];
-        fpart[pbase * 3 * L + i] = s;
-    }
-    if (threadIdx.x < 4) {
-        float m = red[0][3 * L + threadIdx.x];
-        for (int w2 = 1; w2 < 4; ++w2)
-            m = (threadIdx.x & 1) ? fmaxf(m, red[w2][3 * L + threadIdx.x]) : fminf(m, red[w2][3 * L + threadIdx.x]);
-        mpart[pbase * 4 + threadIdx.x] = m;
-    }
-    if (tg.x_march) xmarch_zero_rows(tg, xw, 3 * L, fpart, mpart);
-}
-
-// warp_dice_tile for label counts L = 4 Gr that are not 4 * 2^k (12, 20, 24, 36, ...): the lane groups of the next power of two
-// G >= Gr (dice.hip's layout), so the tile schedule, the xor-shuffle tree and the x-march are warp_dice_tile's.  Lane lg < Gr owns
-// labels 4 lg .. 4 lg + 3 of rows L values apart; a lane lg >= Gr stores nothing, adds +0 to the sums and +-inf to the extrema, and
-// loads the pieces of lane Gr - 1 (the same 16 or 8 bytes as that lane, so no extra traffic: loads under a lane mask would break the
-// counted waits of the two-deep pipeline -- with them the compiler drained every load before each blend).  Row offsets are the corner-000 row times the row's bytes (one 32-bit multiply: Gr is not a power of two) plus uniform
-// x / y / z steps for the corners that differ from it.  The blend and the Dice terms are warp_dice_tile's, operation for operation,
-// and the partial rows hold exactly 3 L sums, so dice_finalize_soft reduces them unchanged.
-template <int G, int MODE, bool STORE, int MINW, typename ST = float>
-__global__ __launch_bounds__(256, MINW) void warp_dice_tile_pad(InterpArgs a, TileGeom tg, const void *__restrict__ fixed,
-                                                          float *__restrict__ fpart, float *__restrict__ mpart, int Gr) {
-    typedef typename RowT<ST>::T Row;
-    constexpr unsigned RB = RowT<ST>::BYTES;
-    constexpr int NG = 256 / G;
-    constexpr int LP = 4 * G;                                  // the padded count: sizes the LDS of the block reduction
-    const int L = 4 * Gr;
-    const unsigned k = blockIdx.x % NRT_NXCD, jb = blockIdx.x / NRT_NXCD;
-    unsigned per = tg.per2 * tg.nTz;
-    unsigned nb = gridDim.x / NRT_NXCD;
-    int b = blockIdx.y;
-    unsigned ucol = 0, prow = blockIdx.x;
-    XmWork xw = {};
-    if (tg.x_march) {
-        if (!xmarch_work(tg, a.O[0], xw)) return;
-        b = xw.b; prow = xw.prow; ucol = xw.ucol;
-        per = jb + 1; nb = 1;
-    }
-
-    const char *volb = (const char *)a.vol + (long long)b * a.vol_bs * (long long)sizeof(ST);
-    const float *locb = a.loc ? a.loc + (long long)b * a.loc_bs : nullptr;
-    char *out = (char *)((float *)a.out + (long long)b * a.out_bs);
-    const char *fix = (const char *)fixed + (long long)b * a.out_bs * (long long)sizeof(ST);
-    const int lg = threadIdx.x % G;
-    const int g = threadIdx.x / G;
-    const bool live = lg < Gr;
-    const int lgl = min(lg, Gr - 1);                           // the piece a lane loads
-    int npass = tg.plane_major ? tg.tz : (1 << (tg.ltx + tg.lty + tg.ltz)) / NG;
-    const unsigned SY = (unsigned)a.S[1], SZ = (unsigned)a.S[2];
-    // bytes of one row and the steps between corner rows (all < 2^32: the C entry bounds the volume's bytes)
-    const unsigned rowB = (unsigned)Gr * RB, zB = rowB, yB = SZ * rowB, xB = SY * SZ * rowB, lgB = (unsigned)lgl * RB;
-
-    nrt_f2 stp_l = {0, 0}, stp_h = {0, 0}, stt_l = {0, 0}, stt_h = {0, 0}, spp_l = {0, 0}, spp_h = {0, 0};
-    float mnt = INFINITY, mxt = -INFINITY, mnp = INFINITY, mxp = -INFINITY;
-
-    for (unsigned j = jb; j < per; j += nb) {
-        unsigned t2l, tzi;
-        if (tg.z_outer) { tzi = j / tg.per2; t2l = j % tg.per2; }
-        else { tzi = j % tg.nTz; t2l = j / tg.nTz; }
-        const unsigned t2 = k * tg.per2 + t2l;
-        if (!tg.x_march && t2 >= tg.nT2) continue;
-        int x0 = (int)(t2 / tg.nTy) << tg.ltx, y0 = (int)(t2 % tg.nTy) << tg.lty, z0 = (int)tzi * tg.tz;
-        if (tg.x_march) {
-            x0 = xw.x0;
-            const unsigned RY = 1u << tg.lry, RZ = 1u << tg.lrz;
-            const unsigned nRz = (tg.nTz + RZ - 1) / RZ;
-            const unsigned reg = ucol / (RY * RZ), w = ucol % (RY * RZ);
-            const unsigned cy = (reg / nRz) * RY + w / RZ, cz = (reg % nRz) * RZ + w % RZ;
-            y0 = (int)cy << tg.lty;
-            z0 = (int)cz << tg.ltz;
-            if (cy >= tg.nTy || cz >= tg.nTz) npass = 0;
-            const int xlen = xw.xlen;
-            if (npass) npass = (xlen << (tg.lty + tg.ltz)) / NG;
-            if (npass <= 0) continue;
-        }
-        auto voxel = [&](int pass, int (&qd)[NRT_MAXD], bool &valid) {
-            int x, y, z;
-            tile_voxel(tg, NG, pass, g, x0, y0, z0, x, y, z);
-            valid = (x < a.O[0]) && (y < a.O[1]) && (z < a.O[2]);
-            qd[0] = min(x, a.O[0] - 1); qd[1] = min(y, a.O[1] - 1); qd[2] = min(z, a.O[2] - 1);
-        };
-        auto fetch_loc = [&](int pass, float (&p)[NRT_MAXD]) {
-            int qd[NRT_MAXD]; bool valid;
-            voxel(pass, qd, valid);
-            const unsigned q = nrt_mad24(nrt_mad24((unsigned)qd[0], (unsigned)a.O[1], (unsigned)qd[1]), (unsigned)a.O[2], (unsigned)qd[2]);
-            if (MODE != NRT_LOC_LINSPACE) {
-                const float *lp = (const float *)((const char *)locb + (size_t)(nrt_times3(q) << 2));
-                p[0] = lp[0]; p[1] = lp[1]; p[2] = lp[2];
-            }
-        };
-        // Q carries the byte offset of the voxel's piece of its `fixed` (and `warped`) row
-        auto prepare = [&](int pass, const float (&praw)[NRT_MAXD], float &W0x, float &W0y, float &W0z, unsigned &Q, bool &VALID,
-                           bool &OOB, unsigned (&off)[8]) {
-            int qd[NRT_MAXD];
-            voxel(pass, qd, VALID);
-            const unsigned q = nrt_mad24(nrt_mad24((unsigned)qd[0], (unsigned)a.O[1], (unsigned)qd[1]), (unsigned)a.O[2], (unsigned)qd[2]);
-            float p[NRT_MAXD];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                if (MODE == NRT_LOC_ABSOLUTE) p[d] = praw[d];
-                else if (MODE == NRT_LOC_SHIFT) p[d] = nrt_add((float)qd[d], praw[d]);
-                else p[d] = (qd[d] == 0) ? 0.0f
-                          : ((qd[d] == a.O[d] - 1) ? (float)(a.S[d] - 1) : nrt_mul(a.delta[d], (float)qd[d]));
-            }
-            int i0x, i1x, i0y, i1y, i0z, i1z;
-            float w1;
-            corner_1d(p[0], a.S[0], i0x, i1x, W0x, w1);
-            corner_1d(p[1], a.S[1], i0y, i1y, W0y, w1);
-            corner_1d(p[2], a.S[2], i0z, i1z, W0z, w1);
-            OOB = a.has_fill ? out_of_bounds<3>(a, p) : false;
-            // corner_1d clips i1 to [i0, i0 + 1]: a corner's row is the corner-000 row plus the steps of the axes it moves along
-            const unsigned base = nrt_mad24(nrt_mad24((unsigned)i0x, SY, (unsigned)i0y), SZ, (unsigned)i0z) * rowB + lgB;
-            const unsigned dx = i1x != i0x ? xB : 0u, dy = i1y != i0y ? yB : 0u, dz = i1z != i0z ? zB : 0u;
-            off[0] = base; off[1] = base + dz; off[2] = base + dy; off[3] = off[2] + dz;
-            off[4] = base + dx; off[5] = off[4] + dz; off[6] = off[4] + dy; off[7] = off[6] + dz;
-            Q = q * rowB + lgB;
-        };
-        auto load_rows = [&](const unsigned (&off)[8], unsigned q, Row (&R)[8], Row &T) {
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) R[corner] = *(const Row *)(volb + (size_t)off[corner]);
-            T = __builtin_nontemporal_load((const Row *)(fix + (size_t)q));
-        };
-        auto finish = [&](float W0x, float W0y, float W0z, unsigned Q, bool VALID, bool OOB, const Row (&Rraw)[8], const Row &Traw) {
-            nrt_f4 R[8];
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) R[corner] = RowT<ST>::widen(Rraw[corner]);
-            const nrt_f4 T = RowT<ST>::widen(Traw);
-            const float W1x = nrt_sub(1.0f, W0x), W1y = nrt_sub(1.0f, W0y), W1z = nrt_sub(1.0f, W0z);
-            const nrt_f2 wy2 = {W0y, W1y}, wz2 = {W0z, W1z};
-            const nrt_f2 wxy0 = (nrt_f2){W0x, W0x} * wy2, wxy1 = (nrt_f2){W1x, W1x} * wy2;
-            nrt_f2 wt2[4];
-            wt2[0] = (nrt_f2){wxy0[0], wxy0[0]} * wz2;
-            wt2[1] = (nrt_f2){wxy0[1], wxy0[1]} * wz2;
-            wt2[2] = (nrt_f2){wxy1[0], wxy1[0]} * wz2;
-            wt2[3] = (nrt_f2){wxy1[1], wxy1[1]} * wz2;
-            nrt_f2 al = {0.0f, 0.0f}, ah = {0.0f, 0.0f};
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
-                const float wt = wt2[corner >> 1][corner & 1];
-                const nrt_f2 w2 = {wt, wt};
-                al = al + w2 * (nrt_f2){R[corner][0], R[corner][1]};
-                ah = ah + w2 * (nrt_f2){R[corner][2], R[corner][3]};
-            }
-            nrt_f4 acc = {al[0], al[1], ah[0], ah[1]};
-            if (a.has_fill) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[c] = apply_fill(acc[c], OOB, a.fill_f);
-            }
-            if (VALID && live) {
-                if (STORE) __builtin_nontemporal_store(acc, (nrt_f4 *)(out + (size_t)Q));
-                const nrt_f2 pl = {acc[0], acc[1]}, ph = {acc[2], acc[3]}, tl = {T[0], T[1]}, th = {T[2], T[3]};
-                stp_l = stp_l + tl * pl; stp_h = stp_h + th * ph;
-                stt_l = stt_l + tl * tl; stt_h = stt_h + th * th;
-                spp_l = spp_l + pl * pl; spp_h = spp_h + ph * ph;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    mnt = fminf(mnt, T[c]); mxt = fmaxf(mxt, T[c]);
-                    mnp = fminf(mnp, acc[c]); mxp = fmaxf(mxp, acc[c]);
-                }
-            }
-        };
-
-        Row Ra[8], Rb[8], Ta, Tb;
-        float Ax, Ay, Az, Bx, By, Bz;
-        unsigned Aq, Bq;
-        bool Av, Ao, Bv, Bo;
-        unsigned off[8];
-        float pn[NRT_MAXD] = {0.0f, 0.0f, 0.0f};
-        const int last = npass - 1;
-        fetch_loc(0, pn);
-        prepare(0, pn, Ax, Ay, Az, Aq, Av, Ao, off);
-        fetch_loc(min(1, last), pn);
-        __builtin_amdgcn_sched_barrier(0);
-        load_rows(off, Aq, Ra, Ta);
-        __builtin_amdgcn_sched_barrier(0);
-        for (int pass = 0; pass < npass; pass += 2) {
-            if ((pass & (FUSED_SYNC - 1)) == 0) __builtin_amdgcn_s_barrier();
-            prepare(min(pass + 1, last), pn, Bx, By, Bz, Bq, Bv, Bo, off);
-            Bv = Bv && (pass + 1 < npass);
-            __builtin_amdgcn_sched_barrier(0);
-            fetch_loc(min(pass + 2, last), pn);
-            load_rows(off, Bq, Rb, Tb);
-            __builtin_amdgcn_sched_barrier(0);
-            finish(Ax, Ay, Az, Aq, Av, Ao, Ra, Ta);
-            __builtin_amdgcn_sched_barrier(0);
-            prepare(min(pass + 2, last), pn, Ax, Ay, Az, Aq, Av, Ao, off);
-            Av = Av && (pass + 2 < npass);
-            __builtin_amdgcn_sched_barrier(0);
-            fetch_loc(min(pass + 3, last), pn);
-            load_rows(off, Aq, Ra, Ta);
-            __builtin_amdgcn_sched_barrier(0);
-            finish(Bx, By, Bz, Bq, Bv, Bo, Rb, Tb);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-
-    nrt_f4 stp = {stp_l[0], stp_l[1], stp_h[0], stp_h[1]}, stt = {stt_l[0], stt_l[1], stt_h[0], stt_h[1]},
-           spp = {spp_l[0], spp_l[1], spp_h[0], spp_h[1]};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        stp[c] = wave_xor_add(stp[c], G);
-        stt[c] = wave_xor_add(stt[c], G);
-        spp[c] = wave_xor_add(spp[c], G);
-    }
-    for (int off = 1; off < NRT_WAVE; off <<= 1) {
-        mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
-        mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
-    }
     __shared__ float red[4][3 * LP + 4];
     const int lane = threadIdx.x & (NRT_WAVE - 1), wv = threadIdx.x / NRT_WAVE;
     if (lane < Gr) {
@@ -508,6 +319,21 @@ __global__ __launch_bounds__(256, MINW) void warp_dice_tile_pad(InterpArgs a, Ti
         mpart[pbase * 4 + threadIdx.x] = m;
     }
     if (tg.x_march) xmarch_zero_rows(tg, xw, 3 * L, fpart, mpart);
+}
+
+// The two entry points.  Their names and template arguments are public: nrt_warp_dice_kernel_name prints them and the counter
+// evidence under profiles/ is keyed by them.  L = 4 G labels ...
+template <int G, int MODE, bool STORE, int MINW, typename ST = float>
+__global__ __launch_bounds__(256, MINW) void warp_dice_tile(InterpArgs a, TileGeom tg, const void *__restrict__ fixed,
+                                                      float *__restrict__ fpart, float *__restrict__ mpart) {
+    warp_dice_tile_body<G, MODE, STORE, ST, false>(a, tg, fixed, fpart, mpart, G);
+}
+
+// ... and L = 4 Gr labels, Gr < G, on the same lane groups
+template <int G, int MODE, bool STORE, int MINW, typename ST = float>
+__global__ __launch_bounds__(256, MINW) void warp_dice_tile_pad(InterpArgs a, TileGeom tg, const void *__restrict__ fixed,
+                                                          float *__restrict__ fpart, float *__restrict__ mpart, int Gr) {
+    warp_dice_tile_body<G, MODE, STORE, ST, true>(a, tg, fixed, fpart, mpart, Gr);
 }
 
 // the fused kernel writes one partial per block: size the workspace for its grid
@@ -558,87 +384,64 @@ inline FusedChoice fused_choose(const InterpArgs &a, const TileGeom &tg, int G, 
     return c;
 }
 
-template <int G, typename ST>
-int launch_fused(const InterpArgs &a, const TileGeom &tg, unsigned nblocks, int batch, int mode, bool store,
+// One launch of either entry point.  dyn > 0: the kernel is given that much (unused) dynamic LDS
+template <typename... P, typename... A>
+int launch_kernel(void (*kern)(P...), dim3 grid, unsigned dyn, hipStream_t st, A... args) {
+    if (dyn && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
+        return NRT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, grid, dim3(256), dyn, st, args...);
+    return NRT_OK;
+}
+
+template <int G, int MODE, bool STORE, int MINW, typename ST, bool PAD>
+int launch_tile(dim3 grid, unsigned dyn, hipStream_t st, const InterpArgs &a, const TileGeom &tg, const void *fixed, float *fpart,
+                float *mpart, int Gr) {
+    if constexpr (PAD) return launch_kernel(warp_dice_tile_pad<G, MODE, STORE, MINW, ST>, grid, dyn, st, a, tg, fixed, fpart, mpart, Gr);
+    else return launch_kernel(warp_dice_tile<G, MODE, STORE, MINW, ST>, grid, dyn, st, a, tg, fixed, fpart, mpart);
+}
+
+// PAD: Gr = L / 4 < G live lanes per voxel (warp_dice_tile_pad), the same schedules
+template <int G, typename ST, bool PAD>
+int launch_fused(const InterpArgs &a, const TileGeom &tg, unsigned nblocks, int batch, int mode, bool store, int Gr,
                  const void *fixed, float *fpart, float *mpart, hipStream_t st, bool allow_wc, bool want_minmax) {
-    if constexpr (G == 8 && std::is_same<ST, float>::value) {
+    if constexpr (G == 8 && std::is_same<ST, float>::value && !PAD) {
         if (fused_choose(a, tg, G, true, allow_wc).wc)
             return launch_wc(a, tg, nblocks, batch, mode, store, want_minmax, (const float *)fixed, fpart, mpart, st);
     }
-    dim3 grid(nblocks, batch), blk(256);
     // x-march: 75 KB of unused dynamic LDS per block = two blocks per CU, so that the blocks an XCD runs together are one region whose
-    // rows stay in its L2
-    const unsigned dyn = tg.x_march ? 75u * 1024u : 0u;
-    if (tg.x_march) {
-        grid = dim3(fused_xmarch_grid(tg, nblocks, batch), 1);
-#define NRT_FUSED_X(MODE)                                                                                           \
-    if (store) hipLaunchKernelGGL((warp_dice_tile<G, MODE, true, FUSED_MINW, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart); \
-    else {                                                                                                          \
-        if (hipFuncSetAttribute((const void *)warp_dice_tile<G, MODE, false, FUSED_MINW, ST>,                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return NRT_ERR_LAUNCH; \
-        hipLaunchKernelGGL((warp_dice_tile<G, MODE, false, FUSED_MINW, ST>), grid, blk, dyn, st, a, tg, fixed, fpart, mpart); \
-    }
-        switch (mode) {
-            case NRT_LOC_ABSOLUTE: NRT_FUSED_X(NRT_LOC_ABSOLUTE); break;
-            case NRT_LOC_SHIFT: NRT_FUSED_X(NRT_LOC_SHIFT); break;
-            default: NRT_FUSED_X(NRT_LOC_LINSPACE); break;
-        }
-#undef NRT_FUSED_X
-        return NRT_OK;
-    }
-#define NRT_FUSED(MODE)                                                                                          \
-    if (store) hipLaunchKernelGGL((warp_dice_tile<G, MODE, true, 1, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart); \
-    else hipLaunchKernelGGL((warp_dice_tile<G, MODE, false, 1, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart);
+    // rows stay in its L2 (the instance that stores `warped` runs without it)
+    const dim3 grid = tg.x_march ? dim3(fused_xmarch_grid(tg, nblocks, batch), 1) : dim3(nblocks, batch);
+    const unsigned dyn = tg.x_march && !store ? 75u * 1024u : 0u;
+#define NRT_FUSED(MODE)                                                                                                          \
+    return tg.x_march ? (store ? launch_tile<G, MODE, true, FUSED_MINW, ST, PAD>(grid, dyn, st, a, tg, fixed, fpart, mpart, Gr)  \
+                               : launch_tile<G, MODE, false, FUSED_MINW, ST, PAD>(grid, dyn, st, a, tg, fixed, fpart, mpart, Gr)) \
+                      : (store ? launch_tile<G, MODE, true, 1, ST, PAD>(grid, dyn, st, a, tg, fixed, fpart, mpart, Gr)           \
+                               : launch_tile<G, MODE, false, 1, ST, PAD>(grid, dyn, st, a, tg, fixed, fpart, mpart, Gr))
     switch (mode) {
-        case NRT_LOC_ABSOLUTE: NRT_FUSED(NRT_LOC_ABSOLUTE); break;
-        case NRT_LOC_SHIFT: NRT_FUSED(NRT_LOC_SHIFT); break;
-        default: NRT_FUSED(NRT_LOC_LINSPACE); break;
+        case NRT_LOC_ABSOLUTE: NRT_FUSED(NRT_LOC_ABSOLUTE);
+        case NRT_LOC_SHIFT: NRT_FUSED(NRT_LOC_SHIFT);
+        default: NRT_FUSED(NRT_LOC_LINSPACE);
     }
 #undef NRT_FUSED
-    return NRT_OK;
 }
 
-// launch_fused for the padded lane groups (warp_dice_tile_pad): Gr = L / 4 < G live lanes per voxel, the same schedules
-template <int G, typename ST>
-int launch_fused_pad(const InterpArgs &a, const TileGeom &tg, unsigned nblocks, int batch, int mode, bool store, int Gr,
-                     const void *fixed, float *fpart, float *mpart, hipStream_t st) {
-    dim3 grid(nblocks, batch), blk(256);
-    const unsigned dyn = tg.x_march ? 75u * 1024u : 0u;
-    if (tg.x_march) {
-        grid = dim3(fused_xmarch_grid(tg, nblocks, batch), 1);
-#define NRT_FUSED_PAD_X(MODE)                                                                                        \
-    if (store) hipLaunchKernelGGL((warp_dice_tile_pad<G, MODE, true, FUSED_MINW, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart, Gr); \
-    else {                                                                                                           \
-        if (hipFuncSetAttribute((const void *)warp_dice_tile_pad<G, MODE, false, FUSED_MINW, ST>,                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return NRT_ERR_LAUNCH; \
-        hipLaunchKernelGGL((warp_dice_tile_pad<G, MODE, false, FUSED_MINW, ST>), grid, blk, dyn, st, a, tg, fixed, fpart, mpart, Gr); \
+// Gr == G: the 4 * 2^k entry point, else the padded one.  G = 1 has no padded form (Gr == G there)
+template <int G, typename ST, typename... A>
+int launch_fused_any(int Gr, const A &...args) {
+    if constexpr (G > 1) {
+        if (Gr != G) return launch_fused<G, ST, true>(args...);
     }
-        switch (mode) {
-            case NRT_LOC_ABSOLUTE: NRT_FUSED_PAD_X(NRT_LOC_ABSOLUTE); break;
-            case NRT_LOC_SHIFT: NRT_FUSED_PAD_X(NRT_LOC_SHIFT); break;
-            default: NRT_FUSED_PAD_X(NRT_LOC_LINSPACE); break;
-        }
-#undef NRT_FUSED_PAD_X
-        return NRT_OK;
-    }
-#define NRT_FUSED_PAD(MODE)                                                                                        \
-    if (store) hipLaunchKernelGGL((warp_dice_tile_pad<G, MODE, true, 1, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart, Gr); \
-    else hipLaunchKernelGGL((warp_dice_tile_pad<G, MODE, false, 1, ST>), grid, blk, 0, st, a, tg, fixed, fpart, mpart, Gr);
-    switch (mode) {
-        case NRT_LOC_ABSOLUTE: NRT_FUSED_PAD(NRT_LOC_ABSOLUTE); break;
-        case NRT_LOC_SHIFT: NRT_FUSED_PAD(NRT_LOC_SHIFT); break;
-        default: NRT_FUSED_PAD(NRT_LOC_LINSPACE); break;
-    }
-#undef NRT_FUSED_PAD
-    return NRT_OK;
+    return launch_fused<G, ST, false>(args...);
 }
 
-// lanes per voxel of the fused kernels: the next power of two >= L / 4 for L = 4, 8, ..., 256 (L / 4 < G: warp_dice_tile_pad), else 0
-inline int fused_group(int nlabels) {
-    if (nlabels < 4 || nlabels > 256 || nlabels % 4) return 0;
-    int g = 1;
-    while (g < nlabels / 4) g <<= 1;
-    return g;
+// What the fused kernels can address: row bytes of `moving` (elem bytes per value) and of `fixed` / `warped` / `loc` as 32-bit
+// offsets, row indices formed by 24-bit multiplies.  One rule for the launch and for nrt_warp_dice_kernel_name
+inline bool fused_fits(const int *vol_shape, const int *out_shape, int nlabels, size_t elem) {
+    if ((long long)vol_shape[0] * vol_shape[1] >= (1 << 24) || vol_shape[2] >= (1 << 24) ||
+        (long long)out_shape[0] * out_shape[1] >= (1 << 24) || out_shape[2] >= (1 << 24)) return false;
+    unsigned long long nvol = 1, nout = 1;
+    for (int d = 0; d < 3; ++d) { nvol *= (unsigned long long)vol_shape[d]; nout *= (unsigned long long)out_shape[d]; }
+    return nvol * nlabels * elem < (1ull << 32) && nout * nlabels * 4ull < (1ull << 32);
 }
 
 }  // namespace
@@ -671,12 +474,8 @@ int warp_dice_soft_impl(const void *moving, const float *loc, const void *fixed,
     if (rc != NRT_OK) return rc;
     if (!warped) a.out = nullptr;
     a.fill_f = fill_value;
-    if ((unsigned long long)vol_bs * sizeof(ST) >= (1ull << 32)) return NRT_ERR_UNSUPPORTED;
-    // the kernel addresses `fixed` / `warped` / `loc` rows with 32-bit byte offsets and forms row indices with 24-bit multiplies
-    if ((unsigned long long)a.nout * (unsigned long long)nlabels * 4ull >= (1ull << 32)) return NRT_ERR_UNSUPPORTED;
+    if (!fused_fits(vol_shape, out_shape, nlabels, sizeof(ST))) return NRT_ERR_UNSUPPORTED;
     if (!std::is_same<ST, float>::value && warped) return NRT_ERR_UNSUPPORTED;      // the warped volume is a float32 output
-    if ((long long)vol_shape[0] * vol_shape[1] >= (1 << 24) || vol_shape[2] >= (1 << 24) ||
-        (long long)out_shape[0] * out_shape[1] >= (1 << 24) || out_shape[2] >= (1 << 24)) return NRT_ERR_UNSUPPORTED;
     if ((((uintptr_t)moving | (uintptr_t)fixed | (uintptr_t)warped) & 15) != 0) return NRT_ERR_INVALID_ARG;
     if (a.nout == 0) return NRT_ERR_INVALID_ARG;
     TileGeom tg;
@@ -697,24 +496,18 @@ int warp_dice_soft_impl(const void *moving, const float *loc, const void *fixed,
     w.ipart = nullptr;
     hipStream_t st = nrt_stream(stream);
     const bool store = warped != nullptr;
-    if (Gr != G) {
-        switch (G) {
-            case 2: rc = launch_fused_pad<2, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-            case 4: rc = launch_fused_pad<4, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-            case 8: rc = launch_fused_pad<8, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-            case 16: rc = launch_fused_pad<16, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-            case 32: rc = launch_fused_pad<32, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-            default: rc = launch_fused_pad<64, ST>(a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st); break;
-        }
-    } else switch (G) {
-        case 1: rc = launch_fused<1, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        case 2: rc = launch_fused<2, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        case 4: rc = launch_fused<4, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        case 8: rc = launch_fused<8, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        case 16: rc = launch_fused<16, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        case 32: rc = launch_fused<32, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
-        default: rc = launch_fused<64, ST>(a, tg, nblocks, batch, loc_mode, store, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr); break;
+#define NRT_FUSED_G(GG) \
+    rc = launch_fused_any<GG, ST>(Gr, a, tg, nblocks, batch, loc_mode, store, Gr, fixed, w.fpart, w.mpart, st, allow_wc, minmax != nullptr)
+    switch (G) {
+        case 1: NRT_FUSED_G(1); break;
+        case 2: NRT_FUSED_G(2); break;
+        case 4: NRT_FUSED_G(4); break;
+        case 8: NRT_FUSED_G(8); break;
+        case 16: NRT_FUSED_G(16); break;
+        case 32: NRT_FUSED_G(32); break;
+        default: NRT_FUSED_G(64); break;
     }
+#undef NRT_FUSED_G
     if (rc != NRT_OK) return rc;              // nothing (or not everything) was launched: do not reduce stale partial sums
     NRT_CHECK_LAUNCH();
     return dice_finalize_soft(w, nblocks, 1, batch, nlabels, laplace_smoothing, sums, dice, minmax, st);
@@ -732,14 +525,9 @@ extern "C" const char *nrt_warp_dice_kernel_name(const int *out_shape, const int
     if (!out_shape || !vol_shape || nlabels < 4 || nlabels % 4 || batch < 1 || loc_mode < 0 || loc_mode > 2) return name;
     const int G = fused_group(nlabels);
     if (!G) return name;
-    unsigned long long nout = 1, nvol = 1;
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < 3; ++d)
         if (out_shape[d] < 1 || vol_shape[d] < 1) return name;
-        nout *= (unsigned long long)out_shape[d]; nvol *= (unsigned long long)vol_shape[d];
-    }
-    if (nvol * nlabels * 4ull >= (1ull << 32) || nout * nlabels * 4ull >= (1ull << 32)) return name;
-    if ((long long)vol_shape[0] * vol_shape[1] >= (1 << 24) || vol_shape[2] >= (1 << 24) ||
-        (long long)out_shape[0] * out_shape[1] >= (1 << 24) || out_shape[2] >= (1 << 24)) return name;
+    if (!fused_fits(vol_shape, out_shape, nlabels, sizeof(float))) return name;
     const bool allow_wc = !(tune > 0 && (tune & FUSED_TUNE_NO_WC));
     if (tune > 0) tune &= ~(FUSED_TUNE_NO_WC | FUSED_TUNE_WC);
     TileGeom tg;

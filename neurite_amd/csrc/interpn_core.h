@@ -327,6 +327,15 @@ inline bool xmarch_applies(const int *out_shape, int batch) {
     return out_shape[0] >= 16 && cols * (unsigned)batch >= 512;
 }
 
+// lanes per voxel of the fused warp + Dice kernels and their backward: the next power of two >= L / 4 for L = 4, 8, ..., 256
+// (L / 4 < G: the padded entry points warp_dice_tile_pad / warp_dice_bwd_rows_pad), else 0
+inline int fused_group(int nlabels) {
+    if (nlabels < 4 || nlabels > 256 || nlabels % 4) return 0;
+    int g = 1;
+    while (g < nlabels / 4) g <<= 1;
+    return g;
+}
+
 // device: which (batch, patch, x segment) does this block own?  false = nothing (padding block)
 __device__ __forceinline__ bool xmarch_block(const TileGeom &tg, int O0, int &b, unsigned &prow, int &x0, int &y0, int &z0, int &xlen) {
     const unsigned k = blockIdx.x % NRT_NXCD, jb = blockIdx.x / NRT_NXCD;

@@ -1,6 +1,7 @@
 """
-The fused warp + Dice entry points for label counts that are multiples of 4 but not 4 * 2^k (csrc/fused.hip, warp_dice_tile_pad):
-which kernel the library names, and that every other count keeps its old answer.  Geometry only, no device needed.
+The fused warp + Dice entry points for label counts that are multiples of 4 but not 4 * 2^k (csrc/fused.hip: warp_dice_tile_pad,
+the padded entry point of the kernel body it shares with warp_dice_tile): which kernel the library names, and that every other
+count keeps its old answer.  Geometry only, no device needed.
 """
 
 import neurite_amd as ne

@@ -1,6 +1,7 @@
 """
-Fused warp + Dice (csrc/fused.hip, warp_dice_tile_pad) and its backward wrt the field (csrc/backward.hip, warp_dice_bwd_rows_pad) for
-label counts that are multiples of 4 but not 4 * 2^k: lane groups of the next power of two, the lanes past L / 4 idle.
+Fused warp + Dice (csrc/fused.hip, entry point warp_dice_tile_pad) and its backward wrt the field (csrc/backward.hip, entry point
+warp_dice_bwd_rows_pad) for label counts that are multiples of 4 but not 4 * 2^k: lane groups of the next power of two, the lanes
+past L / 4 idle.  Each is the PAD = true instance of the one kernel body it shares with the 4 * 2^k entry point.
 Tolerances as tests/test_gpu_dice_cce.py (warped bit-identical, sums / dice 1e-6 against the unfused HIP pipeline) and
 tests/test_gpu_backward.py (gradients 1e-4 of their scale against the float64 oracle).
 """
