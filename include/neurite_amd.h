@@ -678,6 +678,55 @@ int nrt_synth_noise_add_f32(const float *x, const float *noise, const float *sd,
 int nrt_synth_bg_clear_f32(const float *image, const float *labels, const float *flag, float *y, int batch, long long nvox,
                            int channels, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Local and stream layers (neurite/tf/layers.py:746-808, 1535-1607, 1711-1844, 1915-2073): one parameter, or one small matrix, per
+ * voxel, and the running mean / covariance of a stream of batches.  float32, any spatial rank: the tensors are the flat views
+ * [batch, n] (n = every axis but the batch) or [batch, nvox, channels].  Every product and sum is rounded on its own (no fma), a
+ * parameter is read once for all batch entries, and every parameter gradient is written once by the thread that owns the element,
+ * summing b = 0 .. batch-1 in that order: no atomics, run-to-run bit-identical.  16-byte accesses where n (cout, v) is a multiple
+ * of 4 and the pointers are 16-byte aligned, 4-byte ones otherwise.  NRT_ERR_INVALID_ARG: a NULL tensor that is not optional,
+ * batch < 1, n / nvox / v < 1.  NRT_ERR_UNSUPPORTED: element counts beyond 2^62 or a grid beyond the launch limits.
+ *
+ *   nrt_local_affine_f32      params mult, bias [n].  x given:  y[b, i] = x[b, i] * mult[i] + bias[i] * bias_scale   (LocalLinear;
+ *                             mult NULL: y = x + bias * bias_scale, LocalBias with bias = kernel, bias_scale = biasmult).
+ *                             x NULL (mult must be NULL too):  y[b, i] = e[b] * (bias[i] * bias_scale), where e[b] = 1 if probe is
+ *                             NULL (LocalParamLayer, batch 1) and e[b] = probe[b * probe_stride] * 0 + 1 otherwise
+ *                             (LocalParamWithInput, :1837-1841: probe = the first element of input entry b; NaN / Inf there turns
+ *                             entry b into NaN).  x and probe together: NRT_ERR_INVALID_ARG.
+ *   nrt_local_affine_bwd_f32  gx[b, i] = g[b, i] * mult[i] (needs mult);  gmult[i] = sum_b g[b, i] * x[b, i] (needs x);
+ *                             gbias[i] = bias_scale * sum_b e[b] * g[b, i] (e as above, 1 without a probe).  Each output is optional.
+ *   nrt_local_cross_linear_f32      x [batch, nvox, cin], w [nvox, cin, cout], bias [nvox, cout] or NULL:
+ *                             y[b, v, o] = sum_c x[b, v, c] * w[v, c, o] (+ bias[v, o]), c ascending.  1 <= cin, cout <= 64, else
+ *                             NRT_ERR_UNSUPPORTED.  w[v] is read once per 8 batch entries.
+ *   nrt_local_cross_linear_bwd_f32  gx[b, v, c] = sum_o g[b, v, o] * w[v, c, o];  gw[v, c, o] = sum_b x[b, v, c] * g[b, v, o];
+ *                             gbias[v, o] = sum_b g[b, v, o].  Each output is optional (gx needs w, gw needs x).
+ *   nrt_stream_mean_f32       mean [n] and count [1] are device state.  training != 0 (_mean_update, :2059-2073): new_count =
+ *                             count + batch, alpha = batch / min(new_count, cap), mean <- mean * (1 - alpha) + (sum_b x[b] / batch)
+ *                             * alpha, count <- new_count, y[b] = min(1, new_count / cap) * mean, and coef[0] (optional) = min(1,
+ *                             new_count / cap) * alpha / batch.  training == 0: y[b] = min(1, count / cap) * mean, nothing else is
+ *                             written (x may be NULL).  count never travels to the host: the voxel kernel reads the old value and a
+ *                             one-thread kernel that follows it in stream order writes the new one; capturable into a hipGraph.
+ *   nrt_stream_mean_bwd_f32   gx[b, i] = coef[0] * sum_b' g[b', i]  (the assigned variables are not differentiated through)
+ *   nrt_stream_cov_f32        x [batch, v], cov [v, v], mean [v], count [1] (:2014-2052): prev_cap = min(count, cap), cov <- (cov *
+ *                             (prev_cap - 1) + sum_b x[b] x[b]^T) / (prev_cap + batch - 1) by IEEE division (a first call with
+ *                             batch 1 divides by zero, as the reference does), mean and count as above, y[b] = min(1, new_count /
+ *                             cap) * cov.  training == 0: y[b] = min(1, count / cap) * cov.  cov is read and written once, in 16-row
+ *                             tiles with the rows of x for the tile in LDS.
+ * ------------------------------------------------------------------------------------------ */
+int nrt_local_affine_f32(const float *x, const float *probe, long long probe_stride, const float *mult, const float *bias,
+                         float bias_scale, float *y, int batch, long long n, void *stream);
+int nrt_local_affine_bwd_f32(const float *g, const float *x, const float *probe, long long probe_stride, const float *mult,
+                             float bias_scale, float *gx, float *gmult, float *gbias, int batch, long long n, void *stream);
+int nrt_local_cross_linear_f32(const float *x, const float *w, const float *bias, float *y, int batch, long long nvox, int cin,
+                               int cout, void *stream);
+int nrt_local_cross_linear_bwd_f32(const float *g, const float *x, const float *w, float *gx, float *gw, float *gbias, int batch,
+                                   long long nvox, int cin, int cout, void *stream);
+int nrt_stream_mean_f32(const float *x, float *mean, float *count, float cap, float *y, float *coef, int batch, long long n,
+                        int training, void *stream);
+int nrt_stream_mean_bwd_f32(const float *g, const float *coef, float *gx, int batch, long long n, void *stream);
+int nrt_stream_cov_f32(const float *x, float *mean, float *cov, float *count, float cap, float *y, int batch, int v, int training,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,13 @@ _SIGNATURES = {
     'nrt_dice_soft_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _f, _vp, _vp, _vp]),
     'nrt_warp_dice_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i, _i, _ll, _i, _i, _f, _vp]),
     'nrt_wcce_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _f, _f, _vp, _vp]),
+    'nrt_local_affine_f32': (_i, [_vp, _vp, _ll, _vp, _vp, _f, _vp, _i, _ll, _vp]),
+    'nrt_local_affine_bwd_f32': (_i, [_vp, _vp, _vp, _ll, _vp, _f, _vp, _vp, _vp, _i, _ll, _vp]),
+    'nrt_local_cross_linear_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp]),
+    'nrt_local_cross_linear_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp]),
+    'nrt_stream_mean_f32': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _ll, _i, _vp]),
+    'nrt_stream_mean_bwd_f32': (_i, [_vp, _vp, _vp, _i, _ll, _vp]),
+    'nrt_stream_cov_f32': (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
 }
 
 

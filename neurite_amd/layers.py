@@ -5,6 +5,15 @@ Resize / Zoom           neurite/tf/layers.py:91-185
 SpatialTransformer      voxelmorph.layers.SpatialTransformer as the reference calls it
                         (neurite/tf/models.py:806-807 and 1157-1159; not vendored in the reference)
 HyperConv* / HyperDense* neurite/tf/layers.py:2515-3033 (kernel and bias are inputs, one set per batch entry)
+LocalBias, LocalLinear  neurite/tf/layers.py:746-808   (one bias / one linear map per voxel and feature)
+LocalCrossLinear        :1535-1607                     (one Cin x Cout matrix per voxel; up to 64 features each way)
+LocalParamLayer         :1711-1789                     (a learnable tensor without inputs; takes device= or .to())
+LocalParamWithInput     :1792-1844                     (the same tensor once per batch entry of an otherwise ignored input)
+MeanStream, CovStream   :1915-2073                     (running mean / covariance; `count` never leaves the device)
+
+The local and stream layers are float32 only (NotImplementedError otherwise, raised before any device is touched), know the
+initializers 'RandomNormal', 'glorot_uniform' and 'zeros', refuse regularizers, and CovStream has no gradient.  The free function
+LocalParam (:1847) is not provided: a bare tensor cannot own a registered parameter in torch -- use LocalParamLayer.
 
 Same constructor arguments, defaults, lazy build on first call, get_config() keys and error
 behaviour as the Keras layers.  Tensors are channels-last [B, *spatial, C] on a ROCm device.
@@ -24,7 +33,8 @@ from . import utils
 __all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LocallyConnected3D', 'VecInt', 'RescaleTransform',
            'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise',
            'HyperConv', 'HyperConv2D', 'HyperConv3D', 'HyperConvFromDense', 'HyperConv2DFromDense', 'HyperConv3DFromDense',
-           'HyperDense', 'HyperDenseFromDense']
+           'HyperDense', 'HyperDenseFromDense', 'LocalBias', 'LocalLinear', 'LocalCrossLinear', 'LocalParamLayer',
+           'LocalParamWithInput', 'MeanStream', 'CovStream']
 
 
 class _Layer(nn.Module):
@@ -1457,3 +1467,498 @@ class HyperDenseFromDense(_FromDenseMixin, HyperDense):
     def get_config(self):
         base_config = super().get_config()
         return dict(list(base_config.items()) + list(self._from_dense_config().items()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# "Local" layers (a parameter, or a small matrix, at each voxel: neurite/tf/layers.py:746-808, 1535-1607, 1711-1844) and the stream
+# layers (:1915-2073) on csrc/local.hip.  Any spatial rank: the kernels see the flat views [B, n] / [B, V, C], a parameter is read
+# once for all batch entries and its gradient summed over the batch by the thread that owns it (no atomics, bit-reproducible).
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _require_f32_local(what, *tensors):
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise NotImplementedError('%s: the local / stream kernels are float32, got a %s tensor (non-float32 tensors are not '
+                                      'implemented)' % (what, t.dtype))
+
+
+def _keras_fans(shape):
+    """keras initializers _compute_fans"""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1:
+        return 1, 1
+    if len(shape) == 1:
+        return shape[0], shape[0]
+    if len(shape) == 2:
+        return shape
+    rf = int(np.prod(shape[:-2]))
+    return shape[-2] * rf, shape[-1] * rf
+
+
+def _check_initializer(what, initializer):
+    if initializer not in ('RandomNormal', 'glorot_uniform', 'zeros'):
+        raise NotImplementedError("%s: initializer %r is not implemented ('RandomNormal', 'glorot_uniform' and 'zeros' are)"
+                                  % (what, initializer))
+
+
+def _local_init(what, initializer, shape, device, normal=(0.0, 0.05)):
+    """A float32 weight drawn the way Keras draws it: 'RandomNormal' is its default (mean 0, stddev 0.05); `normal` = (mean, stddev)
+    replaces it where the reference passes an initializer object of its own (LocalCrossLinear, :1567-1582)."""
+    shape = tuple(int(s) for s in shape)
+    if initializer is None:
+        return torch.empty(shape, dtype=torch.float32, device=device).normal_(normal[0], normal[1])
+    _check_initializer(what, initializer)
+    if initializer == 'RandomNormal':
+        return torch.empty(shape, dtype=torch.float32, device=device).normal_(0.0, 0.05)
+    if initializer == 'zeros':
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+    fan_in, fan_out = _keras_fans(shape)
+    limit = (6.0 / max(1, fan_in + fan_out)) ** 0.5
+    return torch.empty(shape, dtype=torch.float32, device=device).uniform_(-limit, limit)
+
+
+def _local_affine_launch(x, probe, mult, bias, bias_scale, B, n, dev):
+    """nrt_local_affine_f32 on contiguous float32 tensors; probe: the tensor whose entries' first elements give the factors e[b]"""
+    lib = _lib.lib()
+    y = torch.empty((B, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.nrt_local_affine_f32(_lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0), _lib.ptr(mult),
+                                      _lib.ptr(bias), float(bias_scale), _lib.ptr(y), B, n, _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_local_affine_f32')
+    return y
+
+
+def _local_affine_bwd_launch(g, x, probe, mult, bias_scale, need_x, need_mult, need_bias, B, n, dev):
+    lib = _lib.lib()
+    gx = torch.empty((B, n), dtype=torch.float32, device=dev) if need_x else None
+    gm = torch.empty(n, dtype=torch.float32, device=dev) if need_mult else None
+    gb = torch.empty(n, dtype=torch.float32, device=dev) if need_bias else None
+    with torch.cuda.device(dev):
+        rc = lib.nrt_local_affine_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0),
+                                          _lib.ptr(mult), float(bias_scale), _lib.ptr(gx), _lib.ptr(gm), _lib.ptr(gb), B, n,
+                                          _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_local_affine_bwd_f32')
+    return gx, gm, gb
+
+
+class _LocalAffineFn(torch.autograd.Function):
+    """y = x * mult + bias * bias_scale (mult may be None), parameters of the shape of one batch entry."""
+
+    @staticmethod
+    def forward(ctx, x, mult, bias, bias_scale):
+        B, n = x.shape[0], bias.numel()
+        ctx.save_for_backward(x, mult)
+        ctx.bias_scale = bias_scale
+        return _local_affine_launch(x, None, mult, bias, bias_scale, B, n, x.device).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mult = ctx.saved_tensors
+        need_x, need_m, need_b = ctx.needs_input_grad[:3]
+        need_m = need_m and mult is not None
+        g = g.contiguous()
+        if mult is None and not need_b:
+            return (g if need_x else None), None, None, None
+        B, n = x.shape[0], x[0].numel()
+        gx, gm, gb = _local_affine_bwd_launch(g, x, None, mult, ctx.bias_scale, need_x and mult is not None, need_m, need_b, B, n,
+                                              g.device)
+        if need_x:
+            gx = g if mult is None else gx.view(x.shape)
+        return gx, (gm.view(mult.shape) if need_m else None), (gb.view(x.shape[1:]) if need_b else None), None
+
+
+class _LocalParamFn(torch.autograd.Function):
+    """y[b] = e[b] * (kernel * mult), e[b] = probe[b, 0, ...] * 0 + 1 (1 without a probe); no gradient for the probe."""
+
+    @staticmethod
+    def forward(ctx, kernel, probe, mult, B):
+        ctx.save_for_backward(probe)
+        ctx.cfg = (mult, B)
+        return _local_affine_launch(None, probe, None, kernel, mult, B, kernel.numel(), kernel.device).view((B,) + tuple(kernel.shape))
+
+    @staticmethod
+    def backward(ctx, g):
+        probe, = ctx.saved_tensors
+        mult, B = ctx.cfg
+        g = g.contiguous()
+        _, _, gk = _local_affine_bwd_launch(g, None, probe, None, mult, False, False, True, B, g[0].numel(), g.device)
+        return gk.view(g.shape[1:]), None, None, None
+
+
+def _local_affine(what, x, mult, bias, bias_scale):
+    _require_f32_local(what, x, mult, bias)
+    _lib.require_device(x, mult, bias)
+    if tuple(x.shape[1:]) != tuple(bias.shape):
+        raise ValueError('%s: input of shape %s, the layer was built for %s' % (what, tuple(x.shape[1:]), tuple(bias.shape)))
+    if x.shape[0] < 1 or bias.numel() < 1:
+        raise ValueError('%s: empty input of shape %s' % (what, tuple(x.shape)))
+    x = x.contiguous()
+    if torch.is_grad_enabled() and (x.requires_grad or bias.requires_grad or (mult is not None and mult.requires_grad)):
+        return _LocalAffineFn.apply(x, mult, bias, bias_scale)
+    return _LocalAffineFn.forward(_NoCtx(), x.detach(), None if mult is None else mult.detach(), bias.detach(), bias_scale)
+
+
+class _LocalLayer(_Layer):
+    """float32 is checked before the layer builds its weights (and before any device is touched)"""
+
+    def forward(self, inputs, **kwargs):
+        _require_f32_local(self.__class__.__name__, *(inputs if isinstance(inputs, (list, tuple)) else [inputs]))
+        return super().forward(inputs, **kwargs)
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+
+class LocalBias(_LocalLayer):
+    """
+    One bias per voxel and feature (neurite/tf/layers.py:746-774): `kernel` has the shape of one batch entry and
+    call(x) = x + kernel * biasmult.  One kernel launch (nrt_local_affine_f32); the result equals the float32 evaluation of that
+    expression bit for bit.  float32 only (NotImplementedError otherwise).
+    """
+
+    def __init__(self, my_initializer='RandomNormal', biasmult=1.0, **kwargs):
+        self.initializer = my_initializer
+        self.biasmult = biasmult
+        super().__init__(**kwargs)
+        self.kernel = None
+
+    def build(self, input_shape):
+        self.kernel = nn.Parameter(_local_init('LocalBias', self.initializer, input_shape[1:], getattr(self, '_build_device', None)))
+        self.built = True
+
+    def call(self, x):
+        return _local_affine('LocalBias', x, None, self.kernel, self.biasmult)
+
+
+class LocalLinear(_LocalLayer):
+    """
+    One linear map per voxel and feature (neurite/tf/layers.py:777-808): `mult` and `bias` have the shape of one batch entry and
+    call(x) = x * mult + bias, product and sum rounded separately as the reference's two ops are.  float32 only.
+    """
+
+    def __init__(self, initializer='RandomNormal', **kwargs):
+        self.initializer = initializer
+        super().__init__(**kwargs)
+        self.mult = None
+        self.bias = None
+
+    def build(self, input_shape):
+        dev = getattr(self, '_build_device', None)
+        self.mult = nn.Parameter(_local_init('LocalLinear', self.initializer, input_shape[1:], dev))
+        self.bias = nn.Parameter(_local_init('LocalLinear', self.initializer, input_shape[1:], dev))
+        self.built = True
+
+    def call(self, x):
+        return _local_affine('LocalLinear', x, self.mult, self.bias, 1.0)
+
+
+class _CrossLinearFn(torch.autograd.Function):
+    """y[b, v, :] = x[b, v, :] @ W[v] (+ bias[v]) and its three gradients (csrc/local.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        lib = _lib.lib()
+        dev = x.device
+        cin, cout = w.shape[-2], w.shape[-1]
+        B, V = x.shape[0], x[0].numel() // cin
+        y = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nrt_local_cross_linear_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, V, cin, cout,
+                                                _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_local_cross_linear_f32')
+        ctx.save_for_backward(x, w)
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        lib = _lib.lib()
+        dev = g.device
+        g = g.contiguous()
+        cin, cout = w.shape[-2], w.shape[-1]
+        B, V = x.shape[0], x[0].numel() // cin
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.bias_shape is not None
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(w) if need_w else None
+        gb = torch.empty(ctx.bias_shape, dtype=torch.float32, device=dev) if need_b else None
+        with torch.cuda.device(dev):
+            rc = lib.nrt_local_cross_linear_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(w), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), B, V,
+                                                    cin, cout, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_local_cross_linear_bwd_f32')
+        return gx, gw, gb
+
+
+class LocalCrossLinear(_LocalLayer):
+    """
+    A different linear map between the features at every voxel (neurite/tf/layers.py:1535-1607): x [B, *space, Cin] ->
+    [B, *space, output_features], y[b, v] = x[b, v] @ mult[0, v] (+ bias[0, v]); mult [1, *space, Cin, output_features], bias
+    [1, *space, output_features], both drawn from N(1 / Cin, 0.01) unless an initializer is named.  The batch loop the reference maps
+    with tf.map_fn runs inside the kernel, so a voxel's matrix is read once.  Limits (NotImplementedError): tensors that are not
+    float32, more than 64 input or output features, a regularizer (there is no Keras loss collection here; the arguments are kept
+    for introspection).
+    """
+
+    def __init__(self, output_features, mult_initializer=None, bias_initializer=None, mult_regularizer=None, bias_regularizer=None,
+                 use_bias=True, **kwargs):
+        self.output_features = output_features
+        self.mult_initializer = mult_initializer
+        self.bias_initializer = bias_initializer
+        self.mult_regularizer = mult_regularizer
+        self.bias_regularizer = bias_regularizer
+        self.use_bias = use_bias
+        if mult_regularizer is not None or bias_regularizer is not None:
+            raise NotImplementedError('LocalCrossLinear: regularizers are not implemented (no Keras loss collection)')
+        super().__init__(**kwargs)
+        self.mult = None
+        self.bias = None
+
+    def build(self, input_shape):
+        dev = getattr(self, '_build_device', None)
+        cin = int(input_shape[-1])
+        normal = (1.0 / cin, 0.01)                                                        # :1567-1570, 1579-1582
+        if cin > 64 or int(self.output_features) > 64:
+            raise NotImplementedError('LocalCrossLinear: up to 64 input and output features, got %d -> %d'
+                                      % (cin, self.output_features))
+        mult_shape = [1] + list(input_shape)[1:] + [self.output_features]
+        self.mult = nn.Parameter(_local_init('LocalCrossLinear', self.mult_initializer, mult_shape, dev, normal))
+        if self.use_bias:
+            bias_shape = [1] + list(input_shape)[1:-1] + [self.output_features]
+            self.bias = nn.Parameter(_local_init('LocalCrossLinear', self.bias_initializer, bias_shape, dev, normal))
+        self.built = True
+
+    def compute_output_shape(self, input_shape):
+        return tuple(list(input_shape)[:-1] + [self.output_features])
+
+    def call(self, x):
+        _require_f32_local('LocalCrossLinear', x, self.mult, self.bias)
+        _lib.require_device(x, self.mult, self.bias)
+        if tuple(x.shape[1:]) != tuple(self.mult.shape[1:-1]) or x.dim() < 2:
+            raise ValueError('LocalCrossLinear: input of shape %s, the layer was built for %s'
+                             % (tuple(x.shape[1:]), tuple(self.mult.shape[1:-1])))
+        if x.numel() < 1:
+            raise ValueError('LocalCrossLinear: empty input of shape %s' % (tuple(x.shape),))
+        x = x.contiguous()
+        if torch.is_grad_enabled() and (x.requires_grad or self.mult.requires_grad
+                                        or (self.bias is not None and self.bias.requires_grad)):
+            return _CrossLinearFn.apply(x, self.mult, self.bias)
+        return _CrossLinearFn.forward(_NoCtx(), x.detach(), self.mult.detach(), None if self.bias is None else self.bias.detach())
+
+
+_local_param_uid = [0]
+
+
+class LocalParamLayer(_Layer):
+    """
+    A learnable tensor as a layer without inputs (neurite/tf/layers.py:1711-1789; in Keras a source layer): the parameter `kernel`
+    of shape `shape` is created at construction and forward() returns kernel[None] * mult, shape [1, *shape].  There is no input to
+    build on, so the device comes from a `device=` keyword or from .to().  float32 only.
+    """
+
+    def __init__(self, shape, my_initializer='RandomNormal', dtype=None, name=None, mult=1.0, **kwargs):
+        device = kwargs.pop('device', None)
+        if not name:
+            _local_param_uid[0] += 1
+            name = 'local_param_%d' % _local_param_uid[0]
+        if dtype not in (None, 'float32', torch.float32, np.float32):
+            raise NotImplementedError('LocalParamLayer: float32 only, got dtype %r' % (dtype,))
+        super().__init__(name=name, **kwargs)
+        self.shape = [1, *shape]
+        self.my_initializer = my_initializer
+        self.mult = mult
+        self.kernel = nn.Parameter(_local_init('LocalParamLayer', my_initializer, shape, device))
+        self.trainable = True
+        self.built = True
+
+    def get_config(self):
+        return {'dtype': 'float32', 'sparse': False, 'name': self.name}
+
+    def compute_output_shape(self, input_shape=None):
+        return tuple(self.shape)
+
+    def forward(self, inputs=None):
+        _require_f32_local('LocalParamLayer', self.kernel)
+        _lib.require_device(self.kernel)
+        if torch.is_grad_enabled() and self.kernel.requires_grad:
+            return _LocalParamFn.apply(self.kernel, None, self.mult, 1)
+        return _LocalParamFn.forward(_NoCtx(), self.kernel.detach(), None, self.mult, 1)
+
+    call = forward
+
+
+class LocalParamWithInput(_LocalLayer):
+    """
+    The learnable tensor of LocalParamLayer, repeated for every batch entry of an input that is otherwise ignored
+    (neurite/tf/layers.py:1792-1844; the learnable atlas of the conditional-template models): output [B, *shape], entry b =
+    e[b] * (kernel * mult) with e[b] = x.flatten(1)[b, 0] * 0 + 1 as at :1837-1841 -- so a NaN or Inf in that one element makes
+    entry b NaN, as in the reference.  x gets no gradient, `kernel` does.  float32 only.
+    """
+
+    def __init__(self, shape, initializer='RandomNormal', mult=1.0, **kwargs):
+        self.shape = shape
+        self.initializer = initializer
+        self.biasmult = mult
+        import warnings
+        warnings.warn('LocalParamWithInput: Consider using LocalParamLayer')
+        super().__init__(**kwargs)
+        self.kernel = None
+
+    def get_config(self):
+        config = super().get_config().copy()
+        config.update({'shape': self.shape})
+        return config
+
+    def build(self, input_shape):
+        self.kernel = nn.Parameter(_local_init('LocalParamWithInput', self.initializer, self.shape, getattr(self, '_build_device', None)))
+        self.built = True
+
+    def compute_output_shape(self, input_shape):
+        return (input_shape[0], *self.shape)
+
+    def call(self, x):
+        _require_f32_local('LocalParamWithInput', x, self.kernel)
+        _lib.require_device(x, self.kernel)
+        if x.dim() < 1 or x.numel() < 1 or self.kernel.numel() < 1:
+            raise ValueError('LocalParamWithInput: empty input of shape %s' % (tuple(x.shape),))
+        probe = x.detach()                      # only element [b, 0, ..., 0] of every entry is read, through the batch stride
+        B = x.shape[0]
+        if torch.is_grad_enabled() and self.kernel.requires_grad:
+            return _LocalParamFn.apply(self.kernel, probe, self.biasmult, B)
+        return _LocalParamFn.forward(_NoCtx(), self.kernel.detach(), probe, self.biasmult, B)
+
+
+def _get_training_value(layer, training):
+    """neurite/tf/layers.py:2076-2096 with the module's mode in the place of the Keras learning phase"""
+    if training is None:
+        training = layer.training
+    if isinstance(training, int):
+        training = bool(training)
+    if layer.trainable is False:
+        training = False
+    return training
+
+
+class _StreamMeanFn(torch.autograd.Function):
+    """MeanStream in training mode: `run` updates the buffers in place and returns (y, coef); d y / d x = coef (the assigned
+    variables are not differentiated through)."""
+
+    @staticmethod
+    def forward(ctx, x, run):
+        y, coef = run(x)
+        ctx.save_for_backward(coef)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        coef, = ctx.saved_tensors
+        lib = _lib.lib()
+        dev = g.device
+        g = g.contiguous()
+        gx = torch.empty_like(g)
+        with torch.cuda.device(dev):
+            rc = lib.nrt_stream_mean_bwd_f32(_lib.ptr(g), _lib.ptr(coef), _lib.ptr(gx), g.shape[0], g[0].numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_stream_mean_bwd_f32')
+        return gx, None
+
+
+class _StreamLayer(_LocalLayer):
+    """what MeanStream and CovStream share: cap, the `trainable` flag (a layer that is not trainable always runs the inference
+    branch), the persistent buffers `mean` and `count` (saved with the model, not parameters)."""
+
+    def __init__(self, cap=100, **kwargs):
+        self.cap = float(cap)
+        trainable = kwargs.get('trainable', True)
+        super().__init__(**kwargs)
+        self.trainable = trainable
+        self.register_buffer('mean', None)
+        self.register_buffer('count', None)
+
+    def _build_stats(self, input_shape):
+        dev = getattr(self, '_build_device', None)
+        self.mean = torch.zeros(tuple(int(s) for s in input_shape[1:]), dtype=torch.float32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def _prepare(self, x):
+        what = self.__class__.__name__
+        _require_f32_local(what, x)
+        dev = _lib.require_device(x, self.mean, self.count)
+        if tuple(x.shape[1:]) != tuple(self.mean.shape):
+            raise ValueError('%s: input of shape %s, the layer was built for %s' % (what, tuple(x.shape[1:]), tuple(self.mean.shape)))
+        if x.numel() < 1:
+            raise ValueError('%s: empty input of shape %s' % (what, tuple(x.shape)))
+        return dev
+
+
+class MeanStream(_StreamLayer):
+    """
+    Running mean of a stream of batches (neurite/tf/layers.py:1915-1975, _mean_update :2059-2073): in training mode `mean` and
+    `count` are updated in place (every new batch weighs at least 1 / cap) and the output is min(1, count / cap) * mean repeated
+    for every batch entry; in inference mode the stored statistics are used and nothing is updated.  call(x, training=None): None
+    is the module's mode (train() / eval()), trainable=False forces the inference branch.  `count` stays on the device (no host
+    round trip; the layer captures into a hipGraph).  Differentiable in x in training mode.  float32 only.
+    """
+
+    def __init__(self, cap=100, **kwargs):
+        super().__init__(cap=cap, **kwargs)
+
+    def build(self, input_shape):
+        self._build_stats(input_shape)
+        self.built = True
+
+    def _run(self, x, training, dev):
+        lib = _lib.lib()
+        B, n = x.shape[0], self.mean.numel()
+        y = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        coef = torch.empty(1, dtype=torch.float32, device=dev) if training else None
+        with torch.cuda.device(dev):
+            rc = lib.nrt_stream_mean_f32(_lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.count), self.cap, _lib.ptr(y), _lib.ptr(coef),
+                                         B, n, int(training), _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_stream_mean_f32')
+        return y, coef
+
+    def call(self, x, training=None):
+        training = _get_training_value(self, training)
+        dev = self._prepare(x)
+        x = x.contiguous()
+        if training and torch.is_grad_enabled() and x.requires_grad:
+            return _StreamMeanFn.apply(x, lambda t: self._run(t.detach(), True, dev))
+        return self._run(x.detach(), bool(training), dev)[0]
+
+
+class CovStream(_StreamLayer):
+    """
+    Running covariance of a stream of batches (neurite/tf/layers.py:1978-2056): x [B, *feat] is flattened to [B, v]; in training mode
+    cov <- (cov * (min(count, cap) - 1) + sum_b x_b x_b^T) / (min(count, cap) + B - 1), `mean` and `count` as in MeanStream, and the
+    output is min(1, count / cap) * cov for every batch entry, [B, v, v]; plain IEEE division, so the first call with B = 1 gives
+    Inf / NaN as the reference does.  Inference mode reads the stored `cov`.  The gradient is not implemented: a training-mode call
+    on an x that requires grad raises NotImplementedError (detach it).  float32 only.
+    """
+
+    def __init__(self, cap=100, **kwargs):
+        super().__init__(cap=cap, **kwargs)
+        self.register_buffer('cov', None)
+
+    def build(self, input_shape):
+        self._build_stats(input_shape)
+        v = int(np.prod(input_shape[1:]))
+        self.cov = torch.zeros((v, v), dtype=torch.float32, device=getattr(self, '_build_device', None))
+        self.built = True
+
+    def compute_output_shape(self, input_shape):
+        v = int(np.prod(input_shape[1:]))
+        return (input_shape[0], v, v)
+
+    def call(self, x, training=None):
+        training = _get_training_value(self, training)
+        if training and torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError('CovStream: the gradient with respect to the input is not implemented; detach the input')
+        dev = self._prepare(x)
+        _lib.require_device(x, self.cov)
+        lib = _lib.lib()
+        x = x.detach().contiguous()
+        B, v = x.shape[0], self.cov.shape[0]
+        y = torch.empty((B, v, v), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nrt_stream_cov_f32(_lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.cov), _lib.ptr(self.count), self.cap, _lib.ptr(y),
+                                        B, v, int(bool(training)), _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_stream_cov_f32')
+        return y
