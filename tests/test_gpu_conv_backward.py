@@ -231,6 +231,51 @@ def test_unet_training_step_gradients(dev, kw, ishape):
     assert net(G(x, dev)).requires_grad is False
 
 
+@pytest.mark.parametrize('ishape', [(16, 16, 32, 1), (8, 8, 32, 1)])
+def test_unet_training_step_at_benchmark_channel_counts(dev, ishape):
+    """the benchmarked model -- unet(16 features, 3 levels, feat_mult 2, 32 labels): layers 1 -> 16, 16 -> 32, 32 -> 64, 96 -> 32,
+    48 -> 16 and a 16 -> 32 likelihood -- on a tiny volume, batch 1: loss and every parameter gradient vs the float64 oracle.  These
+    channel counts take the template instances the benchmark runs (conv3d_c1_wgrad<1>, conv1x1_wgrad16<2>, conv1x1_rows<4,32> for the
+    input gradient of the likelihood, softmax_bwd_vec<8> or the joint loss, the folded decoder backward)."""
+    rng = np.random.default_rng(59)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = ne.models.unet(16, ishape, 3, 3, 32, feat_mult=2).to(dev)
+    assert [tuple(m.kernel.shape[-2:]) for m in net.layers_by_name.values()] == [(1, 16), (16, 32), (32, 64), (96, 32), (48, 16), (16, 32)]
+    for m in net.layers_by_name.values():
+        with torch.no_grad():
+            m.kernel.copy_(G((rng.standard_normal(tuple(m.kernel.shape)) * 0.2).astype(F), dev))
+            m.bias.copy_(G((rng.standard_normal(tuple(m.bias.shape)) * 0.1).astype(F), dev))
+    B, L = 1, 32
+    x = rng.standard_normal((B,) + ishape).astype(F)
+    lab = rng.integers(0, L, (B,) + ishape[:-1])
+    t = np.eye(L, dtype=F)[lab]
+    wl = rng.uniform(0.5, 2, L).astype(F)
+    net.train()
+    y = net(G(x, dev))
+    assert tuple(y.shape) == (B,) + ishape[:-1] + (L,)
+    loss = ne.losses.CategoricalCrossentropy(wl)(G(t, dev), y) - ne.metrics.Dice(check_input_limits=False).mean_dice(G(t, dev), y)
+    loss.backward()
+    params = {k: (m.kernel.detach().cpu().double().requires_grad_(), m.bias.detach().cpu().double().requires_grad_())
+              for k, m in net.layers_by_name.items()}
+    decoders = [op for op in net.ops if op['kind'] == 'conv' and op.get('lo')]
+    assert len(decoders) == 2
+    names = [net.output_name] + [op[k] for op in decoders for k in ('src', 'lo')]
+    ts = tuo.forward(net, torch.from_numpy(x).double(), params, return_tensors=names)
+    for op in decoders:                           # the folded backward is what ran for both decoder layers
+        mod = net.layers_by_name[op['name']]
+        assert mod.fold_backward and M._fold_backward_ok(mod, ts[op['src']], ts[op['lo']], op['up']), op['name']
+    yo = ts[net.output_name]
+    from oracle import grad_oracle as go
+    to = torch.from_numpy(t).double()
+    lo = go.cce_per_voxel(to, yo, torch.from_numpy(wl).double()).mean() - go.soft_dice(to, yo).mean()
+    lo.backward()
+    close(float(loss.detach()), float(lo.detach()), 'loss', 1e-4)
+    for k, m in net.layers_by_name.items():
+        assert m.kernel.grad.shape == m.kernel.shape and m.bias.grad.shape == m.bias.shape
+        close(N(m.kernel.grad), params[k][0].grad.numpy(), k + ' kernel', 5e-4)
+        close(N(m.bias.grad), params[k][1].grad.numpy(), k + ' bias', 5e-4)
+
+
 def test_unet_training_with_feature_dropout(dev):
     """conv_dropout > 0: Keras Dropout with noise_shape [None, 1, 1, 1, C] (models.py:1390-1399) in training mode; gradients vs
     the oracle run with the recorded masks; eval mode ignores it"""

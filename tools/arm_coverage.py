@@ -1,0 +1,87 @@
+"""Which template instances of the U-Net head and glue kernels did a traced run never launch?
+
+    hipcc <build.FLAGS> --cuda-device-only -S neurite_amd/csrc/conv.hip -o conv.s          (the same for conv_bwd.hip)
+    python tools/kernel_digest.py conv.s > conv_kernels.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d out -o arms -- python -m pytest tests/test_gpu_dispatch_arms.py ...
+    python tools/arm_coverage.py --kernels conv_kernels.txt conv_bwd_kernels.txt --stats out/arms_kernel_stats.csv
+
+The kernel tables (tools/kernel_digest.py) list every instance the compiler emitted; the stats file lists every kernel that ran,
+with its number of launches.  Prints one line per instance of the families below that the run never launched -- nothing when
+every arm ran -- and exits 1 if there is one.  --all lists the launched instances with their launch counts too.
+"""
+import argparse
+import csv
+import re
+import sys
+
+# the dispatchers of nrt_conv1x1_softmax_f32, nrt_softmax_lastdim_f32, nrt_softmax_bwd_f32, nrt_conv3d_wgrad2_f32 (its two
+# streaming arms), the single-channel arms of nrt_conv3d_f32 with shared weights and without the folded pooling, and the
+# element-wise / pooling / batch-norm kernels
+FAMILIES = [r'conv1x1_rows<\d+,\d+>', r'conv1x1_vec<\d+,0>', r'conv1x1_softmax<\d+>', r'softmax_lastdim', r'softmax_lastdim_vec<\d+>',
+            r'softmax_bwd', r'softmax_bwd_vec<\d+>', r'conv1x1_wgrad16<\d+>', r'conv3d_c1_wgrad<\d+>', r'conv3d_c1_mfma<\d+,false,false>',
+            r'conv3d_c1_vec<\d+,false>', r'act_bwd', r'act_bwd_tail', r'maxpool_bwd', r'add_act_affine', r'add_act_affine_v4',
+            r'channel_sums', r'channel_axpby']
+FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
+
+
+def norm(name):
+    """`void (anonymous namespace)::f<1, 2>(args)` and `f<1, 2>` -> `f<1,2>`"""
+    name = name.strip().strip('"')
+    if name.endswith('.kd'):
+        name = name[:-3]
+    name = name.replace('(anonymous namespace)::', '')
+    name = re.sub(r'^void\s+', '', name)
+    depth = 0
+    for i, ch in enumerate(name):                 # cut the argument list: the first '(' outside the template brackets
+        if ch == '<':
+            depth += 1
+        elif ch == '>':
+            depth -= 1
+        elif ch == '(' and depth == 0:
+            name = name[:i]
+            break
+    return name.replace(' ', '')
+
+
+def instances(paths):
+    found = set()
+    for p in paths:
+        for ln in open(p):
+            m = re.match(r'(.*?)\s+v\d+\s+s\d+\s+spill\d+', ln)
+            if m and FAMILY.match(norm(m.group(1))):
+                found.add(norm(m.group(1)))
+    return sorted(found)
+
+
+def launches(path):
+    calls = {}
+    with open(path, newline='') as f:
+        for row in csv.DictReader(f):
+            n = norm(row['Name'])
+            calls[n] = calls.get(n, 0) + int(row['Calls'])
+    return calls
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--kernels', nargs='+', required=True, help='tables written by tools/kernel_digest.py')
+    ap.add_argument('--stats', required=True, help='kernel stats CSV of a rocprofv3 --kernel-trace --stats run')
+    ap.add_argument('--all', action='store_true', help='list the launched instances and their launch counts as well')
+    args = ap.parse_args()
+    inst, calls = instances(args.kernels), launches(args.stats)
+    if not inst:
+        raise SystemExit('no instance of the families in %s' % ', '.join(args.kernels))
+    missing = [k for k in inst if not calls.get(k)]
+    if args.all:
+        for k in inst:
+            if calls.get(k):
+                print('%8d launches  %s' % (calls[k], k))
+    for k in missing:
+        print('never launched: %s' % k)
+    if args.all:
+        print('%d instances, %d never launched' % (len(inst), len(missing)))
+    return 1 if missing else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
