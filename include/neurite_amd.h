@@ -727,6 +727,30 @@ int nrt_stream_mean_bwd_f32(const float *g, const float *coef, float *gx, int ba
 int nrt_stream_cov_f32(const float *x, float *mean, float *cov, float *count, float cap, float *y, int batch, int v, int training,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dense layer on one shared weight matrix (the bottleneck of models.ae / single_ae, neurite/tf/models.py:499, 558, 618).  float32;
+ * x [batch, in], w [in, out] row-major (the Keras `Dense` kernel as stored), bias [out] or NULL, y [batch, out].  Memory bound at the
+ * batch sizes these models run at: w is read once per call for up to 16 batch entries (a larger batch runs in chunks of 16).
+ *   nrt_dense_f32       y[b, o] = act(sum_i x[b, i] w[i, o] + bias[o]); act: any element-wise code of csrc/activations.h (0 = none).
+ *                       variant 0 chooses between the reduce arm (blocks own slabs of `in`, partials in the workspace, summed by a
+ *                       second kernel in slab order) and the expand arm (a thread owns adjacent columns and walks `in`); 1 / 2 force
+ *                       the reduce / expand arm, each correct at every shape.
+ *   nrt_dense_bwd_f32   g [batch, out] = the gradient wrt the pre-activation.  gx[b, i] = sum_o g[b, o] w[i, o] (needs w);
+ *                       gw[i, o] = sum_b x[b, i] g[b, o] (needs x); gbias[o] = sum_b g[b, o].  Each output is optional (NULL).
+ *                       variant 0 / 2: gx straight from the row-dot kernel where a block spans a row, through partials otherwise;
+ *                       1: always through partials.
+ *   nrt_dense_workspace_bytes   what both calls need at most under `variant` (0: none); a smaller or missing workspace is
+ *                       NRT_ERR_WORKSPACE.
+ * No atomics: every sum has a fixed order given the shapes, results are run-to-run bit-identical.  Base pointers need 4-byte
+ * alignment only (16-byte loads are used where out % 4 == 0 and the pointers allow).  NRT_ERR_INVALID_ARG: a NULL tensor that is not
+ * optional, batch / in / out < 1, an unknown act or variant.  NRT_ERR_UNSUPPORTED: in * out >= 2^31.  Checked before any launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_dense_workspace_bytes(int batch, int in, int out, int variant);
+int nrt_dense_f32(const float *x, const float *w, const float *bias, float *y, int batch, int in, int out, int act, int variant,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int nrt_dense_bwd_f32(const float *g, const float *x, const float *w, float *gx, float *gw, float *gbias, int batch, int in, int out,
+                      int variant, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,9 @@ _SIGNATURES = {
     'nrt_stream_mean_f32': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _ll, _i, _vp]),
     'nrt_stream_mean_bwd_f32': (_i, [_vp, _vp, _vp, _i, _ll, _vp]),
     'nrt_stream_cov_f32': (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
+    'nrt_dense_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'nrt_dense_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'nrt_dense_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 

@@ -10,6 +10,7 @@ LocalCrossLinear        :1535-1607                     (one Cin x Cout matrix pe
 LocalParamLayer         :1711-1789                     (a learnable tensor without inputs; takes device= or .to())
 LocalParamWithInput     :1792-1844                     (the same tensor once per batch entry of an otherwise ignored input)
 MeanStream, CovStream   :1915-2073                     (running mean / covariance; `count` never leaves the device)
+SampleNormalLogVar      :2261-2302                     (z = mu + exp(log_var / 2) * noise, the sampling step of models.single_ae)
 
 The local and stream layers are float32 only (NotImplementedError otherwise, raised before any device is touched), know the
 initializers 'RandomNormal', 'glorot_uniform' and 'zeros', refuse regularizers, and CovStream has no gradient.  The free function
@@ -34,7 +35,7 @@ __all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LocallyConnected3D', 'VecInt
            'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise',
            'HyperConv', 'HyperConv2D', 'HyperConv3D', 'HyperConvFromDense', 'HyperConv2DFromDense', 'HyperConv3DFromDense',
            'HyperDense', 'HyperDenseFromDense', 'LocalBias', 'LocalLinear', 'LocalCrossLinear', 'LocalParamLayer',
-           'LocalParamWithInput', 'MeanStream', 'CovStream']
+           'LocalParamWithInput', 'MeanStream', 'CovStream', 'SampleNormalLogVar']
 
 
 class _Layer(nn.Module):
@@ -1962,3 +1963,60 @@ class CovStream(_StreamLayer):
                                         B, v, int(bool(training)), _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_stream_cov_f32')
         return y
+
+
+class _SampleNormalFn(torch.autograd.Function):
+    """z = mu + exp(log_var / 2) * noise on nrt_add_act_affine_f32; d z / d mu = 1, d z / d log_var = exp(log_var / 2) * noise / 2"""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, noise):
+        from .models import _ACTS, _elementwise
+        dev = mu.device
+        half = torch.full((1,), 0.5, dtype=torch.float32, device=dev)
+        zero = torch.zeros(1, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            flat = lambda t: t.contiguous().view(-1, 1)                                    # (one "channel": the affine is a scalar)
+            h = _elementwise(flat(log_var), scale=half, shift=zero)                       # log_var / 2, exact
+            p = _elementwise(h, flat(noise), act=_ACTS['exponential'], mul=True)           # exp(.) * noise
+            z = _elementwise(flat(mu), p)
+        ctx.save_for_backward(p, half, zero)
+        return z.view(mu.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .models import _elementwise
+        p, half, zero = ctx.saved_tensors
+        glv = None
+        if ctx.needs_input_grad[1]:
+            glv = _elementwise(g.contiguous().view(-1, 1), p, scale=half, shift=zero, mul=True).view(g.shape)
+        return (g if ctx.needs_input_grad[0] else None), glv, None
+
+
+class SampleNormalLogVar(_Layer):
+    """
+    Gaussian sample given mean and log-variance (neurite/tf/layers.py:2261-2302): call([mu, log_var]) = mu + exp(log_var / 2) * noise
+    with noise ~ N(0, 1) drawn by torch.randn on the device.  float32, differentiable in both inputs.  The arithmetic runs on the
+    existing element-wise kernel (nrt_add_act_affine_f32, three launches: the halving, exp(.) * noise, the sum); no kernel of its own.
+    `_noise=` (a tensor of mu's shape) replaces the draw, for tests and replays; the noise of the last call is kept as
+    `last_draws['noise']`, as GaussianNoise does.
+    """
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+
+    def compute_output_shape(self, input_shape):
+        return input_shape[0]
+
+    def call(self, x, _noise=None):
+        mu, log_var = x
+        _require_f32_local('SampleNormalLogVar', mu, log_var, _noise)
+        dev = _lib.require_device(mu, log_var, _noise)
+        if tuple(mu.shape) != tuple(log_var.shape):
+            raise ValueError('SampleNormalLogVar: mu %s and log_var %s differ in shape' % (tuple(mu.shape), tuple(log_var.shape)))
+        noise = torch.randn(mu.shape, dtype=torch.float32, device=dev) if _noise is None else _noise
+        if tuple(noise.shape) != tuple(mu.shape):
+            raise ValueError('SampleNormalLogVar: _noise %s, expected %s' % (tuple(noise.shape), tuple(mu.shape)))
+        self.last_draws = dict(noise=noise)
+        if torch.is_grad_enabled() and (mu.requires_grad or log_var.requires_grad):
+            return _SampleNormalFn.apply(mu, log_var, noise)
+        return _SampleNormalFn.forward(_NoCtx(), mu.detach(), log_var.detach(), noise)

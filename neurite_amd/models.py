@@ -45,9 +45,10 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import layers
 from . import utils
 
-__all__ = ['unet', 'conv_enc', 'conv_dec', 'conv_block', 'ConvNet', 'labels_to_image', 'labels_to_image_new', 'SynthStrip', 'add_prior', 'dilation_net', 'load', 'load_config']
+__all__ = ['unet', 'conv_enc', 'conv_dec', 'conv_block', 'ConvNet', 'labels_to_image', 'labels_to_image_new', 'SynthStrip', 'add_prior', 'dilation_net', 'load', 'load_config', 'ae', 'single_ae']
 
 # element-wise activations, codes of include/neurite_amd.h (nrt_activation); definitions follow tf.keras.activations -- the reference
 # hands the string straight to Keras (neurite/tf/models.py:1346, 1429, 1507, 1588)
@@ -129,6 +130,8 @@ def _store_config(func):
     @functools.wraps(func)
     def wrapper(*args, **kwargs):
         net = func(*args, **kwargs)
+        if isinstance(net, tuple):                     # ae(single_model=False): three models, each with the config of its own builder
+            return net
         bound = sig.bind(*args, **kwargs)
         bound.apply_defaults()
         params = {}
@@ -136,6 +139,10 @@ def _store_config(func):
         for k, v in bound.arguments.items():
             if k in ('convL', 'src', 'src_input', 'input_model'):
                 loadable = loadable and v is None
+                continue
+            if k == 'enc_lambda_layers':               # callables do not travel in a config
+                loadable = loadable and not v
+                params[k] = None
                 continue
             params[k] = _jsonable(v)
         params['metadata'] = {}
@@ -453,6 +460,93 @@ class _Conv(nn.Module):
         if self.act > _ACT_LAST_FUSED:            # activations beyond elu / relu: an element-wise pass over the layer output
             out = _elementwise(out, act=self.act)
         return out
+
+
+class _Dense(nn.Module):
+    """Keras Dense: kernel [in, out] (glorot_uniform) exactly as a .h5 file stores it -- nrt_dense_f32 reads that layout, so there is no
+    transposed or packed copy to invalidate -- and bias [out] (zeros)."""
+
+    def __init__(self, name, cin, cout, activation=None):
+        super().__init__()
+        self.layer_name = name
+        self.cin, self.cout = int(cin), int(cout)
+        self.activation = activation
+        self.act = _act_code(activation)
+        limit = math.sqrt(6.0 / (self.cin + self.cout))
+        self.kernel = nn.Parameter((torch.rand(self.cin, self.cout) * 2 - 1) * limit)
+        self.bias = nn.Parameter(torch.zeros(self.cout))
+
+    def forward(self, x, variant=0):
+        return _dense(x, self.kernel, self.bias, self.act, variant)
+
+
+class _LocalBiasWeight(nn.Module):
+    """the one weight of layers.LocalBias (neurite/tf/layers.py:762-767): `kernel` of the shape of one batch entry, Keras' default
+    RandomNormal (stddev 0.05)"""
+
+    def __init__(self, name, shape):
+        super().__init__()
+        self.layer_name = name
+        self.kernel = nn.Parameter(torch.empty(tuple(int(v) for v in shape)).normal_(0.0, 0.05))
+
+
+def _dense_workspace(dev, batch, cin, cout, variant):
+    n = _lib.lib().nrt_dense_workspace_bytes(batch, cin, cout, variant)
+    return (_lib.workspace(dev, n), n) if n else (None, 0)
+
+
+def _dense_run(x, kernel, bias, act, variant):
+    lib = _lib.lib()
+    dev = _lib.require_device(x, kernel, bias)
+    x = x.contiguous()
+    B, cin, cout = x.shape[0], kernel.shape[0], kernel.shape[1]
+    if x.dim() != 2 or x.shape[1] != cin:
+        raise ValueError('Dense: input of shape %s for a kernel %s' % (tuple(x.shape), tuple(kernel.shape)))
+    y = torch.empty((B, cout), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, n = _dense_workspace(dev, B, cin, cout, variant)
+        rc = lib.nrt_dense_f32(_p32(x), _p32(kernel), _p32(bias), _p32(y), B, cin, cout, int(act), int(variant), _lib.ptr(ws), n,
+                               _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_dense_f32')
+    return y
+
+
+class _DenseFn(torch.autograd.Function):
+    """y = act(x @ kernel + bias) and its three gradients on csrc/dense.hip; the activation's backward is nrt_act_bwd_f32 on y"""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, act, variant):
+        with torch.no_grad():
+            y = _dense_run(x, kernel, bias, act, variant)
+        ctx.save_for_backward(x, kernel, y)
+        ctx.cfg = (act, variant)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, kernel, y = ctx.saved_tensors
+        act, variant = ctx.cfg
+        lib = _lib.lib()
+        dev = g.device
+        d = _act_bwd(g, y, act)
+        x = x.contiguous()
+        B, cin, cout = x.shape[0], kernel.shape[0], kernel.shape[1]
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(kernel) if need_w else None
+        gb = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
+        with torch.cuda.device(dev):
+            ws, n = _dense_workspace(dev, B, cin, cout, variant)
+            rc = lib.nrt_dense_bwd_f32(_p32(d), _p32(x), _p32(kernel), _p32(gx), _p32(gw), _p32(gb), B, cin, cout, int(variant),
+                                       _lib.ptr(ws), n, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_dense_bwd_f32')
+        return gx, gw, gb, None, None
+
+
+def _dense(x, kernel, bias, act=0, variant=0):
+    if torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad or (bias is not None and bias.requires_grad)):
+        return _DenseFn.apply(x, kernel, bias, act, variant)
+    return _dense_run(x, kernel.detach(), None if bias is None else bias.detach(), act, variant)
 
 
 class _BatchNorm(nn.Module):
@@ -1142,6 +1236,10 @@ class _SoftmaxFn(torch.autograd.Function):
         return dz
 
 
+# the op kinds of the auto-encoder bottleneck (single_ae); float32 only
+_AE_KINDS = ('flatten', 'reshape', 'dense', 'resize', 'local_bias', 'sample', 'identity', 'lambda')
+
+
 class _PendingConv:
     """inputs of a decoder convolution whose only consumer is the soft-max head: both run as one kernel at the head's op"""
 
@@ -1166,9 +1264,12 @@ class ConvNet(nn.Module):
         for k, m in modules.items():
             self.layers_by_name[k] = m
         self.layer_names = [op['name'] for op in ops]
+        self._flat = {op['name']: bool(op.get('flat')) for op in ops}      # layers whose Keras tensor is [B, E]
         self.output_shape = ops[-1].get('shape') if ops else None
         self.conv_variant = 0                       # 0 auto, 1 direct, 2 MFMA (tests / tuning); float32 only, bf16 ignores it
         self.fold_head = True                       # inference: last decoder convolution + likelihood + soft-max as ONE kernel where it applies
+        self.dense_variant = 0                      # 0 auto, 1 reduce arm, 2 expand arm of csrc/dense.hip (tests / tuning)
+        self.last_draws = {}                        # {sampling layer: the N(0, 1) noise of the last forward}
         # {conv layer: the soft-max likelihood that is its ONLY consumer}: candidates for nrt_conv3d_up2_head_f32 (models.py:1545-1605)
         uses = {}
         for op in ops:
@@ -1208,7 +1309,8 @@ class ConvNet(nn.Module):
 
     # ---- Keras Model weight API (modelio: neurite/tf/modelio.py:111-143 saves/loads `model.get_weights()` lists) ----
     def _weight_tensors(self):
-        """weights in Keras order: layers in graph order; Conv: kernel, bias; BatchNormalization: gamma, beta, mean, variance"""
+        """weights in Keras order: layers in graph order; Conv and Dense: kernel, bias; BatchNormalization: gamma, beta, mean, variance;
+        LocalBias: kernel"""
         out = []
         for name in self.layer_names:
             if name in self.layers_by_name:
@@ -1218,6 +1320,10 @@ class ConvNet(nn.Module):
                 elif isinstance(m, _BatchNorm):
                     out += [(name + '/gamma', m.gamma, None), (name + '/beta', m.beta, None),
                             (name + '/moving_mean', m.moving_mean, None), (name + '/moving_variance', m.moving_variance, None)]
+                elif isinstance(m, _Dense):
+                    out += [(name + '/kernel', m.kernel, None), (name + '/bias', m.bias, None)]
+                elif isinstance(m, _LocalBiasWeight):
+                    out += [(name + '/kernel', m.kernel, None)]
         return out
 
     def get_weights(self):
@@ -1383,6 +1489,8 @@ class ConvNet(nn.Module):
 
         def shape_of(op):
             sp, c = op['shape']
+            if op.get('flat'):
+                return [None, int(c)]
             return [None] + [int(v) for v in sp[3 - nd:]] + [int(c)]
 
         def emit(name, cls, config, inputs, out_shape):
@@ -1436,6 +1544,23 @@ class ConvNet(nn.Module):
                     emit(name, 'Lambda', {'function': [['softmax', op.get('axis', nd + 1)]]}, [op['src']], shape_of(op))
                 else:
                     emit(name, 'Activation', {'activation': op['activation']}, [op['src']], shape_of(op))
+            elif kind == 'flatten':
+                emit(name, 'Flatten', {}, [op['src']], shape_of(op))
+            elif kind == 'reshape':
+                emit(name, 'Reshape', {'target_shape': shape_of(op)[1:]}, [op['src']], shape_of(op))
+            elif kind == 'dense':
+                m = self.layers_by_name[name]
+                emit(name, 'Dense', {'units': m.cout, 'activation': m.activation if m.activation is not None else 'linear',
+                                     'use_bias': True}, [op['src']], shape_of(op))
+            elif kind == 'resize':
+                emit(name, 'Resize', {'zoom_factor': [float(z) for z in op['zoom']], 'interp_method': 'linear'}, [op['src']],
+                     shape_of(op))
+            elif kind == 'local_bias':
+                emit(name, 'LocalBias', {'my_initializer': 'RandomNormal', 'biasmult': 1.0}, [op['src']], shape_of(op))
+            elif kind == 'sample':
+                emit(name, 'SampleNormalLogVar', {}, [op['a'], op['b']], shape_of(op))
+            elif kind in ('identity', 'lambda'):
+                emit(name, 'Lambda', {'function': []}, [op['src']], shape_of(op))
             else:
                 raise RuntimeError('unknown op ' + kind)
         # dropouts are referred to by their builder names inside the op list
@@ -1478,9 +1603,10 @@ class ConvNet(nn.Module):
         shift = bn.beta.detach() - bn.moving_mean * scale
         return scale.contiguous(), shift.contiguous()
 
-    def forward(self, inputs, return_tensors=None):
+    def forward(self, inputs, return_tensors=None, _noise=None):
         """inputs: [B, *spatial, C] (or a list for multi-input nets).  Returns the prediction tensor
-        (or a dict of the named intermediate tensors listed in return_tensors)."""
+        (or a dict of the named intermediate tensors listed in return_tensors).  _noise: {sampling layer name: tensor} replaces the
+        N(0, 1) draw of a SampleNormalLogVar layer (tests, replays); the draws of a call are kept in `last_draws`."""
         if isinstance(inputs, (list, tuple)):
             xs = list(inputs)
         else:
@@ -1488,6 +1614,12 @@ class ConvNet(nn.Module):
         if len(xs) != len(self.input_shapes):
             raise ValueError('%s expects %d input(s), got %d' % (self.name, len(self.input_shapes), len(xs)))
         bf16 = self._compute_dtype() == torch.bfloat16
+        if bf16:
+            for op in self.ops:
+                if op['kind'] in _AE_KINDS:
+                    raise NotImplementedError('%s: %s layers have no bfloat16 kernel; run this network in float32 (net.float())'
+                                              % (op['name'], op['kind']))
+        self._noise = dict(_noise or {})
         if bf16 and self.training and torch.is_grad_enabled():
             raise NotImplementedError('%s: bfloat16 networks run inference only (model.eval() or torch.no_grad()); train in '
                                       'float32' % self.name)
@@ -1561,12 +1693,55 @@ class ConvNet(nn.Module):
                         t[name] = _softmax(t[op['src']])
                     else:
                         t[name] = _elementwise(t[op['src']], act=_act_code(op['activation']))
+                elif kind in _AE_KINDS:
+                    self._ae_op(op, t)
                 else:
                     raise RuntimeError('unknown op ' + kind)
         if return_tensors:
-            return {k: _unlift(t[k], nd) for k in keep}
-        return _unlift(t[self.output_name], nd)
+            return {k: self._unlift_named(k, t[k]) for k in keep}
+        return self._unlift_named(self.output_name, t[self.output_name])
 
+    def _unlift_named(self, name, x):
+        """the tensor of layer `name` in its Keras shape: [B, *spatial, C], or [B, E] behind a Flatten / Dense"""
+        if self._flat.get(name):
+            return x.reshape(x.shape[0], -1)
+        return _unlift(x, self.ndims)
+
+    def _ae_op(self, op, t):
+        """the bottleneck layers of single_ae (models.py:438-646), inference and autograd recording alike: every kernel behind them
+        records itself when gradients are enabled.  A [B, E] tensor rides as [B, 1, 1, 1, E]."""
+        kind, name = op['kind'], op['name']
+        nd = self.ndims
+        if kind == 'identity':
+            t[name] = t[op['src']]
+        elif kind == 'lambda':
+            src = t[op['src']]
+            t[name] = op['fn'](self._unlift_named(op['src'], src)).reshape(src.shape)
+        elif kind == 'flatten':
+            src = t[op['src']]
+            t[name] = src.reshape(src.shape[0], 1, 1, 1, -1)        # channels-last row-major: Keras' Flatten, a view
+        elif kind == 'reshape':
+            sp, c = op['shape']
+            t[name] = t[op['src']].reshape((-1,) + tuple(sp) + (c,))
+        elif kind == 'dense':
+            src = t[op['src']]
+            y = self.layers_by_name[name](src.reshape(src.shape[0], -1), variant=self.dense_variant)
+            t[name] = y.view(y.shape[0], 1, 1, 1, -1)
+        elif kind == 'resize':
+            t[name] = _lift(self.layers_by_name[name](_unlift(t[op['src']], nd)), nd)
+        elif kind == 'local_bias':
+            src, k = t[op['src']], self.layers_by_name[name].kernel
+            t[name] = layers._local_affine('LocalBias', src.reshape((-1,) + tuple(k.shape)), None, k, 1.0).reshape(src.shape)
+        elif kind == 'sample':
+            mu, lv = t[op['a']], t[op['b']]
+            noise = self._noise.get(name)
+            if noise is not None:
+                noise = noise.to(torch.float32).reshape(mu.shape)
+            lay = self.layers_by_name[name]
+            t[name] = lay([mu, lv], _noise=noise)
+            self.last_draws[name] = lay.last_draws['noise']
+        else:
+            raise RuntimeError('unknown op ' + kind)
 
     def _forward_bf16(self, xs, keep, return_tensors):
         """inference of a bf16 network on the bf16 kernels (module docstring: rounding points).  With fold_head every merge whose
@@ -1626,6 +1801,8 @@ class ConvNet(nn.Module):
                         t[name] = _softmax_bf16(t[op['src']])
                     else:
                         t[name] = _elementwise_bf16(t[op['src']], act=_act_code(op['activation']))
+                elif kind in _AE_KINDS:                         # (refused in forward(): no bf16 kernels behind these)
+                    raise NotImplementedError('%s: %s layers have no bfloat16 kernel' % (name, kind))
                 else:
                     raise RuntimeError('unknown op ' + kind)
         if return_tensors:
@@ -1694,11 +1871,13 @@ class ConvNet(nn.Module):
                     t[name] = t[op['src']]
                 else:
                     t[name] = _AddActFn.apply(t[op['src']], None, _act_code(op['activation']))
+            elif kind in _AE_KINDS:
+                self._ae_op(op, t)
             else:
                 raise NotImplementedError('neurite_amd: training through %r layers (%s) is not implemented' % (kind, name))
         if return_tensors:
-            return {k: _unlift(t[k], nd) for k in keep}
-        return _unlift(t[self.output_name], nd)
+            return {k: self._unlift_named(k, t[k]) for k in keep}
+        return self._unlift_named(self.output_name, t[self.output_name])
 
 
 # --------------------------------------------------------------------------------------
@@ -2095,6 +2274,241 @@ def unet(nb_features, input_shape, nb_levels, conv_size, nb_labels, name='unet',
     return net
 
 
+def _keras_shape(bld, name):
+    """shape (without batch) of the Keras tensor behind op `name`: [*spatial, C], or [E] behind a Flatten / Dense"""
+    sp, c = bld.shapes[name]
+    op = next(o for o in bld.ops if o['name'] == name)
+    if op.get('flat'):
+        return [int(c)]
+    return [int(v) for v in sp[3 - bld.ndims:]] + [int(c)]
+
+
+def _last_axis_only(name, axis, rank):
+    """Keras BatchNormalization(axis=...) on a tensor of `rank` axes (batch included): the kernels normalise over the last one"""
+    a = int(axis)
+    if a < 0:
+        a += rank
+    if a != rank - 1:
+        raise NotImplementedError('%s: BatchNormalization over axis %r of a rank-%d tensor is not implemented (the last axis is)'
+                                  % (name, axis, rank))
+
+
+def _single_ae_layers(bld, last, prefix, enc_size, ae_type, conv_size, enc_lambda_layers, batch_norm, padding, activation,
+                      include_mu_shift_layer, do_vae):
+    """the layers of models.single_ae (neurite/tf/models.py:476-642) appended behind tensor `last`; returns the output name"""
+    ndims = bld.ndims
+    input_shape = _keras_shape(bld, last)                                        # :472
+    input_nb_feats = input_shape[-1]
+    one3 = (1, 1, 1)                                                             # a [B, E] tensor rides as [B, 1, 1, 1, E]
+
+    def add(op, sp3, c, flat):
+        if flat:
+            op['flat'] = True
+        return bld.add(op, (tuple(sp3), int(c)))
+
+    def same(op, src):
+        sp3, c = bld.shapes[src]
+        return add(op, sp3, c, next(o for o in bld.ops if o['name'] == src).get('flat'))
+
+    def conv(name, src, filters):
+        sp, cin = bld.shapes[src]
+        bld.modules[name] = _Conv(name, cin, int(filters), k3, 1, padding, activation)
+        return add({'kind': 'conv', 'name': name, 'src': src}, _conv_out(sp, k3, 1, padding), int(filters), False)
+
+    def resize(name, src, target):
+        sp, c = bld.shapes[src]
+        cur = list(sp[3 - ndims:])
+        zf = [target[f] / cur[f] for f in range(ndims)]                           # :516-517, 572-573, 632
+        bld.modules[name] = layers.Resize(zoom_factor=list(zf), name=name)
+        out = (1,) * (3 - ndims) + tuple(int(cur[f] * zf[f]) for f in range(ndims))     # Resize.compute_output_shape
+        return add({'kind': 'resize', 'name': name, 'src': src, 'zoom': zf}, out, c, False)
+
+    def local_bias(name, src):
+        bld.modules[name] = _LocalBiasWeight(name, _keras_shape(bld, src))
+        return same({'kind': 'local_bias', 'name': name, 'src': src}, src)
+
+    def bn(name, src):
+        _last_axis_only(name, batch_norm, len(_keras_shape(bld, src)) + 1)
+        bld.modules[name] = _BatchNorm(name, bld.shapes[src][1])
+        return same({'kind': 'bn', 'name': name, 'src': src, 'axis': batch_norm}, src)
+
+    def clean_up(which, src):                                                     # :535-547, 590-602
+        for layer_fcn in enc_lambda_layers:
+            name = '%s_ae_%s_%s' % (prefix, which, layer_fcn.__name__)
+            src = same({'kind': 'lambda', 'name': name, 'src': src, 'fn': layer_fcn}, src)
+        if batch_norm is not None:
+            src = bn('%s_ae_%s_bn' % (prefix, which), src)
+        return same({'kind': 'identity', 'name': '%s_ae_%s' % (prefix, which), 'src': src}, src)
+
+    if ae_type == 'conv':                                                        # :476-479
+        if len(input_shape) - 1 != ndims or ndims < 1:
+            raise ValueError('a convolutional auto-encoder needs a [*spatial, features] input, got %s' % (input_shape,))
+        assert conv_size is not None, 'with conv ae, need conv_size'
+        k3 = _triple(conv_size, ndims, 'conv_size')
+    if ae_type == 'dense' and len(input_shape) > 1:                              # :486-488
+        last = add({'kind': 'flatten', 'name': '%s_ae_%s_down_flat' % (prefix, ae_type), 'src': last}, one3,
+                   int(np.prod(input_shape)), True)
+    pre_enc = last
+
+    if ae_type == 'dense':                                                       # :494-499
+        assert len(enc_size) == 1, "enc_size should be of length 1 for dense layer"
+        enc_size_str = ''.join(['%d_' % d for d in enc_size])[:-1]
+
+        def dense_enc(which):
+            name = '%s_ae_%s_enc_dense_%s' % (prefix, which, enc_size_str)
+            bld.modules[name] = _Dense(name, bld.shapes[pre_enc][1], int(enc_size[0]))
+            return add({'kind': 'dense', 'name': name, 'src': pre_enc}, one3, int(enc_size[0]), True)
+        last = dense_enc('mu')
+    else:                                                                        # :501-528
+        assert len(enc_size) == len(input_shape), \
+            "encoding size does not match input shape %d %d" % (len(enc_size), len(input_shape))
+        resized = list(enc_size)[:-1] != list(input_shape)[:-1] and all(f is not None for f in input_shape[:-1]) and \
+            all(f is not None for f in enc_size[:-1])
+        if resized:
+            last = conv('%s_ae_mu_enc_conv' % prefix, pre_enc, enc_size[-1])
+            last = resize('%s_ae_mu_enc' % prefix, last, list(enc_size[:-1]))
+        elif enc_size[-1] is None:
+            last = same({'kind': 'identity', 'name': '%s_ae_mu_enc' % prefix, 'src': pre_enc}, pre_enc)
+        else:
+            last = conv('%s_ae_mu_enc' % prefix, pre_enc, enc_size[-1])
+
+    if include_mu_shift_layer:                                                   # :530-533
+        last = local_bias('%s_ae_mu_shift' % prefix, last)
+    last = clean_up('mu', last)
+
+    if do_vae:                                                                   # :550-608
+        mu = last
+        if ae_type == 'dense':
+            last = dense_enc('sigma')
+        elif resized:
+            last = conv('%s_ae_sigma_enc_conv' % prefix, pre_enc, enc_size[-1])
+            last = resize('%s_ae_sigma_enc' % prefix, last, list(enc_size[:-1]))
+        elif enc_size[-1] is None:
+            last = conv('%s_ae_sigma_enc' % prefix, pre_enc, bld.shapes[pre_enc][1])
+        else:
+            last = conv('%s_ae_sigma_enc' % prefix, pre_enc, enc_size[-1])
+        logvar = clean_up('sigma', last)
+        name = '%s_ae_sample' % prefix
+        bld.modules[name] = layers.SampleNormalLogVar(name=name)
+        op = {'kind': 'sample', 'name': name, 'a': mu, 'b': logvar}
+        last = same(op, mu)
+
+    if include_mu_shift_layer:                                                   # :610-613
+        last = local_bias('%s_ae_sample_shift' % prefix, last)
+
+    if ae_type == 'dense':                                                       # :616-623
+        name = '%s_ae_%s_dec_flat_%s' % (prefix, ae_type, enc_size_str)
+        units = int(np.prod(input_shape))
+        bld.modules[name] = _Dense(name, bld.shapes[last][1], units)
+        last = add({'kind': 'dense', 'name': name, 'src': last}, one3, units, True)
+        if len(input_shape) > 1:
+            sp3 = (1,) * (4 - len(input_shape)) + tuple(input_shape[:-1])
+            last = add({'kind': 'reshape', 'name': '%s_ae_%s_dec' % (prefix, ae_type), 'src': last}, sp3, input_shape[-1], False)
+    else:                                                                        # :625-638
+        if resized:
+            last = resize('%s_ae_mu_dec' % prefix, last, list(input_shape[:-1]))
+        last = conv('%s_ae_%s_dec' % (prefix, ae_type), last, input_nb_feats)
+
+    if batch_norm is not None:                                                   # :640-642
+        last = bn('%s_bn_ae_%s_dec' % (prefix, ae_type), last)
+    return last
+
+
+@_store_config
+def single_ae(enc_size, input_shape, name='single_ae', prefix=None, ae_type='dense', conv_size=None, input_model=None,
+              enc_lambda_layers=None, batch_norm=True, padding='same', activation=None, include_mu_shift_layer=False,
+              do_vae=False):
+    """
+    Single-layer (variational) auto-encoder, input - encoding - output (neurite/tf/models.py:438-646): `ae_type='dense'` is
+    Flatten - Dense(enc_size) - Dense(prod(input_shape)) - Reshape on csrc/dense.hip, `ae_type='conv'` a convolution (with a Resize
+    where the encoding's spatial size differs, a pass-through where enc_size[-1] is None).  do_vae adds the sigma branch and
+    layers.SampleNormalLogVar; include_mu_shift_layer a LocalBias before and after it; enc_lambda_layers are callables on torch
+    tensors, named by their __name__; batch_norm is the BatchNormalization axis (it must be the tensor's last one).
+    """
+    model_name = name
+    if prefix is None:
+        prefix = model_name
+    if enc_lambda_layers is None:
+        enc_lambda_layers = []
+    if ae_type not in ('dense', 'conv'):
+        raise ValueError("ae_type must be 'dense' or 'conv', got %r" % (ae_type,))
+    if input_model is None:
+        assert input_shape is not None, 'input_shape of input_model is necessary'
+        input_shape = tuple(int(s) for s in input_shape)
+        ndims = len(input_shape) - 1
+        if ndims > 3:
+            raise NotImplementedError('inputs of up to 3 spatial dimensions are supported')
+        bld = _Builder(ndims)
+        op = {'kind': 'input', 'name': '%s_input' % prefix, 'index': 0}
+        if ndims == 0:
+            op['flat'] = True
+        last = bld.add(op, ((1,) * (3 - ndims) + input_shape[:-1], input_shape[-1]))
+        input_shapes = [input_shape]
+    else:
+        if not isinstance(input_model, ConvNet):
+            raise TypeError('input_model must be a network built by this module')
+        bld = _Builder(input_model.ndims)
+        bld.ops = list(input_model.ops)
+        bld.modules = dict(input_model.layers_by_name.items())
+        bld.shapes = dict(input_model._builder_state['shapes'])
+        last = input_model.output_name
+        input_shapes = input_model.input_shapes
+    last = _single_ae_layers(bld, last, prefix, enc_size, ae_type, conv_size, enc_lambda_layers, batch_norm, padding, activation,
+                             include_mu_shift_layer, do_vae)
+    net = ConvNet(model_name, bld.ndims, input_shapes, bld.ops, last, bld.modules)
+    net._builder_state = dict(shapes=bld.shapes)
+    return net
+
+
+@_store_config
+def ae(nb_features, input_shape, nb_levels, conv_size, nb_labels, enc_size, name='ae', prefix=None, feat_mult=1, pool_size=2,
+       padding='same', activation='elu', use_residuals=False, nb_conv_per_level=1, batch_norm=None, enc_batch_norm=None,
+       ae_type='conv', enc_lambda_layers=None, add_prior_layer=False, add_prior_layer_reg=0, use_logp=True, conv_dropout=0,
+       include_mu_shift_layer=False, single_model=False, final_pred_activation='softmax', src=None, src_input=None,
+       do_vae=False):
+    """
+    Convolutional (optionally variational, optionally dense-bottleneck) auto-encoder (neurite/tf/models.py:249-375):
+    conv_enc - single_ae - conv_dec [- add_prior].  Returns (dec_model, mid_ae_model, enc_model), three stackable networks, or with
+    single_model=True the one chained network.
+    """
+    model_name = name
+    ndims = len(input_shape) - 1
+    if isinstance(pool_size, int):
+        pool_size = (pool_size,) * ndims
+    enc_model = conv_enc(nb_features, input_shape, nb_levels, conv_size, name=model_name, feat_mult=feat_mult,
+                         pool_size=pool_size, padding=padding, activation=activation, use_residuals=use_residuals,
+                         nb_conv_per_level=nb_conv_per_level, conv_dropout=conv_dropout, batch_norm=batch_norm, src=src,
+                         src_input=src_input)
+
+    def out_shape(model):
+        sp, c = model._builder_state['shapes'][model.output_name]
+        return [int(v) for v in sp[3 - model.ndims:]] + [int(c)]
+
+    if single_model:                                                             # :321-326
+        in_input_shape, in_model = None, enc_model
+    else:
+        in_input_shape, in_model = out_shape(enc_model), None
+    mid_ae_model = single_ae(enc_size, in_input_shape, conv_size=conv_size, name=model_name, ae_type=ae_type,
+                             input_model=in_model, batch_norm=enc_batch_norm, enc_lambda_layers=enc_lambda_layers,
+                             include_mu_shift_layer=include_mu_shift_layer, do_vae=do_vae)
+    if single_model:                                                             # :339-344
+        in_input_shape, in_model = None, mid_ae_model
+    else:
+        in_input_shape, in_model = out_shape(mid_ae_model), None
+    dec_model = conv_dec(nb_features, in_input_shape, nb_levels, conv_size, nb_labels, name=model_name, feat_mult=feat_mult,
+                         pool_size=pool_size, use_skip_connections=False, padding=padding, activation=activation,
+                         use_residuals=use_residuals, final_pred_activation=final_pred_activation,
+                         nb_conv_per_level=nb_conv_per_level, batch_norm=batch_norm, conv_dropout=conv_dropout,
+                         input_model=in_model)
+    if add_prior_layer:                                                          # :363-370
+        dec_model = add_prior(dec_model, [*input_shape[:-1], nb_labels], name=model_name, prefix=model_name + '_prior',
+                              use_logp=use_logp, final_pred_activation=final_pred_activation,
+                              add_prior_layer_reg=add_prior_layer_reg)
+    if single_model:
+        return dec_model
+    return (dec_model, mid_ae_model, enc_model)
+
+
 def load_config(path):
     """builder name and arguments stored by `ConvNet.save` (LoadableModel.load_config, neurite/tf/modelio.py:125-143)"""
     if _is_h5(path):
@@ -2116,9 +2530,10 @@ def load(path, by_name=False, **kwargs):
     arguments override them), then load its weights.
     """
     builder, config = load_config(path)
-    builders = {'unet': unet, 'conv_enc': conv_enc, 'conv_dec': conv_dec}
+    builders = {'unet': unet, 'conv_enc': conv_enc, 'conv_dec': conv_dec, 'ae': ae, 'single_ae': single_ae}
     if builder not in builders:
-        raise ValueError('%s was not saved from a unet / conv_enc / conv_dec network (class_name %r)' % (path, builder))
+        raise ValueError('%s was not saved from a unet / conv_enc / conv_dec / ae / single_ae network (class_name %r)'
+                         % (path, builder))
     config.update(kwargs)
     metadata = config.pop('metadata', {})
     model = builders[builder](**config)
