@@ -751,6 +751,29 @@ int nrt_dense_f32(const float *x, const float *w, const float *bias, float *y, i
 int nrt_dense_bwd_f32(const float *g, const float *x, const float *w, float *gx, float *gw, float *gbias, int batch, int in, int out,
                       int variant, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Barycenter (centre of mass) of feature maps, neurite/tf/utils/utils.py:512-573, in one pass, and its gradient (csrc/barycenter.hip).
+ * x [outer, r_0, ..., r_{k-1}, inner] contiguous, stored as `dtype` (NRT_DT_F32 / NRT_DT_BF16 / NRT_DT_F16) and widened to float32 in
+ * registers; red_shape = {r_0 .. r_{k-1}} (host memory), 1 <= k <= 8.  The coordinate of index i along a reduced dimension of size v
+ * is the reference's float32 grid value ((float)i, minus (v - 1) / 2 if shift_center, divided by v if normalize), bit for bit.
+ *   nrt_barycenter       sums [outer, inner, k + 1] float32: the k numerators sum_r g_d(r) x and the denominator D = sum_r x;
+ *                        y [outer, inner, k] float32 = numerator / D, exactly 0 where D == 0 (tf.math.divide_no_nan).
+ *   nrt_barycenter_bwd   gy, y [outer, inner, k] and sums as the forward left them -> gx (the layout and dtype of x):
+ *                        gx[o, r, i] = sum_d gy[o, i, d] (g_d(r) - y[o, i, d]) / D[o, i], 0 where D == 0.
+ *   nrt_barycenter_workspace_bytes   what both calls need at most; 0 for a shape they refuse.
+ * No atomics: every sum has a fixed partition and order given the shapes and pointer alignment, results are run-to-run bit-identical.
+ * Base pointers need the alignment of their element type only (16-byte accesses are used where inner == 1 or inner is a multiple of
+ * 16 bytes and the pointer allows).  Checked before any launch: NRT_ERR_INVALID_ARG for a NULL tensor or red_shape, outer / inner / a
+ * reduced size < 1, k outside 1 .. 8; NRT_ERR_UNSUPPORTED for another dtype, a reduced size >= 2^24 (coordinates stop being exact in
+ * float32) and outer * R * inner >= 2^31 elements; NRT_ERR_WORKSPACE for a missing or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_barycenter_workspace_bytes(int dtype, long long outer, const int *red_shape, int k, long long inner);
+int nrt_barycenter(const void *x, int dtype, long long outer, const int *red_shape, int k, long long inner, int normalize,
+                   int shift_center, float *y, float *sums, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_barycenter_bwd(const float *gy, const float *y, const float *sums, int dtype, long long outer, const int *red_shape, int k,
+                       long long inner, int normalize, int shift_center, void *gx, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,9 @@ _SIGNATURES = {
     'nrt_dense_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'nrt_dense_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'nrt_dense_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'nrt_barycenter_workspace_bytes': (_sz, [_i, _ll, _ip, _i, _ll]),
+    'nrt_barycenter': (_i, [_vp, _i, _ll, _ip, _i, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_barycenter_bwd': (_i, [_vp, _vp, _vp, _i, _ll, _ip, _i, _ll, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -4,7 +4,7 @@ neurite_amd.utils -- the tensor utilities of neurite's hot path on MI355X.
 Mirrors the names, arguments, defaults and error behaviour of neurite/tf/utils/utils.py for
 interpn (:73), resize/zoom (:223,:265), volshape_to_ndgrid (:333), volshape_to_meshgrid (:356),
 ndgrid (:382), meshgrid (:398), sub2ind2d (:1068), prod_n (:1085), batch_channel_flatten (:1175),
-flatten_axes (:1195); plus voxelmorph's transform()/affine_to_dense_shift, which the reference
+flatten_axes (:1195), barycenter (:512); plus voxelmorph's transform()/affine_to_dense_shift, which the reference
 calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159).
 
 Tensors are torch tensors on a ROCm device in the reference's channels-last layout.  All sampling
@@ -20,7 +20,7 @@ import torch
 from . import _lib
 
 __all__ = ['interpn', 'resize', 'zoom', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
-           'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize',
+           'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter',
            'rescale_dense_transform', 'rescale_affine', 'is_affine_shape', 'validate_affine_shape', 'make_square_affine', 'volshape_to_ndgrid',
            'volshape_to_meshgrid', 'ndgrid', 'meshgrid', 'sub2ind2d', 'prod_n', 'batch_channel_flatten',
            'flatten_batch_channel', 'flatten_axes']
@@ -777,6 +777,117 @@ class _SoftQuantizeFn(torch.autograd.Function):
 def soft_digitize(*args, **kwargs):
     """alias of soft_quantize (utils.py:1095-1096)"""
     return soft_quantize(*args, **kwargs)
+
+
+_BARYCENTER_DTYPES = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
+
+
+def _barycenter_axes(axes, nd):
+    """axes of barycenter as a list of distinct non-negative ints, in the order given"""
+    if axes is None:
+        return list(range(nd))
+    axes = [axes] if isinstance(axes, (int, np.integer)) else list(axes)
+    out = []
+    for ax in axes:
+        if isinstance(ax, bool) or not isinstance(ax, (int, np.integer)):
+            raise ValueError('barycenter: axes must be ints, got %r' % (ax,))
+        if not -nd <= ax < nd:
+            raise ValueError('barycenter: axis %d is out of range for a tensor of %d dimensions' % (ax, nd))
+        out.append(int(ax) % nd)
+    if len(set(out)) != len(out):
+        raise ValueError('barycenter: duplicate axes in %r' % (axes,))
+    if not out:
+        raise ValueError('barycenter: no axes to reduce')
+    return out
+
+
+class _BarycenterFn(torch.autograd.Function):
+    """x [outer, *red, inner] contiguous (float32 / bfloat16 / float16) -> y [outer, inner, k] float32 (csrc/barycenter.hip).  The
+    backward needs y and the sums the forward leaves, not x."""
+
+    @staticmethod
+    def forward(ctx, x, red, flags):
+        lib = _lib.lib()
+        dev = x.device
+        k = len(red)
+        outer, inner = int(x.shape[0]), int(x.shape[-1])
+        code = _BARYCENTER_DTYPES[x.dtype]
+        y = torch.empty((outer, inner, k), dtype=torch.float32, device=dev)
+        sums = torch.empty((outer, inner, k + 1), dtype=torch.float32, device=dev)
+        shape = _lib.ints(red)
+        nws = int(lib.nrt_barycenter_workspace_bytes(code, outer, shape, k, inner))
+        ws = _lib.workspace(dev, max(nws, 16))
+        with torch.cuda.device(dev):
+            rc = lib.nrt_barycenter(_lib.ptr(x), code, outer, shape, k, inner, flags[0], flags[1], _lib.ptr(y), _lib.ptr(sums),
+                                    _lib.ptr(ws), nws, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_barycenter')
+        ctx.save_for_backward(y, sums)
+        ctx.cfg = (code, outer, tuple(red), inner, flags, x.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, sums = ctx.saved_tensors
+        code, outer, red, inner, flags, dtype = ctx.cfg
+        lib = _lib.lib()
+        dev = y.device
+        k = len(red)
+        gy = gy.to(torch.float32).contiguous()
+        gx = torch.empty((outer,) + red + (inner,), dtype=dtype, device=dev)
+        shape = _lib.ints(red)
+        nws = int(lib.nrt_barycenter_workspace_bytes(code, outer, shape, k, inner))
+        ws = _lib.workspace(dev, max(nws, 16))
+        with torch.cuda.device(dev):
+            rc = lib.nrt_barycenter_bwd(_lib.ptr(gy), _lib.ptr(y), _lib.ptr(sums), code, outer, shape, k, inner, flags[0], flags[1],
+                                        _lib.ptr(gx), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_barycenter_bwd')
+        return gx, None, None
+
+
+def barycenter(x, axes=None, normalize=False, shift_center=False, dtype=torch.float32):
+    """
+    Barycenter (centre of mass) along the given axes (utils.py:512-573), in one pass over x (csrc/barycenter.hip).
+
+    x:            tensor of any type; float32, bfloat16 and float16 are read as stored, anything else is cast to float32 first.
+    axes:         axes along which to compute the barycenter, an int or a sequence of ints; None means all axes.  Negative axes count
+                  from the end (the reference fails on them); duplicates and out-of-range values raise ValueError.
+    normalize:    normalise the grid dimensions to unit length.
+    shift_center: shift the grid to the image centre.
+    dtype:        output data type; the computation always uses single precision.
+
+    Returns [*kept axes in their order, len(axes)]; the last index runs over `axes` in the order given.  Where x sums to zero the result
+    is exactly 0 (tf.math.divide_no_nan).  Differentiable in x, the gradient comes back in x's dtype; nothing travels to the host, so
+    a forward + backward captures into a graph.
+
+    Axes that form an ascending run of neighbours (all axes, the spatial axes of a channels-last batch, trailing axes) are reduced in
+    place from a contiguous x; any other `axes` pays one permute(...).contiguous() copy of x that moves them to the end.
+    """
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('expected a torch.Tensor, got %s' % type(x).__name__)
+    nd = x.dim()
+    if nd == 0:
+        raise ValueError('barycenter: x has no axes')
+    axes = _barycenter_axes(axes, nd)
+    _lib.require_device(x)
+    if x.dtype not in _BARYCENTER_DTYPES:
+        x = x.to(torch.float32)
+    k = len(axes)
+    if k > 8:
+        raise NotImplementedError('barycenter: up to 8 axes, got %d' % k)
+    kept = [ax for ax in range(nd) if ax not in axes]
+    if axes != list(range(axes[0], axes[0] + k)):
+        x = x.permute(*kept, *axes)                     # as the reference moves them: one copy
+        lead, trail = [int(x.shape[i]) for i in range(len(kept))], []
+    else:
+        lead, trail = [int(v) for v in x.shape[:axes[0]]], [int(v) for v in x.shape[axes[0] + k:]]
+    red = tuple(int(x.shape[len(lead) + i]) for i in range(k))
+    out_shape = tuple(lead) + tuple(trail) + (k,)
+    if x.numel() == 0:
+        return torch.zeros(out_shape, dtype=dtype, device=x.device)
+    outer, inner = int(np.prod(lead, dtype=np.int64)), int(np.prod(trail, dtype=np.int64))
+    x3 = x.contiguous().view((outer,) + red + (inner,))
+    y = _BarycenterFn.apply(x3, red, (int(bool(normalize)), int(bool(shift_center)))).view(out_shape)
+    return y if dtype == torch.float32 else y.to(dtype)
 
 
 # --------------------------------------------------------------------------------------
