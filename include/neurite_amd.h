@@ -308,7 +308,10 @@ int nrt_conv3d_pack_weights_f32(const float *weights /* Keras [kx,ky,kz,cin,cout
  *   nrt_conv3d_pack_weights_f32 (MFMA kernel; may be NULL => direct kernel); bias [cout] or NULL.
  * variant 0 = auto (MFMA implicit GEMM when k in {1,3}^3, SAME, dilation <= 2, cout <= 64, cin >= 8; its persistent LDS-DMA
  * schedule for 3x3x3, dilation 1, cin % 16 == 0 when there is more than one tile per CU), 1 = direct, 2 = MFMA (one tile per
- * block), 5 = MFMA in the persistent schedule.
+ * block), 5 = MFMA in the persistent schedule, 6 = the 2x2x2 MFMA arm (2x2x2 kernel, dilation 1, SAME, cin >= 8, cout <= 64,
+ * c0 % 4 == 0 with a second source, 16-byte aligned sources; anything else is NRT_ERR_UNSUPPORTED).  An even kernel runs on the
+ * direct kernel under variant 0, except that the 2x2x2 arm is taken where it has been measured faster (profiles/conv_even: 16 .. 64
+ * channels on both sides and at least 4 * 40^3 output voxels over the batch).
  */
 int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const int *up,
                    const float *weights, const float *packed_weights, const float *bias, float *out,
@@ -431,8 +434,11 @@ int nrt_add_act_affine_bf16(const void *a, const void *b, const float *scale, co
  *   nrt_conv3d_wgrad_f32   grad_weights [kx,ky,kz,cin,cout] += sum_v x[v + off(tap)] (x) grad_pre[v] (SAME padding) and
  *                          grad_bias [cout] += sum_v grad_pre[v]; both must be ZERO-FILLED by the caller (float
  *                          atomics, one per weight and block); x is the conv input as the layer saw it
- *                          (the concatenation, if any, materialised); ksize entries 1 or 3, dilation <= 2
- *   (grad_x = nrt_conv3d_f32(grad_pre, weights flipped in space and transposed in the channel axes))
+ *                          (the concatenation, if any, materialised); ksize entries 1 .. 4 (SAME padding as the forward pads
+ *                          it: floor((k - 1) * dilation / 2) before; kernels of more than 28 taps take a launch per 28),
+ *                          dilation <= 2
+ *   (grad_x = nrt_conv3d_pad_f32(grad_pre, weights flipped in space and transposed in the channel axes, pad_before =
+ *   (k - 1) * dilation - floor((k - 1) * dilation / 2)); for odd kernels that is nrt_conv3d_f32 with SAME padding)
  *   nrt_maxpool3d_bwd_f32  stride == pool: the window's gradient goes to its first maximum
  *   nrt_upsample_sum_f32   nearest up-sampling: grad_lo[v] = sum over the up^3 fine voxels of channels
  *                          [channel_offset, channel_offset + channels) of grad_up [.., grad_channels]
@@ -495,7 +501,7 @@ int nrt_hyperconv3d_f32(const float *src, int cin, const float *weights, const f
 /* Per-entry weight and bias gradient (what tf.GradientTape derives for neurite/tf/layers.py:2580-2612 with respect to the kernel and
  * bias inputs): grad_weights [batch, kx,ky,kz, cin, cout] and grad_bias [batch, cout] (or NULL), NOT summed over the batch.  Contract of
  * nrt_conv3d_wgrad_f32 otherwise: SAME padding, both outputs ZERO-FILLED by the caller (float atomics, one per weight and block: the sums
- * are not run-to-run bit-identical), ksize entries 1 or 3, dilation <= 2.  A block only accumulates tiles of one batch entry. */
+ * are not run-to-run bit-identical), ksize entries 1 .. 4, dilation <= 2.  A block only accumulates tiles of one batch entry. */
 int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad_weights, float *grad_bias, int batch,
                               const int *shape, int cin, int cout, const int *ksize, int dilation, void *stream);
 
@@ -773,6 +779,52 @@ int nrt_barycenter(const void *x, int dtype, long long outer, const int *red_sha
 int nrt_barycenter_bwd(const float *gy, const float *y, const float *sums, int dtype, long long outer, const int *red_shape, int k,
                        long long inner, int normalize, int shift_center, void *gx, void *workspace, size_t workspace_bytes,
                        void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Global max over the spatial axes and its gradient (csrc/globalmax.hip): Keras GlobalMaxPooling{1,2,3}D and, with channels = 1
+ * and v = V * C, the flatten-then-max lambda of design_dnn (neurite/tf/models.py:1640-1642, 1764).  float32, channels-last.
+ *   nrt_global_max_f32       x [batch, v, channels] -> y [batch, channels] = max over v, count [batch, channels] (int32) = how many
+ *                            positions attain it.  One pass over x; per-block (max, count) pairs in the workspace are merged by a
+ *                            second kernel (the larger max wins, equal maxima add their counts: exact and order-independent).
+ *                            The accumulator starts at -inf; a NaN anywhere in a slice gives y = NaN, count = 0.
+ *   nrt_global_max_bwd_f32   x, y, count as the forward left them, g [batch, channels] -> gx [batch, v, channels] =
+ *                            x == y ? (1.0f / count) * g : 0 (tf.reduce_max: ties share the gradient; the reciprocal is rounded
+ *                            first); a slice whose max is NaN gets NaN throughout.  One read of x, one write of gx.
+ *   nrt_global_max_workspace_bytes   what both calls need: batch * blocks * max(channels, 4) * 8 bytes, where blocks = the number of
+ *                            first-stage blocks per batch entry, min(ceil(v * channels / 16384), max(1, 2048 / batch), v); 0 for a
+ *                            shape the calls refuse.  Monotone in v.
+ * No atomics and no host synchronisation (both calls capture into a graph); run-to-run bit-identical.  Base pointers need 4-byte
+ * alignment only: 16-byte accesses are used where channels % 4 == 0 (or channels <= 2 and v * channels % 4 == 0) and the pointers allow.
+ * Checked before any launch: NRT_ERR_INVALID_ARG for a NULL tensor or batch / v / channels < 1; NRT_ERR_UNSUPPORTED for
+ * batch * v * channels >= 2^31 or batch > 65535; NRT_ERR_WORKSPACE for a missing or short workspace.
+ *
+ *   nrt_maxnorm_f32          Keras constraints.MaxNorm(max_value, axis=0) in place on w [k0, rest] (a convolution kernel
+ *                            [k0, ..., cin, cout]): n = sqrt(sum_k0 w^2), w <- w * (clip(n, 0, max_value) / (eps + n)); Keras' eps is
+ *                            1e-7.  NRT_ERR_INVALID_ARG: NULL w, k0 / rest < 1, max_value <= 0 or NaN, eps < 0 or NaN;
+ *                            NRT_ERR_UNSUPPORTED: k0 * rest >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_global_max_workspace_bytes(int batch, long long v, int channels);
+int nrt_global_max_f32(const float *x, int batch, long long v, int channels, float *y, int *count, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int nrt_global_max_bwd_f32(const float *x, const float *y, const int *count, const float *g, int batch, long long v, int channels,
+                           float *gx, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_maxnorm_f32(float *w, int k0, long long rest, float max_value, float eps, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Convolution with an explicit zero padding BEFORE (csrc/conv.hip): nrt_conv3d_f32 / nrt_hyperconv3d_f32 with padding_same = 1,
+ * except that pad_before[d] (0 .. (k_d - 1) * dilation) zeros precede the input along axis d and (k_d - 1) * dilation - pad_before[d]
+ * follow it; the output keeps the input's shape.  'same' pads floor((k - 1) * dilation / 2) before, so the transpose of a 'same'
+ * convolution -- its input gradient -- pads (k - 1) * dilation - floor((k - 1) * dilation / 2) before: the two differ for even
+ * kernels.  Where pad_before is what 'same' pads, the call IS the 'same' call (every variant); otherwise the direct kernel runs
+ * (variant 0 or 1) or, for nrt_conv3d_pad_f32, the 2x2x2 MFMA arm (variant 6, under the conditions stated at nrt_conv3d_f32;
+ * its halo follows pad_before); another variant is NRT_ERR_UNSUPPORTED.  A pad_before outside its range or NULL: NRT_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+int nrt_conv3d_pad_f32(const float *src0, int c0, const float *src1, int c1, const int *up, const float *weights,
+                       const float *packed_weights, const float *bias, float *out, int batch, const int *shape, const int *ksize,
+                       int cout, int dilation, const int *pad_before, int activation, int variant, void *stream);
+int nrt_hyperconv3d_pad_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias,
+                            float *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
+                            const int *pad_before, int activation, int variant, void *stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,12 @@ _SIGNATURES = {
     'nrt_barycenter_workspace_bytes': (_sz, [_i, _ll, _ip, _i, _ll]),
     'nrt_barycenter': (_i, [_vp, _i, _ll, _ip, _i, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'nrt_barycenter_bwd': (_i, [_vp, _vp, _vp, _i, _ll, _ip, _i, _ll, _i, _i, _vp, _vp, _sz, _vp]),
+    'nrt_global_max_workspace_bytes': (_sz, [_i, _ll, _i]),
+    'nrt_global_max_f32': (_i, [_vp, _i, _ll, _i, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_global_max_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _sz, _vp]),
+    'nrt_maxnorm_f32': (_i, [_vp, _i, _ll, _f, _f, _vp]),
+    'nrt_conv3d_pad_f32': (_i, [_vp, _i, _vp, _i, _ip, _vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _ip, _i, _i, _vp]),
+    'nrt_hyperconv3d_pad_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _ip, _i, _i, _vp]),
 }
 
 

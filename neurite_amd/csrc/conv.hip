@@ -1002,6 +1002,159 @@ int dispatch_mfma(const ConvArgs &a, const float *wpacked, int batch, hipStream_
     }
 }
 
+// ============================================================================================
+// 2x2x2 kernel, dilation 1, output of the input's size (variant 6): the implicit GEMM above with 8 taps and a halo of ONE voxel, on
+// the side the padding leaves it -- 'same' pads 0 before / 1 after (a.px = 0: the forward of design_dnn's stride-1 "strided"
+// convolution), its transpose 1 before / 0 after (a.px = 1: the input gradient, nrt_conv3d_pad_f32).  A kernel of its own, so that no
+// instantiation of conv3d_mfma changes: same 4 x 4 x 16 output tile, same LDS row layout and packed-weight order
+// ([chunk][tap][nt][lane][4], tap = (dx * 2 + dy) * 2 + dz), same epilogue; the 5 x 5 x 17 halo tile of the next 16-channel chunk is
+// fetched into registers (7 rows per thread) while the current one is on the matrix cores.
+// ============================================================================================
+template <int NT>
+__global__ __launch_bounds__(256) void conv3d_mfma_k2(ConvArgs a, const float *__restrict__ wpacked, unsigned nblk, unsigned nbx,
+                                                      unsigned nby, unsigned nbz) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const unsigned lb = nrt_xcd_block(blockIdx.x, gridDim.x);
+    if (lb >= nblk) return;
+    const int b = blockIdx.y;
+    const int bz = lb % nbz, by = (lb / nbz) % nby, bx = lb / (nbz * nby);
+    const int x0 = bx * CT_X, y0 = by * CT_Y, z0 = bz * CT_Z;
+    constexpr int HX = CT_X + 1, HY = CT_Y + 1, HZ = CT_Z + 1, NROWS = HX * HY * HZ, PF = (NROWS + 63) / 64;
+    const int Cin = a.c0 + a.c1;
+    const int nchunk = (Cin + 15) / 16;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int q4 = threadIdx.x & 3;
+
+    const float *s0 = a.src0 + (long long)b * a.X * a.Y * a.Z * a.c0;
+    const float *s1 = a.src1 ? a.src1 + (long long)b * a.X1 * a.Y1 * a.Z1 * a.c1 : nullptr;
+
+    f32x4 acc[4][NT];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+    // row r (voxel of the halo tile), float4 q4 of its 16-channel chunk; zero outside the volume and beyond Cin
+    auto load_row = [&](int r, int cbase) -> f32x4 {
+        const int rz = r % HZ, ry = (r / HZ) % HY, rx = r / (HZ * HY);
+        const int x = x0 - a.px + rx, y = y0 - a.py + ry, z = z0 - a.pz + rz;
+        f32x4 v = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        if (r < NROWS && x >= 0 && x < a.X && y >= 0 && y < a.Y && z >= 0 && z < a.Z) {
+            const int c = cbase + 4 * q4;
+            if (c < a.c0) {
+                const float *p = s0 + (((long long)x * a.Y + y) * a.Z + z) * a.c0 + c;
+                if (c + 3 < a.c0 && (a.c0 & 3) == 0) v = *(const f32x4 *)p;
+                else { for (int e = 0; e < 4; ++e) if (c + e < a.c0) v[e] = p[e]; }
+            } else if (c < Cin) {
+                const int c1 = c - a.c0;
+                const float *p = s1 + (((long long)(x / a.ux) * a.Y1 + (y / a.uy)) * a.Z1 + (z / a.uz)) * a.c1 + c1;
+                if (c1 + 3 < a.c1 && (a.c1 & 3) == 0 && (a.c0 & 3) == 0) v = *(const f32x4 *)p;
+                else { for (int e = 0; e < 4; ++e) if (c1 + e < a.c1) v[e] = p[e]; }
+            }
+        }
+        return v;
+    };
+    f32x4 stage[PF];
+#pragma unroll
+    for (int i = 0; i < PF; ++i) stage[i] = load_row((threadIdx.x >> 2) + 64 * i, 0);
+    for (int ch = 0; ch < nchunk; ++ch) {
+        __syncthreads();                                   // previous chunk fully consumed
+#pragma unroll
+        for (int i = 0; i < PF; ++i) {
+            const int r = (threadIdx.x >> 2) + 64 * i;
+            if (r < NROWS) *(f32x4 *)&lds[r * LDS_ROW + 4 * q4] = stage[i];
+        }
+        __syncthreads();
+        const f32x4 *wp = (const f32x4 *)wpacked + ((long long)ch * 8) * NT * 64 + lane;
+        f32x4 bfrag[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bfrag[nt] = wp[nt * 64];
+        if (ch + 1 < nchunk) {
+#pragma unroll
+            for (int i = 0; i < PF; ++i) stage[i] = load_row((threadIdx.x >> 2) + 64 * i, ch * 16 + 16);
+        }
+        const float *abase = &lds[((w * HY) * HZ + li) * LDS_ROW + 4 * kq];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            f32x4 bnext[NT];
+            const int tn = t + 1 < 8 ? t + 1 : t;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bnext[nt] = wp[(tn * NT + nt) * 64];
+            const int dz = t & 1, dy = (t >> 1) & 1, dx = t >> 2;
+            f32x4 av[4];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) av[mt] = *(const f32x4 *)(abase + ((dx * HY + (mt + dy)) * HZ + dz) * LDS_ROW);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt)
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][m], bfrag[nt][m], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bfrag[nt] = bnext[nt];
+        }
+    }
+    // ---- epilogue: D[row = (lane>>4)*4 + r][col = lane&15] ---------------------------------------
+    float *ob = a.out + (long long)b * a.OX * a.OY * a.OZ * a.Cout;
+    const int x = x0 + w;
+    if (x < a.OX) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int y = y0 + mt;
+            if (y >= a.OY) continue;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int co = nt * 16 + li;
+                if (co >= a.Cout) continue;
+                const float bv = a.bias ? a.bias[co] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int z = z0 + kq * 4 + r;
+                    if (z < a.OZ)
+                        ob[(((long long)x * a.OY + y) * a.OZ + z) * a.Cout + co] = activate(acc[mt][nt][r] + bv, a.act);
+                }
+            }
+        }
+    }
+}
+
+// what conv3d_mfma_k2 takes.  a.px .. a.pz are 0 or 1 here (conv_args: 'same' gives 0; nrt_conv3d_pad_f32 checks its range)
+bool k2_ok(const ConvArgs &a) {
+    if (a.kx != 2 || a.ky != 2 || a.kz != 2 || a.dil != 1) return false;
+    if (a.OX != a.X || a.OY != a.Y || a.OZ != a.Z) return false;
+    if (a.Cout > 64 || (a.c0 + a.c1) < 8) return false;
+    if (a.c1 > 0 && (a.c0 % 4)) return false;
+    if (a.fold || a.wstride) return false;
+    if ((((uintptr_t)a.src0 | (uintptr_t)a.src1) & 15) != 0) return false;        // the staging loads 16 bytes where the channels allow
+    return true;
+}
+
+int launch_k2(const ConvArgs &a, const float *wpacked, int batch, hipStream_t st) {
+    const unsigned nbx = (a.OX + CT_X - 1) / CT_X, nby = (a.OY + CT_Y - 1) / CT_Y, nbz = (a.OZ + CT_Z - 1) / CT_Z;
+    const unsigned nblk = nbx * nby * nbz;
+    const size_t shm = (size_t)(CT_X + 1) * (CT_Y + 1) * (CT_Z + 1) * LDS_ROW * sizeof(float);
+    const dim3 grid(nrt_xcd_grid(nblk), batch);
+    switch ((a.Cout + 15) / 16) {
+        case 1: hipLaunchKernelGGL((conv3d_mfma_k2<1>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz); break;
+        case 2: hipLaunchKernelGGL((conv3d_mfma_k2<2>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz); break;
+        case 3: hipLaunchKernelGGL((conv3d_mfma_k2<3>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz); break;
+        default: hipLaunchKernelGGL((conv3d_mfma_k2<4>), grid, dim3(256), shm, st, a, wpacked, nblk, nbx, nby, nbz); break;
+    }
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+// variant 0 sends a 2x2x2 layer to conv3d_mfma_k2 only where it was measured faster than conv3d_direct on the same tensors
+// (tools/conv_even_bench.py, profiles/conv_even/conv_even_bench.jsonl: 16 -> 16, 32 -> 32 and 64 -> 64 at 4 x 40^3, 4 x 80^3 and
+// 4 x 160^3, forward and input gradient: 3.8 to 27 times faster at every one of them, run-to-run spread at most 0.26).  The rule is
+// the hull of what was measured: 16 .. 64 channels on both sides, at least 4 x 40^3 output voxels; the direct kernel stays the
+// default below it (fewer channels, smaller volumes: not measured).
+bool k2_auto(const ConvArgs &a, int batch) {
+    return a.c0 + a.c1 >= 16 && a.Cout >= 16 && (long long)batch * a.OX * a.OY * a.OZ >= 4ll * 40 * 40 * 40;
+}
+
 #include "conv_up2.h"
 #include "conv_p27.h"
 
@@ -1146,6 +1299,11 @@ template <bool HYPER>
 int conv3d_dispatch(ConvArgs &a, const float *weights, const float *packed_weights, float *out, int batch, int padding_same,
                     int variant, hipStream_t st) {
     const int c0 = a.c0, c1 = a.c1, cout = a.Cout;
+    // variant 6: the 2x2x2 matrix-core arm (conv3d_mfma_k2); auto takes it where k2_auto says it was measured faster
+    if (variant == 6 || (variant == 0 && !HYPER && packed_weights && k2_ok(a) && k2_auto(a, batch))) {
+        if (HYPER || !packed_weights || !k2_ok(a)) return NRT_ERR_UNSUPPORTED;
+        return launch_k2(a, packed_weights, batch, st);
+    }
     const bool can_mfma = mfma_ok(a, padding_same) && packed_weights != nullptr;
     if (HYPER) {                                                 // floats per entry of the array the chosen kernel reads
         const int k3[3] = {a.kx, a.ky, a.kz};
@@ -1231,6 +1389,53 @@ extern "C" int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int 
     return conv3d_dispatch<false>(a, weights, packed_weights, out, batch, padding_same, variant, nrt_stream(stream));
 }
 
+namespace {
+
+// explicit zero padding before (the output keeps the input's shape, so (k - 1) * dilation - pad_before follows).  Returns 1 where
+// pad_before is what 'same' pads anyway, 0 where it differs (a.px .. a.pz are then replaced), or an error code.
+int conv_pad_before(ConvArgs &a, const int *pad_before) {
+    if (!pad_before) return NRT_ERR_INVALID_ARG;
+    const int k[3] = {a.kx, a.ky, a.kz};
+    for (int d = 0; d < 3; ++d)
+        if (pad_before[d] < 0 || pad_before[d] > (k[d] - 1) * a.dil) return NRT_ERR_INVALID_ARG;
+    if (pad_before[0] == a.px && pad_before[1] == a.py && pad_before[2] == a.pz) return 1;
+    a.px = pad_before[0]; a.py = pad_before[1]; a.pz = pad_before[2];
+    return 0;
+}
+
+template <bool HYPER>
+int conv3d_direct_launch(const ConvArgs &a, const float *weights, int batch, hipStream_t st) {
+    const long long nvox = (long long)a.OX * a.OY * a.OZ;
+    unsigned blocks = (unsigned)((nvox + 255) / 256);
+    if (blocks > 256u * 32u) blocks = 256u * 32u;
+    hipLaunchKernelGGL((conv3d_direct<HYPER>), dim3(blocks, batch), dim3(256), 0, st, a, weights);
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+}  // namespace
+
+extern "C" int nrt_conv3d_pad_f32(const float *src0, int c0, const float *src1, int c1, const int *up, const float *weights,
+                                  const float *packed_weights, const float *bias, float *out, int batch, const int *shape,
+                                  const int *ksize, int cout, int dilation, const int *pad_before, int activation, int variant,
+                                  void *stream) {
+    ConvArgs a;
+    int rc = conv_args(a, src0, c0, src1, c1, up, bias, out, shape, ksize, cout, dilation, 1, activation);
+    if (rc != NRT_OK) return rc;
+    if (batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
+    if (activation < ACT_NONE || activation > ACT_LAST_FUSED) return NRT_ERR_INVALID_ARG;
+    rc = conv_pad_before(a, pad_before);
+    if (rc < 0) return rc;
+    if (rc == 1) return conv3d_dispatch<false>(a, weights, packed_weights, out, batch, 1, variant, nrt_stream(stream));
+    if (variant == 6 || (variant == 0 && packed_weights && k2_ok(a) && k2_auto(a, batch))) {
+        if (!packed_weights || !k2_ok(a)) return NRT_ERR_UNSUPPORTED;
+        return launch_k2(a, packed_weights, batch, nrt_stream(stream));
+    }
+    if (variant != 0 && variant != 1) return NRT_ERR_UNSUPPORTED;            // the other tiled kernels centre their halo
+    if (!weights) return NRT_ERR_INVALID_ARG;
+    return conv3d_direct_launch<false>(a, weights, batch, nrt_stream(stream));
+}
+
 // ---- hyper-convolution: one weight set and one bias per batch entry (neurite/tf/layers.py:2515-2612) -----------------------------------
 extern "C" int nrt_hyperconv3d_pack_weights_f32(const float *weights, int batch, const int *ksize, int cin, int cout, int transpose_flip,
                                                 float *packed, void *stream) {
@@ -1269,6 +1474,26 @@ extern "C" int nrt_hyperconv3d_f32(const float *src, int cin, const float *weigh
     if (variant != 0 && variant != 1 && variant != 2 && variant != 5) return NRT_ERR_INVALID_ARG;
     a.bstride = bias ? cout : 0;
     return conv3d_dispatch<true>(a, weights, packed_weights, out, batch, padding_same, variant, nrt_stream(stream));
+}
+
+extern "C" int nrt_hyperconv3d_pad_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias,
+                                       float *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
+                                       const int *pad_before, int activation, int variant, void *stream) {
+    ConvArgs a;
+    int rc = conv_args(a, src, cin, nullptr, 0, nullptr, bias, out, shape, ksize, cout, dilation, 1, activation);
+    if (rc != NRT_OK) return rc;
+    if (batch < 1 || batch > 65535) return NRT_ERR_INVALID_ARG;
+    if (!weights && !packed_weights) return NRT_ERR_INVALID_ARG;
+    if (activation < ACT_NONE || activation > ACT_LAST_FUSED) return NRT_ERR_INVALID_ARG;
+    if (variant != 0 && variant != 1 && variant != 2 && variant != 5) return NRT_ERR_INVALID_ARG;
+    a.bstride = bias ? cout : 0;
+    rc = conv_pad_before(a, pad_before);
+    if (rc < 0) return rc;
+    if (rc == 1) return conv3d_dispatch<true>(a, weights, packed_weights, out, batch, 1, variant, nrt_stream(stream));
+    if (variant != 0 && variant != 1) return NRT_ERR_UNSUPPORTED;
+    if (!weights) return NRT_ERR_INVALID_ARG;
+    a.wstride = (long long)a.kx * a.ky * a.kz * cin * cout;
+    return conv3d_direct_launch<true>(a, weights, batch, nrt_stream(stream));
 }
 
 // the single-channel first layer + the 2x2x2 max-pooling behind it (models.py:1378-1388, 1436-1438) in one kernel: `out` as nrt_conv3d_f32

@@ -156,6 +156,7 @@ struct WgArgs {
                              // channels), blockIdx.z = parity group P, its 8 taps are e = p + t per axis (t in {0,1}), and
                              // dw is [8 groups][8 taps][Cin][Cout]
     int pe;                  // host side: launch the per-entry instantiation (PE below)
+    int t0;                  // first tap of this launch (the general kernel: 28 taps per launch)
 };
 
 constexpr int WT_X = 4, WT_Y = 4, WT_Z = 8;     // voxel tile: 128 voxels = 32 k-steps of 4
@@ -176,8 +177,11 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
     constexpr int CC = 16 * NA, CO = 16 * NB;
     constexpr int RSA = (CC % 32 == 0) ? CC + 16 : CC;          // row strides: 16 mod 32 floats
     constexpr int RSB = (CO % 32 == 0) ? CO + 16 : CO;
-    const int hx = KF ? HALO : (a.kx > 1 ? a.dil : 0), hy = KF ? HALO : (a.ky > 1 ? a.dil : 0), hz = KF ? HALO : (a.kz > 1 ? a.dil : 0);
-    const int HX = WT_X + 2 * hx, HY = WT_Y + 2 * hy, HZ = WT_Z + 2 * hz;
+    // zero padding before = what the forward pads, floor((k - 1) dil / 2); the halo spans (k - 1) dil (odd k: the same on both sides)
+    const int hx = KF ? HALO : ((a.kx - 1) * a.dil) / 2, hy = KF ? HALO : ((a.ky - 1) * a.dil) / 2, hz = KF ? HALO : ((a.kz - 1) * a.dil) / 2;
+    const int HX = WT_X + (KF ? 2 * HALO : (a.kx - 1) * a.dil), HY = WT_Y + (KF ? 2 * HALO : (a.ky - 1) * a.dil),
+              HZ = WT_Z + (KF ? 2 * HALO : (a.kz - 1) * a.dil);
+    const int tb = KF ? 0 : a.t0;                               // first tap of this launch (kernels of more than 28 taps take several)
     const int nrowsA = HX * HY * HZ;
     float *la = lds;                                            // [nrowsA][RSA]
     float *lb = lds + nrowsA * RSA;                             // [128][RSB]
@@ -202,7 +206,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
     int toff[WG_MAXT];
 #pragma unroll
     for (int i = 0; i < WG_MAXT; ++i) {
-        const int t = min(wv + 4 * i, ntap - 1);
+        const int t = min(tb + wv + 4 * i, ntap - 1);
         const int kz = K3 ? 3 : K1 ? 1 : a.kz, ky = K3 ? 3 : K1 ? 1 : a.ky, dil = KF ? 1 : a.dil;
         int dz = t % kz, dy = (t / kz) % ky, dx = t / (kz * ky);
         if (FOLD) { dx = ((P >> 2) & 1) + ((t >> 2) & 1); dy = ((P >> 1) & 1) + ((t >> 1) & 1); dz = (P & 1) + (t & 1); }
@@ -446,7 +450,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
             for (int nb = 0; nb < NB; ++nb) bf[nb] = lb[vrow * RSB + nb * 16 + l15];
 #pragma unroll
             for (int i = 0; i < WG_MAXT; ++i) {
-                if (wv + 4 * i < ntap) {
+                if (tb + wv + 4 * i < ntap) {
 #pragma unroll
                     for (int na = 0; na < NA; ++na) {
                         const float af = la[(arow + toff[i]) * RSA + na * 16 + l15];
@@ -462,7 +466,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad(WgArgs a) {
     float *dwb = PE ? a.dw + (long long)bpe * ntap * a.Cin * a.Cout : a.dw;      // (the im2col form: ntap = 1, Cin = 27)
 #pragma unroll
     for (int i = 0; i < WG_MAXT; ++i) {
-        const int t = K1 ? 0 : wv + 4 * i;
+        const int t = K1 ? 0 : tb + wv + 4 * i;
         if (K1 ? i == 0 : t < ntap) {
 #pragma unroll
             for (int na = 0; na < NA; ++na)
@@ -799,8 +803,8 @@ template <int NA, int NB>
 int launch_wgrad(WgArgs &a, hipStream_t st) {
     constexpr int CC = 16 * NA, CO = 16 * NB;
     constexpr int RSA = (CC % 32 == 0) ? CC + 16 : CC, RSB = (CO % 32 == 0) ? CO + 16 : CO;
-    const int hx = a.kx > 1 ? a.dil : 0, hy = a.ky > 1 ? a.dil : 0, hz = a.kz > 1 ? a.dil : 0;
-    const size_t lds = ((size_t)(WT_X + 2 * hx) * (WT_Y + 2 * hy) * (WT_Z + 2 * hz) * RSA + 128 * RSB) * sizeof(float);
+    const int hx = (a.kx - 1) * a.dil, hy = (a.ky - 1) * a.dil, hz = (a.kz - 1) * a.dil;       // halo, both sides together
+    const size_t lds = ((size_t)(WT_X + hx) * (WT_Y + hy) * (WT_Z + hz) * RSA + 128 * RSB) * sizeof(float);
     if (lds > 160 * 1024) return NRT_ERR_UNSUPPORTED;
     a.ncic = (a.Cin + CC - 1) / CC;
     a.ncoc = (a.Cout + CO - 1) / CO;
@@ -853,6 +857,22 @@ int launch_wgrad(WgArgs &a, hipStream_t st) {
 #undef NRT_WG_LAUNCH
     NRT_CHECK_LAUNCH();
     return NRT_OK;
+}
+
+// a wave holds 7 taps, a launch 28: kernels with more (4x4x4) take one launch per 28 taps, the bias gradient with the first
+template <int NA, int NB>
+int launch_wgrad_taps(WgArgs &a, hipStream_t st) {
+    const int ntap = a.kx * a.ky * a.kz;
+    float *db = a.db;
+    int rc = NRT_OK;
+    for (int t0 = 0; t0 < ntap && rc == NRT_OK; t0 += 28) {
+        a.t0 = t0;
+        rc = launch_wgrad<NA, NB>(a, st);
+        a.db = nullptr;
+    }
+    a.db = db;
+    a.t0 = 0;
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -979,7 +999,7 @@ extern "C" int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, 
     if (c1 > 0 && (!x_lo || !up)) return NRT_ERR_INVALID_ARG;
     for (int d = 0; d < 3; ++d) {
         if (shape[d] < 1 || ksize[d] < 1) return NRT_ERR_INVALID_ARG;
-        if (ksize[d] != 1 && ksize[d] != 3) return NRT_ERR_UNSUPPORTED;           // the kernel sizes of the conv stacks
+        if (ksize[d] > 4) return NRT_ERR_UNSUPPORTED;                                 // the kernel sizes of the conv stacks: 1 .. 4
         if (c1 > 0 && (up[d] < 1 || shape[d] % up[d])) return NRT_ERR_INVALID_ARG;
     }
     if (dilation > 2) return NRT_ERR_UNSUPPORTED;
@@ -993,7 +1013,7 @@ extern "C" int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, 
     a.kx = ksize[0]; a.ky = ksize[1]; a.kz = ksize[2]; a.dil = dilation;
     a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
     a.im2col = 0;
-    a.dps = cout; a.fold = 0; a.pe = 0;
+    a.dps = cout; a.fold = 0; a.pe = 0; a.t0 = 0;
     if (cin == 1 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3 && dilation == 1 && cout % 16 == 0 && cout <= 64 &&
         (long long)shape[0] * shape[1] * shape[2] < (1ll << 31)) {
         // the single-channel first layer: gathered straight from the volume (conv3d_c1_wgrad)
@@ -1032,9 +1052,9 @@ extern "C" int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, 
     // dilated kernels have larger halo tiles: shrink the cin chunk until the tiles fit the LDS
     for (; na >= 1; --na) {
         int rc;
-        if (na == 1) rc = nb == 1 ? launch_wgrad<1, 1>(a, st) : launch_wgrad<1, 2>(a, st);
-        else if (na == 2) rc = nb == 1 ? launch_wgrad<2, 1>(a, st) : launch_wgrad<2, 2>(a, st);
-        else rc = nb == 1 ? launch_wgrad<3, 1>(a, st) : launch_wgrad<3, 2>(a, st);
+        if (na == 1) rc = nb == 1 ? launch_wgrad_taps<1, 1>(a, st) : launch_wgrad_taps<1, 2>(a, st);
+        else if (na == 2) rc = nb == 1 ? launch_wgrad_taps<2, 1>(a, st) : launch_wgrad_taps<2, 2>(a, st);
+        else rc = nb == 1 ? launch_wgrad_taps<3, 1>(a, st) : launch_wgrad_taps<3, 2>(a, st);
         if (rc != NRT_ERR_UNSUPPORTED) return rc;
     }
     return NRT_ERR_UNSUPPORTED;
@@ -1054,7 +1074,7 @@ extern "C" int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, 
     if (batch < 1 || batch > 65535 || cin < 1 || cout < 1 || dilation < 1) return NRT_ERR_INVALID_ARG;
     for (int d = 0; d < 3; ++d) {
         if (shape[d] < 1 || ksize[d] < 1) return NRT_ERR_INVALID_ARG;
-        if (ksize[d] != 1 && ksize[d] != 3) return NRT_ERR_UNSUPPORTED;
+        if (ksize[d] > 4) return NRT_ERR_UNSUPPORTED;                                 // the kernel sizes of the conv stacks: 1 .. 4
     }
     if (dilation > 2) return NRT_ERR_UNSUPPORTED;
     WgArgs a;
@@ -1063,7 +1083,7 @@ extern "C" int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, 
     a.B = batch; a.X = shape[0]; a.Y = shape[1]; a.Z = shape[2]; a.Cin = cin; a.Cout = cout;
     a.kx = ksize[0]; a.ky = ksize[1]; a.kz = ksize[2]; a.dil = dilation;
     a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
-    a.im2col = 0; a.dps = cout; a.fold = 0; a.pe = 1;
+    a.im2col = 0; a.dps = cout; a.fold = 0; a.pe = 1; a.t0 = 0;
     if (cin == 1 && ksize[0] == 3 && ksize[1] == 3 && ksize[2] == 3) {
         a.im2col = 1; a.Cin = 27; a.kx = a.ky = a.kz = 1;        // [27 taps][1][cout] and [1 tap][27][cout] are the same memory
         cin = 27;
@@ -1073,9 +1093,9 @@ extern "C" int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, 
     const int nb = cout <= 16 ? 1 : 2;
     for (; na >= 1; --na) {                                      // dilated kernels: shrink the cin chunk until the tiles fit the LDS
         int rc;
-        if (na == 1) rc = nb == 1 ? launch_wgrad<1, 1>(a, st) : launch_wgrad<1, 2>(a, st);
-        else if (na == 2) rc = nb == 1 ? launch_wgrad<2, 1>(a, st) : launch_wgrad<2, 2>(a, st);
-        else rc = nb == 1 ? launch_wgrad<3, 1>(a, st) : launch_wgrad<3, 2>(a, st);
+        if (na == 1) rc = nb == 1 ? launch_wgrad_taps<1, 1>(a, st) : launch_wgrad_taps<1, 2>(a, st);
+        else if (na == 2) rc = nb == 1 ? launch_wgrad_taps<2, 1>(a, st) : launch_wgrad_taps<2, 2>(a, st);
+        else rc = nb == 1 ? launch_wgrad_taps<3, 1>(a, st) : launch_wgrad_taps<3, 2>(a, st);
         if (rc != NRT_ERR_UNSUPPORTED) return rc;
     }
     return NRT_ERR_UNSUPPORTED;
@@ -1095,7 +1115,7 @@ extern "C" int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre
     a.kx = a.ky = a.kz = 3; a.dil = 1;
     a.ntx = (a.X + WT_X - 1) / WT_X; a.nty = (a.Y + WT_Y - 1) / WT_Y; a.ntz = (a.Z + WT_Z - 1) / WT_Z;
     a.im2col = 0;
-    a.dps = 8 * group; a.fold = 1; a.pe = 0;
+    a.dps = 8 * group; a.fold = 1; a.pe = 0; a.t0 = 0;
     hipStream_t st = nrt_stream(stream);
     // all 8 parity groups per block when the staging's assumptions hold (quad-aligned channels, 32-bit offsets, 24-bit strides)
     const bool foldall = cin % 4 == 0 && group % 4 == 0 && (long long)a.X * a.Y * a.Z * cin < (1ll << 31) &&

@@ -35,7 +35,7 @@ __all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LocallyConnected3D', 'VecInt
            'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise',
            'HyperConv', 'HyperConv2D', 'HyperConv3D', 'HyperConvFromDense', 'HyperConv2DFromDense', 'HyperConv3DFromDense',
            'HyperDense', 'HyperDenseFromDense', 'LocalBias', 'LocalLinear', 'LocalCrossLinear', 'LocalParamLayer',
-           'LocalParamWithInput', 'MeanStream', 'CovStream', 'SampleNormalLogVar']
+           'LocalParamWithInput', 'MeanStream', 'CovStream', 'SampleNormalLogVar', 'Negate', 'RescaleValues']
 
 
 class _Layer(nn.Module):
@@ -74,6 +74,47 @@ class _Layer(nn.Module):
     def forward(self, inputs, **kwargs):
         self._maybe_build(inputs)
         return self.call(inputs, **kwargs)
+
+
+class Negate(_Layer):
+    """The negative of the input (neurite/tf/layers.py:49-64); forward and gradient on the element-wise kernel."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+    def call(self, x):
+        from .models import _scale_values
+        if x.dtype != torch.float32:                  # refused before the device is looked at
+            raise NotImplementedError('%s runs on the float32 element-wise kernel, got %s' % (self.__class__.__name__, x.dtype))
+        _lib.require_device(x)
+        return _scale_values(x, -1.0)
+
+
+class RescaleValues(_Layer):
+    """Rescale data values (e.g. intensities) by a fixed factor (neurite/tf/layers.py:67-88); forward and gradient on the
+    element-wise kernel."""
+
+    def __init__(self, resize, **kwargs):
+        self.resize = resize
+        super().__init__(**kwargs)
+
+    def get_config(self):
+        config = super().get_config().copy()
+        config.update({'resize': self.resize})
+        return config
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+    def call(self, x):
+        from .models import _scale_values
+        if x.dtype != torch.float32:                  # refused before the device is looked at
+            raise NotImplementedError('%s runs on the float32 element-wise kernel, got %s' % (self.__class__.__name__, x.dtype))
+        _lib.require_device(x)
+        return _scale_values(x, self.resize)
 
 
 class Resize(_Layer):
@@ -1055,9 +1096,17 @@ def _hyperconv_run(x, kernel, bias, ksize3, dilation, same, kact, flipped=False)
         else:
             # the direct and single-input-channel kernels read the Keras layout (one batched re-layout for the input gradient)
             weights = kernel.flip(1, 2, 3).transpose(4, 5).contiguous() if flipped else kernel
-        rc = lib.nrt_hyperconv3d_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
-                                     _lib.ints(S), _lib.ints(ksize3), co, int(dilation), int(same), int(kact), 0,
-                                     _lib.stream_ptr(dev))
+        if flipped:
+            # the transpose of a 'same' convolution pads (k - 1) * dilation - (k - 1) * dilation // 2 before (even kernels: one more
+            # than 'same' does)
+            from .models import _dgrad_pad_before
+            rc = lib.nrt_hyperconv3d_pad_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
+                                             _lib.ints(S), _lib.ints(ksize3), co, int(dilation),
+                                             _lib.ints(_dgrad_pad_before(ksize3, dilation)), int(kact), 0, _lib.stream_ptr(dev))
+        else:
+            rc = lib.nrt_hyperconv3d_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
+                                         _lib.ints(S), _lib.ints(ksize3), co, int(dilation), int(same), int(kact), 0,
+                                         _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_hyperconv3d_f32')
     return out
 

@@ -48,7 +48,7 @@ from . import _lib
 from . import layers
 from . import utils
 
-__all__ = ['unet', 'conv_enc', 'conv_dec', 'conv_block', 'ConvNet', 'labels_to_image', 'labels_to_image_new', 'SynthStrip', 'add_prior', 'dilation_net', 'load', 'load_config', 'ae', 'single_ae']
+__all__ = ['unet', 'conv_enc', 'conv_dec', 'conv_block', 'ConvNet', 'labels_to_image', 'labels_to_image_new', 'SynthStrip', 'add_prior', 'dilation_net', 'load', 'load_config', 'ae', 'single_ae', 'design_dnn', 'EncoderNet']
 
 # element-wise activations, codes of include/neurite_amd.h (nrt_activation); definitions follow tf.keras.activations -- the reference
 # hands the string straight to Keras (neurite/tf/models.py:1346, 1429, 1507, 1588)
@@ -226,6 +226,7 @@ class _Conv(nn.Module):
         self._packed_bf16 = None                     # bf16 weights in v_mfma_f32_16x16x32_bf16 operand order (run_bf16)
         self._packed_bf16_version = None
         self.fold_backward = True                    # decoder form: differentiate the up-sampled channels on the low-resolution grid
+        self.max_norm = None                         # Keras kernel_constraint=MaxNorm(max_norm, axis=0); ConvNet.apply_constraints
 
     def invalidate_packed(self):
         """forget the MFMA-packed copy of the kernel.  The cache key below sees in-place writes through the Parameter
@@ -471,13 +472,18 @@ class _Dense(nn.Module):
         self.layer_name = name
         self.cin, self.cout = int(cin), int(cout)
         self.activation = activation
-        self.act = _act_code(activation)
+        # the softmax is not element-wise: a linear Dense, then the softmax kernel over the units
+        self.post_softmax = activation == 'softmax'
+        self.act = 0 if self.post_softmax else _act_code(activation)
         limit = math.sqrt(6.0 / (self.cin + self.cout))
         self.kernel = nn.Parameter((torch.rand(self.cin, self.cout) * 2 - 1) * limit)
         self.bias = nn.Parameter(torch.zeros(self.cout))
 
     def forward(self, x, variant=0):
-        return _dense(x, self.kernel, self.bias, self.act, variant)
+        y = _dense(x, self.kernel, self.bias, self.act, variant)
+        if self.post_softmax:
+            return _softmax_with_grad(y) if (torch.is_grad_enabled() and y.requires_grad) else _softmax(y)
+        return y
 
 
 class _LocalBiasWeight(nn.Module):
@@ -579,6 +585,101 @@ def _elementwise(a, b=None, scale=None, shift=None, act=0, mul=False):
                                         a.numel(), a.shape[-1], int(act), _lib.stream_ptr(dev))
     _lib.check(rc, 'nrt_add_act_affine_f32')
     return y
+
+
+def _global_max_workspace(dev, B, V, C):
+    n = _lib.lib().nrt_global_max_workspace_bytes(B, V, C)
+    if not n:
+        raise NotImplementedError('global max of a [%d, %d, %d] tensor: the kernels index elements with 32 bits' % (B, V, C))
+    return _lib.workspace(dev, n), n
+
+
+class _GlobalMaxFn(torch.autograd.Function):
+    """max over everything between the batch axis and the channels (per_channel: Keras GlobalMaxPooling{1,2,3}D, [B, *S, C] ->
+    [B, C]) or over everything but the batch axis (design_dnn's flatten-then-max lambda, -> [B, 1]), with tf.reduce_max's gradient:
+    the positions that attain the max share it (csrc/globalmax.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, per_channel):
+        lib = _lib.lib()
+        dev = _lib.require_device(x)
+        x = x.contiguous()
+        B = x.shape[0]
+        C = x.shape[-1] if per_channel else 1
+        V = x.numel() // (B * C)
+        y = torch.empty((B, C), dtype=torch.float32, device=dev)
+        count = torch.empty((B, C), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ws, n = _global_max_workspace(dev, B, V, C)
+            rc = lib.nrt_global_max_f32(_p32(x), B, V, C, _p32(y), _lib.ptr(count), _lib.ptr(ws), n, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_global_max_f32')
+        ctx.save_for_backward(x, y, count)
+        ctx.dims = (B, V, C)
+        ctx.mark_non_differentiable(count)
+        return y, count
+
+    @staticmethod
+    def backward(ctx, g, _gcount):
+        x, y, count = ctx.saved_tensors
+        B, V, C = ctx.dims
+        lib = _lib.lib()
+        dev = g.device
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            ws, n = _global_max_workspace(dev, B, V, C)
+            rc = lib.nrt_global_max_bwd_f32(_p32(x), _p32(y), _lib.ptr(count), _p32(g), B, V, C, _p32(gx), _lib.ptr(ws), n,
+                                            _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_global_max_bwd_f32')
+        return gx, None
+
+
+def _global_max(x, per_channel=True, return_count=False):
+    if x.dtype != torch.float32:
+        raise NotImplementedError('the global max kernels are float32')
+    y, count = _GlobalMaxFn.apply(x, bool(per_channel))
+    return (y, count) if return_count else y
+
+
+class _ScaleFn(torch.autograd.Function):
+    """y = x * factor (layers.RescaleValues, layers.Negate) on the element-wise kernel; the gradient is the same call"""
+
+    @staticmethod
+    def _apply(x, factor):
+        C = x.shape[-1]
+        scale = torch.full((C,), float(factor), dtype=torch.float32, device=x.device)
+        shift = torch.zeros(C, dtype=torch.float32, device=x.device)
+        return _elementwise(x, scale=scale, shift=shift)
+
+    @staticmethod
+    def forward(ctx, x, factor):
+        ctx.factor = float(factor)
+        with torch.no_grad():
+            return _ScaleFn._apply(x, factor)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ScaleFn._apply(g, ctx.factor), None
+
+
+def _scale_values(x, factor):
+    if x.dtype != torch.float32:
+        raise NotImplementedError('the element-wise kernel behind RescaleValues / Negate is float32 here')
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _ScaleFn.apply(x, factor)
+    return _ScaleFn._apply(x, factor)
+
+
+def _maxnorm(w, max_value, eps=1e-7):
+    """Keras MaxNorm(max_value, axis=0) in place on a contiguous float32 weight tensor"""
+    lib = _lib.lib()
+    dev = _lib.require_device(w)
+    if not w.is_contiguous():
+        raise ValueError('a constrained weight must be contiguous')
+    with torch.cuda.device(dev):
+        rc = lib.nrt_maxnorm_f32(_p32(w), int(w.shape[0]), w.numel() // int(w.shape[0]), float(max_value), float(eps),
+                                 _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_maxnorm_f32')
 
 
 def _maxpool(x, pool3, padding):
@@ -752,12 +853,21 @@ def _upsample_sum(g, c_off, c, lo_shape, up3):
     return d
 
 
-def _conv_dgrad(dpre, wpart, ksize3, dilation):
-    """grad wrt the conv input: conv(dpre, weights flipped in space and transposed in the channel axes) on the forward kernel."""
+def _dgrad_pad_before(ksize3, dilation):
+    """zero padding before of the transpose of a 'same' convolution: the forward pads p = (k - 1) * dilation // 2 before and
+    (k - 1) * dilation - p after, so its transpose pads (k - 1) * dilation - p before.  Odd kernels: the same p; even kernels: one more."""
+    return [(k - 1) * int(dilation) - ((k - 1) * int(dilation)) // 2 for k in ksize3]
+
+
+def _conv_dgrad(dpre, wpart, ksize3, dilation, variant=0):
+    """grad wrt the conv input: conv(dpre, weights flipped in space and transposed in the channel axes) on the forward kernel, padded
+    as the transpose is (nrt_conv3d_pad_f32)."""
     lib = _lib.lib()
     dev = dpre.device
     cout, cpart = wpart.shape[-1], wpart.shape[-2]
     wt = wpart.flip(0, 1, 2).transpose(3, 4).contiguous()             # [k, k, k, cout, cpart]; a few KB of glue
+    if variant == 6 and not (cout >= 8 and cpart <= 64):
+        variant = 0                  # the transposed layer swaps the channel counts: outside the 2x2x2 arm's, it is not forced
     if tuple(ksize3) == (1, 1, 1) and cpart % 4 == 0 and cpart <= 64:
         # 1x1x1 (the likelihood layer): a per-voxel matrix product on the streaming kernel, not on the halo-tile convolution
         dpre = dpre.contiguous()
@@ -774,9 +884,10 @@ def _conv_dgrad(dpre, wpart, ksize3, dilation):
     with torch.cuda.device(dev):
         rc = lib.nrt_conv3d_pack_weights_f32(_p32(wt), _lib.ints(ksize3), cout, cpart, _p32(packed), _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-        rc = lib.nrt_conv3d_f32(_p32(dpre), cout, None, 0, None, _p32(wt), _p32(packed), None, _p32(out), B,
-                                _lib.ints(S), _lib.ints(ksize3), cpart, int(dilation), 1, 0, 0, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv3d_f32 (dgrad)')
+        rc = lib.nrt_conv3d_pad_f32(_p32(dpre), cout, None, 0, None, _p32(wt), _p32(packed), None, _p32(out), B,
+                                    _lib.ints(S), _lib.ints(ksize3), cpart, int(dilation),
+                                    _lib.ints(_dgrad_pad_before(ksize3, dilation)), 0, int(variant), _lib.stream_ptr(dev))
+    _lib.check(rc, 'nrt_conv3d_pad_f32 (dgrad)')
     return out
 
 
@@ -879,6 +990,7 @@ class _ConvFn(torch.autograd.Function):
             else:
                 out = mod._run(x, lo, up, variant)
         ctx.mod, ctx.up = mod, up
+        ctx.dgrad_variant = 6 if variant == 6 else 0          # a forced 2x2x2 matrix-core arm is forced in the input gradient too
         ctx.save_for_backward(x, lo, kernel, out)
         return out
 
@@ -944,14 +1056,14 @@ class _ConvFn(torch.autograd.Function):
         k5 = kernel.detach()
         if lo is not None and need_x and need_lo and mod.cin <= 64:
             # one dgrad for both sources of the fused loader (dpre is staged once, three N-tiles per A fragment)
-            full = _conv_dgrad(dpre, k5, mod.ksize3, mod.dilation)
+            full = _conv_dgrad(dpre, k5, mod.ksize3, mod.dilation, ctx.dgrad_variant)
             dx = full[..., :c0]
             dlo = _upsample_sum(full, c0, mod.cin - c0, list(lo.shape[1:4]), up)
         else:
             if need_x:
-                dx = _conv_dgrad(dpre, k5[..., :c0, :], mod.ksize3, mod.dilation)
+                dx = _conv_dgrad(dpre, k5[..., :c0, :], mod.ksize3, mod.dilation, ctx.dgrad_variant)
             if lo is not None and need_lo:
-                full = _conv_dgrad(dpre, k5[..., c0:, :], mod.ksize3, mod.dilation)
+                full = _conv_dgrad(dpre, k5[..., c0:, :], mod.ksize3, mod.dilation, ctx.dgrad_variant)
                 dlo = _upsample_sum(full, 0, full.shape[-1], list(lo.shape[1:4]), up)
         return dx, dlo, dw if need_w else None, db if need_b else None, None, None, None, None
 
@@ -1238,6 +1350,9 @@ class _SoftmaxFn(torch.autograd.Function):
 
 # the op kinds of the auto-encoder bottleneck (single_ae); float32 only
 _AE_KINDS = ('flatten', 'reshape', 'dense', 'resize', 'local_bias', 'sample', 'identity', 'lambda')
+# the layers design_dnn / EncoderNet add: GlobalMaxPooling{1,2,3}D, the flatten-then-max lambda, layers.RescaleValues and the plain
+# (element-wise) Dropout; float32 only, like the auto-encoder kinds
+_CLS_KINDS = ('global_max', 'global_max_all', 'rescale', 'dropout_ew')
 
 
 class _PendingConv:
@@ -1265,8 +1380,10 @@ class ConvNet(nn.Module):
             self.layers_by_name[k] = m
         self.layer_names = [op['name'] for op in ops]
         self._flat = {op['name']: bool(op.get('flat')) for op in ops}      # layers whose Keras tensor is [B, E]
+        self._keras_shape = {op['name']: tuple(op['keras_shape']) for op in ops if op.get('keras_shape')}   # any other rank
+        self.last_dropout_masks = {}                # {element-wise Dropout layer: the mask / (1 - rate) of the last training forward}
         self.output_shape = ops[-1].get('shape') if ops else None
-        self.conv_variant = 0                       # 0 auto, 1 direct, 2 MFMA (tests / tuning); float32 only, bf16 ignores it
+        self.conv_variant = 0                       # 0 auto, 1 direct, 2 MFMA, 6 the 2x2x2 MFMA arm (tests / tuning); float32 only, bf16 ignores it
         self.fold_head = True                       # inference: last decoder convolution + likelihood + soft-max as ONE kernel where it applies
         self.dense_variant = 0                      # 0 auto, 1 reduce arm, 2 expand arm of csrc/dense.hip (tests / tuning)
         self.last_draws = {}                        # {sampling layer: the N(0, 1) noise of the last forward}
@@ -1316,7 +1433,7 @@ class ConvNet(nn.Module):
             if name in self.layers_by_name:
                 m = self.layers_by_name[name]
                 if isinstance(m, _Conv):
-                    out += [(name + '/kernel', m.kernel, self.ndims), (name + '/bias', m.bias, None)]
+                    out += [(name + '/kernel', m.kernel, getattr(m, 'keras_nd', self.ndims)), (name + '/bias', m.bias, None)]
                 elif isinstance(m, _BatchNorm):
                     out += [(name + '/gamma', m.gamma, None), (name + '/beta', m.beta, None),
                             (name + '/moving_mean', m.moving_mean, None), (name + '/moving_variance', m.moving_variance, None)]
@@ -1353,6 +1470,19 @@ class ConvNet(nn.Module):
                 t.copy_(torch.from_numpy(w))
         for m in self.layers_by_name.values():
             if isinstance(m, _Conv):
+                m.invalidate_packed()
+
+    def apply_constraints(self):
+        """Apply the kernel constraints the builder attached (design_dnn(conv_maxnorm=m): MaxNorm(m, axis=0) on every convolution,
+        nrt_maxnorm_f32 in place).  Call it after `optimizer.step()`: Keras' optimizers apply a variable's constraint themselves,
+        torch's do not know about it.  Launches only, so it can be captured in the training step's graph; a no-op on a network
+        without constraints.  The packed copies of a constrained kernel are dropped as after any weight write."""
+        for name in self.layer_names:
+            m = self.layers_by_name[name] if name in self.layers_by_name else None
+            if isinstance(m, _Conv) and m.max_norm:
+                # Keras' axis 0 is the first kernel axis of the Conv{N}D layer: behind the unit axes a 1-D / 2-D kernel is lifted by
+                with torch.no_grad():
+                    _maxnorm(m.kernel.data.view(m.kernel.shape[3 - getattr(m, 'keras_nd', self.ndims):]), m.max_norm)
                 m.invalidate_packed()
 
     def _weights_by_layer(self):
@@ -1489,6 +1619,8 @@ class ConvNet(nn.Module):
 
         def shape_of(op):
             sp, c = op['shape']
+            if op.get('keras_shape'):
+                return [None] + [int(v) for v in op['keras_shape']]
             if op.get('flat'):
                 return [None, int(c)]
             return [None] + [int(v) for v in sp[3 - nd:]] + [int(c)]
@@ -1505,10 +1637,13 @@ class ConvNet(nn.Module):
                 emit(name, 'Concatenate', {'axis': -1}, op['src'], shape_of(op))
             elif kind in ('conv', 'likelihood'):
                 m = self.layers_by_name[name]
-                cfg = {'filters': m.cout, 'kernel_size': [int(k) for k in m.ksize3[3 - nd:]], 'strides': [1] * nd,
-                       'padding': getattr(m, 'keras_padding', m.padding), 'dilation_rate': [m.dilation] * nd,
+                cnd = getattr(m, 'keras_nd', nd)                      # (design_dnn ends a 3-D network in a Conv1D)
+                cfg = {'filters': m.cout, 'kernel_size': [int(k) for k in m.ksize3[3 - cnd:]], 'strides': [1] * cnd,
+                       'padding': getattr(m, 'keras_padding', m.padding), 'dilation_rate': [m.dilation] * cnd,
                        'activation': m.activation if m.activation is not None else 'linear', 'use_bias': True}
-                emit(name, 'Conv%dD' % nd, cfg, [op['merge'] if op.get('lo') else op['src']], shape_of(op))
+                if m.max_norm:
+                    cfg['kernel_constraint'] = {'class': 'MaxNorm', 'max_value': m.max_norm, 'axis': 0}
+                emit(name, 'Conv%dD' % cnd, cfg, [op['merge'] if op.get('lo') else op['src']], shape_of(op))
             elif kind == 'dropout':
                 sp, c = op['shape']
                 auto = 'dropout' if ndrop == 0 else 'dropout_%d' % ndrop
@@ -1517,6 +1652,19 @@ class ConvNet(nn.Module):
                 emit(op_name, 'Dropout', {'rate': float(op['rate']), 'noise_shape': [None] + [1] * nd + [int(c)]},
                      [op['src']], shape_of(op))
                 layers[-1]['alias'] = name
+            elif kind == 'dropout_ew':
+                op_name = name
+                if op.get('auto_name'):                               # the reference passes no name: Keras numbers them
+                    op_name = 'dropout' if ndrop == 0 else 'dropout_%d' % ndrop
+                    ndrop += 1
+                emit(op_name, 'Dropout', {'rate': float(op['rate']), 'noise_shape': None}, [op['src']], shape_of(op))
+                layers[-1]['alias'] = name
+            elif kind == 'global_max':
+                emit(name, 'GlobalMaxPooling%dD' % nd, {}, [op['src']], shape_of(op))
+            elif kind == 'global_max_all':
+                emit(name, 'Lambda', {'function': [['batch_flatten'], ['max', 1, True]]}, [op['src']], shape_of(op))
+            elif kind == 'rescale':
+                emit(name, 'RescaleValues', {'resize': op['resize']}, [op['src']], shape_of(op))
             elif kind == 'maxpool':
                 pool = [int(p) for p in op['pool'][3 - nd:]]
                 emit(name, 'MaxPooling%dD' % nd, {'pool_size': pool, 'strides': pool, 'padding': op['padding']}, [op['src']],
@@ -1540,7 +1688,7 @@ class ConvNet(nn.Module):
                 emit(name, 'BatchNormalization', {'axis': int(op['axis']), 'momentum': float(m.momentum),
                                                   'epsilon': float(m.epsilon)}, [op['src']], shape_of(op))
             elif kind == 'prediction':
-                if op['activation'] == 'softmax':
+                if op['activation'] == 'softmax' and not op.get('as_activation'):
                     emit(name, 'Lambda', {'function': [['softmax', op.get('axis', nd + 1)]]}, [op['src']], shape_of(op))
                 else:
                     emit(name, 'Activation', {'activation': op['activation']}, [op['src']], shape_of(op))
@@ -1616,7 +1764,7 @@ class ConvNet(nn.Module):
         bf16 = self._compute_dtype() == torch.bfloat16
         if bf16:
             for op in self.ops:
-                if op['kind'] in _AE_KINDS:
+                if op['kind'] in _AE_KINDS or op['kind'] in _CLS_KINDS:
                     raise NotImplementedError('%s: %s layers have no bfloat16 kernel; run this network in float32 (net.float())'
                                               % (op['name'], op['kind']))
         self._noise = dict(_noise or {})
@@ -1695,6 +1843,8 @@ class ConvNet(nn.Module):
                         t[name] = _elementwise(t[op['src']], act=_act_code(op['activation']))
                 elif kind in _AE_KINDS:
                     self._ae_op(op, t)
+                elif kind in _CLS_KINDS:
+                    self._cls_op(op, t, False)
                 else:
                     raise RuntimeError('unknown op ' + kind)
         if return_tensors:
@@ -1703,6 +1853,8 @@ class ConvNet(nn.Module):
 
     def _unlift_named(self, name, x):
         """the tensor of layer `name` in its Keras shape: [B, *spatial, C], or [B, E] behind a Flatten / Dense"""
+        if name in self._keras_shape:
+            return x.reshape((x.shape[0],) + self._keras_shape[name])
         if self._flat.get(name):
             return x.reshape(x.shape[0], -1)
         return _unlift(x, self.ndims)
@@ -1740,6 +1892,29 @@ class ConvNet(nn.Module):
             lay = self.layers_by_name[name]
             t[name] = lay([mu, lv], _noise=noise)
             self.last_draws[name] = lay.last_draws['noise']
+        else:
+            raise RuntimeError('unknown op ' + kind)
+
+    def _cls_op(self, op, t, recording):
+        """the layers design_dnn / EncoderNet add to the conv stacks (neurite/tf/models.py:1620-1848), inference and autograd
+        recording alike; a [B, E] tensor rides as [B, 1, 1, 1, E].  recording: model.train() with gradients enabled -- the only
+        state in which Dropout draws."""
+        kind, name = op['kind'], op['name']
+        src = t[op['src']]
+        if kind in ('global_max', 'global_max_all'):
+            y = _global_max(src, per_channel=kind == 'global_max')
+            t[name] = y.view(y.shape[0], 1, 1, 1, -1)
+        elif kind == 'rescale':
+            t[name] = _scale_values(src, op['resize'])
+        elif kind == 'dropout_ew':
+            rate = float(op.get('rate', 0))
+            if recording and rate > 0:
+                # KL.Dropout(rate) without a noise_shape: one draw per element.  The draw is plumbing, the multiply the kernel
+                mask = ((torch.rand(src.shape, device=src.device) >= rate).to(torch.float32) / (1.0 - rate)).contiguous()
+                self.last_dropout_masks[name] = mask
+                t[name] = _MulFn.apply(src, mask)
+            else:
+                t[name] = src
         else:
             raise RuntimeError('unknown op ' + kind)
 
@@ -1801,7 +1976,7 @@ class ConvNet(nn.Module):
                         t[name] = _softmax_bf16(t[op['src']])
                     else:
                         t[name] = _elementwise_bf16(t[op['src']], act=_act_code(op['activation']))
-                elif kind in _AE_KINDS:                         # (refused in forward(): no bf16 kernels behind these)
+                elif kind in _AE_KINDS or kind in _CLS_KINDS:   # (refused in forward(): no bf16 kernels behind these)
                     raise NotImplementedError('%s: %s layers have no bfloat16 kernel' % (name, kind))
                 else:
                     raise RuntimeError('unknown op ' + kind)
@@ -1815,6 +1990,7 @@ class ConvNet(nn.Module):
         nd = self.ndims
         t = {}
         self.last_dropout_scales = {}
+        self.last_dropout_masks = {}
         for op in self.ops:
             kind, name = op['kind'], op['name']
             if kind == 'input':
@@ -1873,6 +2049,8 @@ class ConvNet(nn.Module):
                     t[name] = _AddActFn.apply(t[op['src']], None, _act_code(op['activation']))
             elif kind in _AE_KINDS:
                 self._ae_op(op, t)
+            elif kind in _CLS_KINDS:
+                self._cls_op(op, t, True)
             else:
                 raise NotImplementedError('neurite_amd: training through %r layers (%s) is not implemented' % (kind, name))
         if return_tensors:
@@ -2509,6 +2687,171 @@ def ae(nb_features, input_shape, nb_levels, conv_size, nb_labels, enc_size, name
     return (dec_model, mid_ae_model, enc_model)
 
 
+def _flat_tail(bld):
+    """helpers that append [B, E] layers (riding as [B, 1, 1, 1, E]) behind a builder's last tensor"""
+    one3 = (1, 1, 1)
+
+    def flatten(name, src):
+        sp, c = bld.shapes[src]
+        op = {'kind': 'flatten', 'name': name, 'src': src, 'flat': True}
+        return bld.add(op, (one3, int(np.prod(sp)) * int(c)))
+
+    def dense(name, src, units, activation=None):
+        bld.modules[name] = _Dense(name, bld.shapes[src][1], int(units), activation)
+        return bld.add({'kind': 'dense', 'name': name, 'src': src, 'flat': True}, (one3, int(units)))
+
+    def dropout(name, src, rate, auto_name=False):
+        op = {'kind': 'dropout_ew', 'name': name, 'src': src, 'rate': float(rate), 'auto_name': auto_name}
+        srcop = next(o for o in bld.ops if o['name'] == src)
+        for k in ('flat', 'keras_shape'):
+            if srcop.get(k):
+                op[k] = srcop[k]
+        return bld.add(op, bld.shapes[src])
+
+    return flatten, dense, dropout
+
+
+@_store_config
+def design_dnn(nb_features, input_shape, nb_levels, conv_size, nb_labels, feat_mult=1, pool_size=2, padding='same',
+               activation='elu', final_layer='dense-sigmoid', conv_dropout=0, conv_maxnorm=0, nb_input_features=1,
+               batch_norm=False, name=None, prefix=None, use_strided_convolution_maxpool=True, nb_conv_per_level=2):
+    """
+    "Deep" CNN that ends in a number per volume (neurite/tf/models.py:1620-1775): nb_levels x (nb_conv_per_level convolutions, then a
+    stride-1 convolution of kernel size pool_size -- it does not down-sample -- or, with use_strided_convolution_maxpool=False, a
+    max-pooling), then `final_layer`:
+      'dense-sigmoid'       Flatten - Dense(1, sigmoid)
+      'dense-softmax'       Flatten - Dense(nb_labels, softmax)
+      'myglobalmaxpooling'  BatchNormalization(axis=batch_norm) - max over everything but the batch axis - Reshape((1, 1)) -
+                            Conv1D(1, 1, sigmoid).  batch_norm IS the axis here, as in the reference: the last axis runs, the default
+                            False is axis 0, which Keras refuses (ValueError)
+      'globalmaxpooling'    Conv3D(2, 1, relu) - GlobalMaxPooling3D - softmax (3-D inputs only)
+      'dense-tanh'          raises TypeError, as the reference does ('%s_%s_tanh' % prefix)
+      anything else         the model ends at the last convolution or pooling
+    input_shape is the SPATIAL shape; nb_input_features the channels.  conv_dropout is a plain element-wise Dropout in front of every
+    convolution (it draws in model.train() only; the mask of the last draw is in `last_dropout_masks`).  conv_maxnorm > 0 attaches
+    MaxNorm(conv_maxnorm) to every convolution of the levels: call `apply_constraints()` after each optimizer step.
+    """
+    model_name = name
+    if model_name is None:
+        model_name = 'model_1'
+    if prefix is None:
+        prefix = model_name
+    ndims = len(input_shape)
+    if ndims < 1 or ndims > 3:
+        raise NotImplementedError('1-, 2- and 3-D networks are supported')
+    input_shape = tuple(int(v) for v in input_shape)
+    if not use_strided_convolution_maxpool and ndims == 1:
+        raise ValueError('design_dnn pools with MaxPooling2D unless the input is 3-D: a 1-D input cannot be pooled')
+    pool3 = _triple(pool_size, ndims, 'pool_size')
+    k3 = _triple(conv_size, ndims, 'conv_size')
+    bld = _Builder(ndims)
+    flatten, dense, dropout = _flat_tail(bld)
+    in_name = '%s_input' % prefix
+    last = bld.add({'kind': 'input', 'name': in_name, 'index': 0}, ((1,) * (3 - ndims) + input_shape, int(nb_input_features)))
+
+    def conv(name, src, filters, ksize):
+        sp, cin = bld.shapes[src]
+        m = bld.modules[name] = _Conv(name, cin, int(filters), ksize, 1, padding, activation)
+        if conv_maxnorm > 0:
+            m.max_norm = conv_maxnorm
+        return bld.add({'kind': 'conv', 'name': name, 'src': src}, (_conv_out(sp, ksize, 1, padding), int(filters)))
+
+    for level in range(nb_levels):
+        for ci in range(nb_conv_per_level):
+            if conv_dropout > 0:                                                  # :1675-1678, no name: Keras numbers them
+                last = dropout('%s_dropout_%d_%d' % (prefix, level, ci), last, conv_dropout, auto_name=True)
+            nb_lvl_feats = int(np.round(nb_features * feat_mult ** level))
+            last = conv('%s_conv_%d_%d' % (prefix, level, ci), last, nb_lvl_feats, k3)
+        if use_strided_convolution_maxpool:                                       # :1687-1691
+            last = conv('%s_strided_conv_%d' % (prefix, level), last, nb_lvl_feats, pool3)
+        else:
+            sp, c = bld.shapes[last]
+            osp = tuple((sp[d] + pool3[d] - 1) // pool3[d] if padding == 'same' else sp[d] // pool3[d] for d in range(3))
+            last = bld.add({'kind': 'maxpool', 'name': '%s_maxpool_%d' % (prefix, level), 'src': last, 'pool': pool3,
+                            'padding': padding}, (osp, c))
+
+    if final_layer == 'dense-sigmoid':
+        last = flatten('%s_flatten' % prefix, last)
+        last = dense('%s_dense' % prefix, last, 1, 'sigmoid')
+    elif final_layer == 'dense-tanh':
+        last = flatten('%s_flatten' % prefix, last)
+        last = dense('%s_dense' % prefix, last, 1)
+        tanh_name = '%s_%s_tanh' % prefix                                          # :1725 -- TypeError, as in the reference
+        op = {'kind': 'activation', 'name': tanh_name, 'src': last, 'activation': 'tanh', 'flat': True}
+        last = bld.add(op, bld.shapes[last])
+    elif final_layer == 'dense-softmax':
+        last = flatten('%s_flatten' % prefix, last)
+        last = dense('%s_dense' % prefix, last, nb_labels, 'softmax')
+    elif final_layer == 'myglobalmaxpooling':
+        name = '%s_batch_norm' % prefix
+        if int(batch_norm) == 0:
+            raise ValueError('%s: BatchNormalization(axis=%r): axis 0 is the batch axis (pass the feature axis as batch_norm)'
+                             % (name, batch_norm))
+        _last_axis_only(name, batch_norm, ndims + 2)
+        bld.modules[name] = _BatchNorm(name, bld.shapes[last][1])
+        last = bld.add({'kind': 'bn', 'name': name, 'src': last, 'axis': int(batch_norm)}, bld.shapes[last])
+        one3 = (1, 1, 1)
+        last = bld.add({'kind': 'global_max_all', 'name': '%s_global_max_pool' % prefix, 'src': last, 'flat': True}, (one3, 1))
+        last = bld.add({'kind': 'reshape', 'name': '%s_global_max_pool_reshape' % prefix, 'src': last, 'keras_shape': (1, 1)},
+                       (one3, 1))
+        name = '%s_global_max_pool_sigmoid' % prefix
+        m = bld.modules[name] = _Conv(name, 1, 1, one3, 1, 'valid', 'sigmoid')
+        m.keras_nd = 1                                                            # KL.Conv1D(1, 1) on [B, 1, 1]
+        last = bld.add({'kind': 'conv', 'name': name, 'src': last, 'keras_shape': (1, 1)}, (one3, 1))
+    elif final_layer == 'globalmaxpooling':
+        if ndims != 3:
+            raise ValueError("final_layer='globalmaxpooling' is Conv3D + GlobalMaxPooling3D: it needs a 3-D input, got %d-D" % ndims)
+        name = '%s_conv_to_featmaps' % prefix
+        sp, cin = bld.shapes[last]
+        bld.modules[name] = _Conv(name, cin, 2, (1, 1, 1), 1, 'valid', 'relu')
+        last = bld.add({'kind': 'conv', 'name': name, 'src': last}, (sp, 2))
+        last = bld.add({'kind': 'global_max', 'name': '%s_global_max_pool' % prefix, 'src': last, 'flat': True}, ((1, 1, 1), 2))
+        last = bld.add({'kind': 'prediction', 'name': '%s_global_max_pool_softmax' % prefix, 'src': last, 'activation': 'softmax',
+                        'as_activation': True, 'flat': True}, ((1, 1, 1), 2))
+    net = ConvNet(model_name, ndims, [input_shape + (int(nb_input_features),)], bld.ops, last, bld.modules)
+    net._builder_state = dict(shapes=bld.shapes)
+    return net
+
+
+@_store_config
+def EncoderNet(nb_features, input_shape, nb_levels, conv_size, name=None, prefix=None, feat_mult=1, pool_size=2,
+               dilation_rate_mult=1, padding='same', activation='elu', layer_nb_feats=None, use_residuals=False,
+               nb_conv_per_level=2, conv_dropout=0, dense_size=256, nb_labels=2, final_activation=None, rescale=None, dropout=None,
+               batch_norm=None):
+    """
+    Convolutional encoder with a classifier or regressor on top (neurite/tf/models.py:1782-1848): conv_enc - Flatten - [Dropout] -
+    Dense(dense_size) - [Dropout] - [layers.RescaleValues(rescale)] - Dense(nb_labels, final_activation).  nb_labels <= 0 is a
+    one-unit regressor (final_activation None: linear); otherwise final_activation None is softmax.  As in the reference, `prefix`,
+    `dilation_rate_mult` and `layer_nb_feats` are accepted and not passed on to the encoder.
+    """
+    enc = conv_enc(nb_features, input_shape, nb_levels, conv_size, name=name, feat_mult=feat_mult, pool_size=pool_size,
+                   padding=padding, activation=activation, use_residuals=use_residuals, nb_conv_per_level=nb_conv_per_level,
+                   conv_dropout=conv_dropout, batch_norm=batch_norm)
+    bld = _Builder(enc.ndims)
+    bld.ops = list(enc.ops)
+    bld.modules = dict(enc.layers_by_name.items())
+    bld.shapes = dict(enc._builder_state['shapes'])
+    flatten, dense, drop = _flat_tail(bld)
+    last = flatten('flatten', enc.output_name)
+    if dropout is not None and dropout > 0:
+        last = drop('dropout_flat', last, dropout)
+    last = dense('dense', last, dense_size)
+    if dropout is not None and dropout > 0:
+        last = drop('dropout_dense', last, dropout)
+    if nb_labels <= 0:                                                             # a regression net
+        nb_labels = 1
+        if final_activation is None:
+            final_activation = 'linear'
+    elif final_activation is None:
+        final_activation = 'softmax'
+    if rescale is not None:
+        last = bld.add({'kind': 'rescale', 'name': 'rescale_values', 'src': last, 'resize': rescale, 'flat': True}, bld.shapes[last])
+    last = dense('output_dense', last, nb_labels, final_activation)
+    net = ConvNet(None, enc.ndims, enc.input_shapes, bld.ops, last, bld.modules)
+    net._builder_state = dict(shapes=bld.shapes)
+    return net
+
+
 def load_config(path):
     """builder name and arguments stored by `ConvNet.save` (LoadableModel.load_config, neurite/tf/modelio.py:125-143)"""
     if _is_h5(path):
@@ -2530,9 +2873,10 @@ def load(path, by_name=False, **kwargs):
     arguments override them), then load its weights.
     """
     builder, config = load_config(path)
-    builders = {'unet': unet, 'conv_enc': conv_enc, 'conv_dec': conv_dec, 'ae': ae, 'single_ae': single_ae}
+    builders = {'unet': unet, 'conv_enc': conv_enc, 'conv_dec': conv_dec, 'ae': ae, 'single_ae': single_ae,
+                'design_dnn': design_dnn, 'EncoderNet': EncoderNet}
     if builder not in builders:
-        raise ValueError('%s was not saved from a unet / conv_enc / conv_dec / ae / single_ae network (class_name %r)'
+        raise ValueError('%s was not saved from a unet / conv_enc / conv_dec / ae / single_ae / design_dnn / EncoderNet network (class_name %r)'
                          % (path, builder))
     config.update(kwargs)
     metadata = config.pop('metadata', {})
