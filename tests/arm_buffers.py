@@ -1,0 +1,49 @@
+"""
+Guarded device buffers for the tests that call the C ABI directly (tests/test_gpu_dispatch_arms.py,
+tests/test_gpu_warp_backward_arms.py): the alignment of every pointer is exact, and a write outside an output is caught.
+"""
+
+import numpy as np
+import torch
+
+from neurite_amd import _lib
+
+F = np.float32
+PAD = 8                     # guard floats on each side of a buffer the test owns (32 bytes: the payload stays 16-byte aligned)
+FILL = -12345.0
+
+
+def N(t):
+    return t.detach().cpu().numpy()
+
+
+class Buf:
+    """n floats with PAD guard floats on each side.  off = 0: the payload starts 16-byte aligned; off = 1: one float later, which
+    is what sends a dispatcher to its unaligned arm."""
+
+    def __init__(self, dev, n, off=0, data=None):
+        _lib.require_device(torch.empty(1, device=dev))
+        self.whole = torch.full((n + 2 * PAD + 1,), FILL, dtype=torch.float32, device=dev)
+        assert self.whole.data_ptr() % 16 == 0
+        self.lo, self.n = PAD + off, n
+        self.t = self.whole[self.lo:self.lo + n]
+        assert (self.t.data_ptr() % 16 == 0) == (off == 0)
+        if data is not None:
+            self.t.copy_(torch.from_numpy(np.ascontiguousarray(data, F).reshape(-1)))
+
+    @property
+    def p(self):
+        return _lib.ptr(self.t)
+
+    def get(self, shape=None):
+        """the payload, after checking that nothing outside it was written"""
+        w = N(self.whole)
+        assert (w[:self.lo] == F(FILL)).all() and (w[self.lo + self.n:] == F(FILL)).all(), 'a write outside the output'
+        out = w[self.lo:self.lo + self.n]
+        return out.reshape(shape) if shape is not None else out
+
+
+def call(dev, name, *args):
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*args, _lib.stream_ptr(dev))
+    _lib.check(rc, name)

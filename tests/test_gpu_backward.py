@@ -539,7 +539,10 @@ def test_grad_vol_few_channels(dev, C, mode, monkeypatch):
     """d out / d vol at few channels, 3-D (the backward of VecInt / compose and of warped few-channel network outputs): the
     counting-sort merge over 4 x 4 x 8 tiles (interpn_bwd_vol_sort_any, default) and the per-element scatter
     (NRT_BWD_VOL_SORT_ANY=0) against the float64 oracle: smooth field (many duplicate rows), rough field (every pair its own row),
-    fill value (masked voxels), output extents that are no multiples of the tile, a source volume of another shape"""
+    fill value (masked voxels), output extents that are no multiples of the tile, a source volume of another shape.
+    C = 8 does NOT reach either kernel here: these tensors are 16-byte aligned, and an aligned 8-channel volume takes
+    interpn_bwd_rows<2> in both modes.  interpn_bwd_vol_sort_any at 6, 7 and (4 bytes off the boundary) 4 and 8 channels is in
+    tests/test_gpu_warp_backward_arms.py."""
     monkeypatch.setenv('NRT_BWD_VOL_SORT_ANY', mode)
     rng = np.random.default_rng(41 + C)
     B, S = 2, (9, 14, 21)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from arm_buffers import Buf, call
 from neurite_amd import _lib
 from neurite_amd import models as M
 from oracle import torch_unet_oracle as tuo
@@ -25,8 +26,6 @@ from oracle import torch_unet_oracle as tuo
 pytestmark = pytest.mark.gpu
 F = np.float32
 TOL = 2e-4                  # gradients, of the gradient scale
-PAD = 8                     # guard floats on each side of a buffer the test owns (32 bytes: the payload stays 16-byte aligned)
-FILL = -12345.0
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -40,38 +39,6 @@ def N(t):
 def G(a, dev, grad=False):
     t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     return t.requires_grad_() if grad else t
-
-
-class Buf:
-    """n floats with PAD guard floats on each side.  off = 0: the payload starts 16-byte aligned; off = 1: one float later, which
-    is what sends a dispatcher to its unaligned arm."""
-
-    def __init__(self, dev, n, off=0, data=None):
-        _lib.require_device(torch.empty(1, device=dev))
-        self.whole = torch.full((n + 2 * PAD + 1,), FILL, dtype=torch.float32, device=dev)
-        assert self.whole.data_ptr() % 16 == 0
-        self.lo, self.n = PAD + off, n
-        self.t = self.whole[self.lo:self.lo + n]
-        assert (self.t.data_ptr() % 16 == 0) == (off == 0)
-        if data is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(data, F).reshape(-1)))
-
-    @property
-    def p(self):
-        return _lib.ptr(self.t)
-
-    def get(self, shape=None):
-        """the payload, after checking that nothing outside it was written"""
-        w = N(self.whole)
-        assert (w[:self.lo] == F(FILL)).all() and (w[self.lo + self.n:] == F(FILL)).all(), 'a write outside the output'
-        out = w[self.lo:self.lo + self.n]
-        return out.reshape(shape) if shape is not None else out
-
-
-def call(dev, name, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.stream_ptr(dev))
-    _lib.check(rc, name)
 
 
 def close(got, ref, tol=1e-5, what=''):

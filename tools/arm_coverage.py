@@ -1,4 +1,5 @@
-"""Which template instances of the U-Net head and glue kernels did a traced run never launch?
+"""Which template instances of the U-Net head and glue kernels (or, --families warp_bwd, of the warp backward) did a traced run
+never launch?
 
     hipcc <build.FLAGS> --cuda-device-only -S neurite_amd/csrc/conv.hip -o conv.s          (the same for conv_bwd.hip)
     python tools/kernel_digest.py conv.s > conv_kernels.txt
@@ -8,6 +9,9 @@
 The kernel tables (tools/kernel_digest.py) list every instance the compiler emitted; the stats file lists every kernel that ran,
 with its number of launches.  Prints one line per instance of the families below that the run never launched -- nothing when
 every arm ran -- and exits 1 if there is one.  --all lists the launched instances with their launch counts too.
+
+--families warp_bwd checks the dispatch arms of nrt_interpn_bwd_f32 and nrt_interpn_nearest_bwd_f32 instead (csrc/backward.hip,
+tests/test_gpu_warp_backward_arms.py; kernel table profiles/dispatch_arms/backward_kernels.txt).
 """
 import argparse
 import csv
@@ -21,6 +25,11 @@ FAMILIES = [r'conv1x1_rows<\d+,\d+>', r'conv1x1_vec<\d+,0>', r'conv1x1_softmax<\
             r'softmax_bwd', r'softmax_bwd_vec<\d+>', r'conv1x1_wgrad16<\d+>', r'conv3d_c1_wgrad<\d+>', r'conv3d_c1_mfma<\d+,false,false>',
             r'conv3d_c1_vec<\d+,false>', r'act_bwd', r'act_bwd_tail', r'maxpool_bwd', r'add_act_affine', r'add_act_affine_v4',
             r'channel_sums', r'channel_axpby']
+# the dispatchers of nrt_interpn_bwd_f32 and nrt_interpn_nearest_bwd_f32 (the x-march kernels interpn_bwd_vol_sort and warp_dice_bwd_xm
+# are the benchmark path and have their own tests)
+WARP_BWD_FAMILIES = [r'interpn_bwd_rows<\d+,\d+>', r'interpn_bwd_generic<\d+,\d+>', r'interpn_bwd_vol_elems<\d+,\d+>',
+                     r'interpn_bwd_vol_sort_any<\d+>', r'interpn_nearest_bwd<\d+,\d+>']
+FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
@@ -67,7 +76,10 @@ def main():
     ap.add_argument('--kernels', nargs='+', required=True, help='tables written by tools/kernel_digest.py')
     ap.add_argument('--stats', required=True, help='kernel stats CSV of a rocprofv3 --kernel-trace --stats run')
     ap.add_argument('--all', action='store_true', help='list the launched instances and their launch counts as well')
+    ap.add_argument('--families', choices=sorted(FAMILY_SETS), default='conv', help='which dispatchers (default: the head and glue kernels)')
     args = ap.parse_args()
+    global FAMILY
+    FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILY_SETS[args.families]))
     inst, calls = instances(args.kernels), launches(args.stats)
     if not inst:
         raise SystemExit('no instance of the families in %s' % ', '.join(args.kernels))
