@@ -826,6 +826,44 @@ int nrt_hyperconv3d_pad_f32(const float *src, int cin, const float *weights, con
                             float *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
                             const int *pad_before, int activation, int variant, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Patch-wise volume prediction, neurite/tf/utils/seg.py (csrc/seg.hip): the arg-max of a probability map with the probability of a
+ * label in the same pass, a label lookup, patch extraction and its inverse, the quilt.  Four streaming kernels: no atomics, no
+ * workspace, no host synchronisation (all capture into a graph); run-to-run bit-identical.  Base pointers need the alignment of their
+ * element type only (wider accesses are used where the shape and the pointers allow).  Checked before any launch, by every call:
+ * NRT_ERR_INVALID_ARG for a NULL tensor or shape array that is not optional and for a size < 1; NRT_ERR_UNSUPPORTED for a dtype
+ * outside the ones named and for 2^31 or more elements in any one tensor.
+ *
+ *   nrt_seg_argmax     pred [n_vox, channels] (NRT_DT_F32 / NRT_DT_BF16), 1 <= channels <= 256 (more: NRT_ERR_UNSUPPORTED).
+ *                      labels [n_vox] (int64 if labels_i64 else int32; may be NULL) = np.argmax(pred, -1): the first index wins a tie,
+ *                      a NaN counts as the maximum (the first NaN wins).  prob [n_vox] float32 (may be NULL) =
+ *                      pred[v, l] / sum_c pred[v, c] (float32 sum), where l = of_labels[v] (int64 if of_labels_i64 else int32) or,
+ *                      with of_labels NULL, the arg-max itself; an l outside [0, channels) gives NaN and reads nothing.  labels and
+ *                      prob both NULL, or of_labels without prob: NRT_ERR_INVALID_ARG.  channels % 4 == 0: a group of lanes shares a
+ *                      voxel's channels with 8- / 16-byte loads and merges (value, index) pairs across lanes; else a thread per voxel.
+ *   nrt_seg_recode     out[v] = lookup[seg[v]] for v < n; seg int64 if seg_i64 else int32, lookup [n_lookup] and out float32.
+ *                      An index outside [0, n_lookup) writes 0 and reads nothing.
+ *   nrt_patch_extract  vol [*vol_shape, channels] (rank ndim 1 .. 3; NRT_DT_F32 / NRT_DT_BF16) -> patches [count, *patch_size,
+ *                      channels]: the patches n0 .. n0 + count - 1 of the grid; patch n has the grid index unravel_index(n, grid_size)
+ *                      (C order) and starts at index * patch_stride.  NRT_ERR_INVALID_ARG: ndim outside 1 .. 3, a stride < 1, a grid
+ *                      that does not fit ((grid - 1) * stride + patch > vol on an axis), n0 < 0 or n0 + count > prod(grid_size).
+ *   nrt_patch_quilt    patches [prod(grid_size), *patch_size, channels] (NRT_DT_F32 / NRT_DT_I32, converted to float32) ->
+ *                      vol [*((grid - 1) * stride + patch), channels] float32.  An output element reduces the patch values that cover
+ *                      it, read in ascending patch index, NaN values skipped (np.nanmean / np.nanmedian over the stack of patches):
+ *                      NRT_QUILT_MEAN    float32 sum in that order / the number of values; any cover count.
+ *                      NRT_QUILT_MEDIAN  exact selection, (a + b) / 2 of the two middle values of an even count; up to 64 covering
+ *                                        patches: prod(ceil(patch / stride)) > 64 is NRT_ERR_UNSUPPORTED.
+ *                      No cover (stride > patch) or only NaN values: NaN.  Another `reduce`: NRT_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum { NRT_QUILT_MEAN = 0, NRT_QUILT_MEDIAN = 1 } nrt_quilt_reduce;
+int nrt_seg_argmax(const void *pred, int dtype, long long n_vox, int channels, void *labels, int labels_i64, const void *of_labels,
+                   int of_labels_i64, float *prob, void *stream);
+int nrt_seg_recode(const void *seg, int seg_i64, long long n, const float *lookup, long long n_lookup, float *out, void *stream);
+int nrt_patch_extract(const void *vol, int dtype, int ndim, const int *vol_shape, int channels, const int *patch_size,
+                      const int *patch_stride, const int *grid_size, long long n0, long long count, void *patches, void *stream);
+int nrt_patch_quilt(const void *patches, int dtype, int ndim, const int *patch_size, const int *patch_stride, const int *grid_size,
+                    int channels, int reduce, float *vol, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

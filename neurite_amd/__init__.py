@@ -29,6 +29,9 @@ from . import distributed  # noqa: F401
 from . import augment  # noqa: F401
 from . import synthesis  # noqa: F401
 from . import synth  # noqa: F401
+from . import seg  # noqa: F401
+
+utils.seg = seg         # the reference's place for it: neurite.utils.seg
 
 backend = 'pytorch'
 

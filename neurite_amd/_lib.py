@@ -153,6 +153,10 @@ _SIGNATURES = {
     'nrt_maxnorm_f32': (_i, [_vp, _i, _ll, _f, _f, _vp]),
     'nrt_conv3d_pad_f32': (_i, [_vp, _i, _vp, _i, _ip, _vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _ip, _i, _i, _vp]),
     'nrt_hyperconv3d_pad_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _ip, _i, _i, _vp]),
+    'nrt_seg_argmax': (_i, [_vp, _i, _ll, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'nrt_seg_recode': (_i, [_vp, _i, _ll, _vp, _ll, _vp, _vp]),
+    'nrt_patch_extract': (_i, [_vp, _i, _i, _ip, _i, _ip, _ip, _ip, _ll, _ll, _vp, _vp]),
+    'nrt_patch_quilt': (_i, [_vp, _i, _i, _ip, _ip, _ip, _i, _i, _vp, _vp]),
 }
 
 
