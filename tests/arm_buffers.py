@@ -1,6 +1,7 @@
 """
 Guarded device buffers for the tests that call the C ABI directly (tests/test_gpu_dispatch_arms.py,
-tests/test_gpu_warp_backward_arms.py): the alignment of every pointer is exact, and a write outside an output is caught.
+tests/test_gpu_warp_backward_arms.py, tests/test_gpu_filter_arms.py): the alignment of every pointer is exact, and a write outside
+an output is caught.
 """
 
 import numpy as np
@@ -41,6 +42,28 @@ class Buf:
         assert (w[:self.lo] == F(FILL)).all() and (w[self.lo + self.n:] == F(FILL)).all(), 'a write outside the output'
         out = w[self.lo:self.lo + self.n]
         return out.reshape(shape) if shape is not None else out
+
+
+class Bytes:
+    """a workspace of exactly n bytes (64-byte aligned) with GUARD guard bytes on each side"""
+
+    GUARD, MARK = 64, 0xA5
+
+    def __init__(self, dev, n):
+        _lib.require_device(torch.empty(1, device=dev))
+        self.whole = torch.full((n + 2 * self.GUARD,), self.MARK, dtype=torch.uint8, device=dev)
+        assert self.whole.data_ptr() % 64 == 0
+        self.n = n
+        self.t = self.whole[self.GUARD:self.GUARD + n]
+
+    @property
+    def p(self):
+        return _lib.ptr(self.t)
+
+    def check(self):
+        """nothing outside the n bytes was written"""
+        w = N(self.whole)
+        assert (w[:self.GUARD] == self.MARK).all() and (w[self.GUARD + self.n:] == self.MARK).all(), 'a write outside the workspace'
 
 
 def call(dev, name, *args):
