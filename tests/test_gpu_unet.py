@@ -113,7 +113,9 @@ def test_conv3d_mfma_vs_oracle(dev, cin, cout, shape, k, dil, act):
 
 
 @pytest.mark.parametrize('cin,cout,shape,act', [
-    (16, 16, (22, 9, 37), 'elu'),             # several tiles per persistent block, ragged on every axis, deferred stores
+    (16, 16, (22, 9, 37), 'elu'),             # 6 x 3 x 3 tiles x 3 entries = 162: one tile per persistent block on 256 CUs (several only
+                                              # below 162 CUs; tests/test_gpu_conv_fwd_arms.py has the multi-tile cases), ragged on every
+                                              # axis, deferred stores
     (32, 32, (8, 12, 48), None),              # two chunks per tile, two N-tiles
     (48, 40, (6, 6, 20), 'relu'),             # three chunks, partial third N-tile (immediate stores)
     (16, 64, (4, 4, 16), 'elu'),              # one tile

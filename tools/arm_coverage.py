@@ -1,5 +1,5 @@
 """Which template instances of the U-Net head and glue kernels (or, --families warp_bwd, of the warp backward; --families
-conv_wgrad, of the conv weight gradient) did a traced run never launch?
+conv_wgrad, of the conv weight gradient; --families conv_fwd, of the conv forward) did a traced run never launch?
 
     hipcc <build.FLAGS> --cuda-device-only -S neurite_amd/csrc/conv.hip -o conv.s          (the same for conv_bwd.hip)
     python tools/kernel_digest.py conv.s > conv_kernels.txt
@@ -18,6 +18,10 @@ profiles/dispatch_arms/conv_bwd_kernels.txt).  Instances that no call within the
 REGEX (default for this family: the six per-parity-group folded instances conv3d_wgrad<NA,NB,3,2,false>, see
 profiles/dispatch_arms/README.md): they are listed as such and do not count towards the exit status -- unless the run DID launch
 one, which is reported and exits 1.
+
+--families conv_fwd checks the convolution forward kernels of csrc/conv.hip, conv_p27.h and conv_up2.h with space_to_depth2 and the
+weight-pack kernels (tests/test_gpu_conv_fwd_arms.py; kernel table profiles/dispatch_arms/conv_kernels.txt).  Every instance is
+reachable.
 """
 import argparse
 import csv
@@ -39,10 +43,16 @@ WARP_BWD_FAMILIES = [r'interpn_bwd_rows<\d+,\d+>', r'interpn_bwd_generic<\d+,\d+
 # nrt_upsample_sum_f32 (the two streaming arms are in FAMILIES as well: here they make the weight-gradient table whole)
 CONV_WGRAD_FAMILIES = [r'conv3d_wgrad<\d+,\d+,\d+,\d+,(?:false|true)>', r'conv3d_wgrad_fold<\d+>', r'upsample_sum', r'conv1x1_wgrad16<\d+>',
                        r'conv3d_c1_wgrad<\d+>']
-FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES}
+# the dispatchers of nrt_conv3d_f32 / nrt_conv3d_pad_f32, nrt_hyperconv3d_f32 / nrt_hyperconv3d_pad_f32, nrt_conv3d_pool_f32, nrt_conv3d_up2_f32
+# and nrt_conv3d_s2d_taps_f32, with nrt_space_to_depth2_f32 and the four weight-pack kernels their tests go through (the head forms
+# conv3d_up2_mfma<1,1> and <1,2> and the single-channel first-layer kernels have their own tests and are outside this family)
+CONV_FWD_FAMILIES = [r'conv3d_mfma<\d+,(?:false|true),(?:false|true),(?:false|true)>', r'conv3d_p27_mfma<\d+,(?:false|true),(?:false|true)>',
+                     r'conv3d_up2_mfma<\d+,0>', r'conv3d_mfma_k2<\d+>', r'conv3d_direct<(?:false|true)>', r'space_to_depth2',
+                     r'conv3d_pack_weights', r'conv3d_pack_weights_batched<(?:false|true)>', r'conv3d_pack_weights_up2']
+FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
 # aligned, which include/neurite_amd.h rules out
-UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>']}
+UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': []}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
