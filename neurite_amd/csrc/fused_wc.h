@@ -20,9 +20,9 @@
 //        with two ds_read_b128 and fetch one 128-byte row each: ceil(n / 8) load instructions per pass instead of 8 (n = 23 on
 //        the bench field); the source row of every reference is broadcast to its group through 128 bytes
 //        of LDS (16-bit offsets, one ds_read_b128, unpacked by the SDWA operands of the address additions);
-//   M2   the row loads (four always -- entries past n address bytes past the volume: no memory access -- and four more under a
-//        wave-uniform branch when n > 32: 19 % of the passes), the fixed row;
-//   D    the fetched rows are stored to their slots;
+//   M2   the row loads, one per group of 8 list entries (four always -- entries past n address bytes past the volume: no memory
+//        access -- and one per group that holds an entry under a wave-uniform branch when n > 32: 18 % of the passes), the fixed row;
+//   D    the fetched rows are stored to their slots, one ds_write_b128 per group that holds an entry (3.3 per pass, not 4.7);
 //   B    blend: 8 ds_read_b128 per lane from the slots recorded in M1c, then exactly the arithmetic of warp_dice_tile /
 //        interpn.hip (same op order: bit-identical warped rows).
 // A pass with more than 16 orphans (incoherent fields) invalidates the cache and fetches its 64 references as they are.
@@ -57,6 +57,9 @@ namespace {
 #endif
 #ifndef WC_NST_BWD
 #define WC_NST_BWD 3                                            // pass states of the backward forms (they store the location gradient every pass)
+#endif
+#ifndef WC_FIXED_GROUPS
+#define WC_FIXED_GROUPS 4                                       // groups of 8 fetch-list entries whose row loads go out whatever n is (3 or 4)
 #endif
 constexpr int WC_SLOTS = 128;                                   // direct-mapped rows per wave
 constexpr int WC_OVF = 16;                                      // overflow rows (orphans of the current pass)
@@ -186,18 +189,22 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
     nrt_f2 stp_l = {0, 0}, stp_h = {0, 0}, stt_l = {0, 0}, stt_h = {0, 0}, spp_l = {0, 0}, spp_h = {0, 0};
     float mnt = INFINITY, mxt = -INFINITY, mnp = INFINITY, mxp = -INFINITY;
 
+    // The fetch list travels in groups of 8 entries (one row load and one 1 KB LDS store per group).  The loads of the first FG groups
+    // go out whatever n is; their stores, and both halves of the groups behind them, only where the group holds an entry (wave-uniform)
+    constexpr int FG = WC_FIXED_GROUPS, NX = 8 - FG;
+    static_assert(FG == 3 || FG == 4, "WC_FIXED_GROUPS");
     // ---- per-pass state.  Two passes are in flight: the loop is unrolled by two and the passes alternate between the states A and B
     struct Pass {
         float w0x, w0y, w0z;         // lower-corner weights
         unsigned sl[8];              // byte offset (row * 128) of the source row of the 8 corners in this wave's LDS rows
-        unsigned lr[4], ld[4];       // fetch-list entries g, 8 + g, 16 + g, 24 + g: byte offset of the row in the volume, of its LDS row
-        unsigned xr[4], xd[4];       // entries 32 + g ... (n > 32 only)
+        unsigned lr[FG], ld[FG];     // fetch-list entries g, 8 + g ... of the fixed groups: byte offset of the row in the volume, of its LDS row
+        unsigned xr[NX], xd[NX];     // entries 8 FG + g ... (n > 8 FG only)
         int n;                       // wave-uniform: entries of the fetch list
         int xq;                      // wave-uniform: output x-plane of the pass
         float mk[3];                 // BWD: 1 where the location lies inside the closed range of the axis, else 0 (the slope of `clip`)
         bool oob;
         nrt_f4 T;                    // the fixed row
-        nrt_f4 F[4], Fx[4];          // rows in flight
+        nrt_f4 F[FG], Fx[NX];        // rows in flight
         float pn[3];                 // location of the pass that will use this state next
     };
     // a pass under management: from the tag read (m1a) to the fetch list (m1c)
@@ -214,12 +221,16 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
     // registers (backward forms: 217 - 243 registers; the stand-alone warp keeps a set per state: 198 - 221)
     constexpr bool XSH = NST == 3 && DICE;
     Pass A, B, C;
-    nrt_f4 FxS[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    nrt_f4 FxS[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) FxS[i] = (nrt_f4){0.f, 0.f, 0.f, 0.f};
     auto reset = [&](Pass &s) {
         s.w0x = s.w0y = s.w0z = 0.f; s.n = 0; s.xq = x0; s.oob = false; s.mk[0] = s.mk[1] = s.mk[2] = 0.f;
         s.T = (nrt_f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { s.F[i] = s.Fx[i] = (nrt_f4){0.f, 0.f, 0.f, 0.f}; s.lr[i] = s.xr[i] = WC_NOROW << 7; s.ld[i] = s.xd[i] = WC_TRASH_ROW * 128u; }
+        for (int i = 0; i < FG; ++i) { s.F[i] = (nrt_f4){0.f, 0.f, 0.f, 0.f}; s.lr[i] = WC_NOROW << 7; s.ld[i] = WC_TRASH_ROW * 128u; }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) { s.Fx[i] = (nrt_f4){0.f, 0.f, 0.f, 0.f}; s.xr[i] = WC_NOROW << 7; s.xd[i] = WC_TRASH_ROW * 128u; }
 #pragma unroll
         for (int i = 0; i < 8; ++i) s.sl[i] = 0;
         s.pn[0] = s.pn[1] = s.pn[2] = 0.f;
@@ -301,45 +312,55 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         const nrt_i4 la = *(wc_lds_vi4 *)(wl + WC_LIST_OFF + g * 64), lb = *(wc_lds_vi4 *)(wl + WC_LIST_OFF + g * 64 + 16);
         const nrt_i4 sh = *(wc_lds_vi4 *)(wl + WC_BC_OFF + g * 16);
         s.lr[0] = (unsigned)la[0]; s.ld[0] = (unsigned)la[1]; s.lr[1] = (unsigned)la[2]; s.ld[1] = (unsigned)la[3];
-        s.lr[2] = (unsigned)lb[0]; s.ld[2] = (unsigned)lb[1]; s.lr[3] = (unsigned)lb[2]; s.ld[3] = (unsigned)lb[3];
+        s.lr[2] = (unsigned)lb[0]; s.ld[2] = (unsigned)lb[1];
+        if (FG == 4) { s.lr[FG - 1] = (unsigned)lb[2]; s.ld[FG - 1] = (unsigned)lb[3]; }
+        else { s.xr[0] = (unsigned)lb[2]; s.xd[0] = (unsigned)lb[3]; }
         if (__builtin_expect(n > 32, 0)) {
             const nrt_i4 lc = *(wc_lds_vi4 *)(wl + WC_LIST_OFF + g * 64 + 32), le = *(wc_lds_vi4 *)(wl + WC_LIST_OFF + g * 64 + 48);
-            s.xr[0] = (unsigned)lc[0]; s.xd[0] = (unsigned)lc[1]; s.xr[1] = (unsigned)lc[2]; s.xd[1] = (unsigned)lc[3];
-            s.xr[2] = (unsigned)le[0]; s.xd[2] = (unsigned)le[1]; s.xr[3] = (unsigned)le[2]; s.xd[3] = (unsigned)le[3];
+            s.xr[NX - 4] = (unsigned)lc[0]; s.xd[NX - 4] = (unsigned)lc[1]; s.xr[NX - 3] = (unsigned)lc[2]; s.xd[NX - 3] = (unsigned)lc[3];
+            s.xr[NX - 2] = (unsigned)le[0]; s.xd[NX - 2] = (unsigned)le[1]; s.xr[NX - 1] = (unsigned)le[2]; s.xd[NX - 1] = (unsigned)le[3];
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) { s.sl[2 * c] = (unsigned)sh[c] & 0xffffu; s.sl[2 * c + 1] = (unsigned)sh[c] >> 16; }
-        s.w0x = m.w0x; s.w0y = m.w0y; s.w0z = m.w0z; s.oob = m.oob; s.n = n;
+        s.w0x = m.w0x; s.w0y = m.w0y; s.w0z = m.w0z; s.oob = m.oob;
+        s.n = __builtin_amdgcn_readfirstlane(n);                 // (an SGPR for the compiler: the conditions on it below are scalar branches)
         if (BWD) { s.mk[0] = m.mk[0]; s.mk[1] = m.mk[1]; s.mk[2] = m.mk[2]; }
         s.xq = x0 + pass;
     };
-    // M2: the row loads of the pass in s.  Four whatever n is (entries past n address bytes past the volume: no memory access): with
-    // every load under a condition the compiler's in-order vmcnt count assumes none was issued and each wait covers the other state's
-    // pass as well (round 4, v3: 1.37 ms); four more when the list is longer than 32 (19 % of the passes on the bench field)
+    // M2: the row loads of the pass in s.  Those of the first FG groups go out whatever n is (entries past n address bytes past the volume:
+    // no memory access): with every load under a condition the compiler's in-order vmcnt count assumes none was issued and each wait covers
+    // the other state's pass as well (round 4, v3: 1.37 ms).  The groups behind them go out under a wave-uniform branch (n > 32: 18 % of the
+    // passes on the bench field), each only when it holds an entry.
     auto issue = [&](Pass &s) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) s.F[i] = fetch_row(s.lr[i]);
-        if (!XSH && __builtin_expect(s.n > 32, 0)) {
+        for (int i = 0; i < FG; ++i) s.F[i] = fetch_row(s.lr[i]);
+        if (!XSH && __builtin_expect(s.n > 8 * FG, 0)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) s.Fx[i] = fetch_row(s.xr[i]);
+            for (int i = 0; i < NX; ++i)
+                if (i == 0 || s.n > 8 * (FG + i)) s.Fx[i] = fetch_row(s.xr[i]);
         }
         if (DICE) s.T = __builtin_bit_cast(nrt_f4, __builtin_amdgcn_raw_buffer_load_b128(fres, row_lane, (unsigned)s.xq * row_step, 2));
     };
-    // (XSH) the rows 32 .. of the pass in s, into the shared registers: called at the end of the step BEFORE the one that blends the pass,
+    // (XSH) the rows 8 FG .. of the pass in s, into the shared registers: called at the end of the step BEFORE the one that blends the pass,
     // behind the delivery of the previous pass's
     auto issue_x = [&](Pass &s) {
-        if (XSH && __builtin_expect(s.n > 32, 0)) {
+        if (XSH && __builtin_expect(s.n > 8 * FG, 0)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) FxS[i] = fetch_row(s.xr[i]);
+            for (int i = 0; i < NX; ++i)
+                if (i == 0 || s.n > 8 * (FG + i)) FxS[i] = fetch_row(s.xr[i]);
         }
     };
-    // D: rows fetched for the pass -> their cache / overflow rows
+    // D: rows fetched for the pass -> their cache / overflow rows.  A group without an entry (n <= 8 i) would store zeros to the trash row:
+    // its ds_write_b128 -- about 13 cycles of the VGPR-to-LDS path, the busiest unit of the pass -- is skipped
     auto deliver = [&](Pass &s) {
+        *(wc_lds_f4 *)(lrow + s.ld[0]) = s.F[0];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *(wc_lds_f4 *)(lrow + s.ld[i]) = s.F[i];
-        if (__builtin_expect(s.n > 32, 0)) {
+        for (int i = 1; i < FG; ++i)
+            if (s.n > 8 * i) *(wc_lds_f4 *)(lrow + s.ld[i]) = s.F[i];
+        if (__builtin_expect(s.n > 8 * FG, 0)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) *(wc_lds_f4 *)(lrow + s.xd[i]) = XSH ? FxS[i] : s.Fx[i];
+            for (int i = 0; i < NX; ++i)
+                if (i == 0 || s.n > 8 * (FG + i)) *(wc_lds_f4 *)(lrow + s.xd[i]) = XSH ? FxS[i] : s.Fx[i];
         }
     };
 
@@ -477,11 +498,20 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
             fetch_loc(min(5, last), C);
             issue_x(A);
             __builtin_amdgcn_sched_barrier(0);
+            // The first step of each state runs OUTSIDE the loop, and no path leads from the prologue to the loop but through them: behind
+            // the prologue fewer loads are in flight than in steady state, and the compiler's vmcnt count at the loop head is the smallest
+            // over the paths into it -- with a path from the prologue among them every pass waited in M1a for its own fixed row, which the
+            // design first touches behind M1c
             int pass = 0;
-            for (; pass + 2 < npass; pass += 3) {
-                step(pass, A, C, B, masked);
-                step(pass + 1, B, A, C, masked);
-                step(pass + 2, C, B, A, masked);
+            if (npass >= 3) {
+                step(0, A, C, B, masked);
+                step(1, B, A, C, masked);
+                step(2, C, B, A, masked);
+                for (pass = 3; pass + 2 < npass; pass += 3) {
+                    step(pass, A, C, B, masked);
+                    step(pass + 1, B, A, C, masked);
+                    step(pass + 2, C, B, A, masked);
+                }
             }
             if (pass < npass) step(pass, A, C, B, masked);        // (what the last steps prepare beyond the end is not used)
             if (pass + 1 < npass) step(pass + 1, B, A, C, masked);
@@ -496,9 +526,13 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         fetch_loc(min(3, last), B);
         __builtin_amdgcn_sched_barrier(0);
         int pass = 0;
-        for (; pass + 1 < npass; pass += 2) {
-            step(pass, A, B, B, masked);
-            step(pass + 1, B, A, A, masked);
+        if (npass >= 2) {                                         // (as above)
+            step(0, A, B, B, masked);
+            step(1, B, A, A, masked);
+            for (pass = 2; pass + 1 < npass; pass += 2) {
+                step(pass, A, B, B, masked);
+                step(pass + 1, B, A, A, masked);
+            }
         }
         if (pass < npass) step(pass, A, B, B, masked);            // odd march: one more pass (what it prepares beyond the end is not used)
     };

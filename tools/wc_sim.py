@@ -107,7 +107,8 @@ def histogram(patch=(1, 2, 4), hbits=(2, 2, 3), waves=60):
             orph.append(no)
     ns, orph = np.array(ns), np.array(orph)
     return {'mean_n': float(ns.mean()), 'p_n_gt16': float((ns > 16).mean()), 'p_n_gt24': float((ns > 24).mean()), 'p_n_gt32': float((ns > 32).mean()),
-            'p_n_gt40': float((ns > 40).mean()), 'p_orph_gt8': float((orph > 8).mean()), 'p_orph_gt16': float((orph > 16).mean()), 'max_n': int(ns.max())}
+            'p_n_gt40': float((ns > 40).mean()), 'p_orph_gt8': float((orph > 8).mean()), 'p_orph_gt16': float((orph > 16).mean()), 'max_n': int(ns.max()),
+            'p_groups_of_8': [round(float(x), 4) for x in np.bincount(-(-ns // 8), minlength=9) / ns.size]}    # P(ceil(n / 8) = 0 .. 8)
 
 
 if '--hist' in sys.argv:
