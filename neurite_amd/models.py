@@ -13,7 +13,13 @@ parameters keep the Keras layouts (Conv kernel [k.., Cin, Cout], bias [Cout]) so
 one to one.  Forward runs on the HIP kernels of csrc/conv.hip: Conv3D = MFMA implicit GEMM (fp32), with
 UpSampling3D + concatenate fused into the following convolution's loader and the final 1x1 conv fused
 with the channel softmax.  1-D / 2-D nets are lifted to 3-D with unit leading dimensions.
-Inference only: Dropout is the identity, BatchNormalization uses its moving statistics.
+
+One interpreter, `ConvNet._interpret`, walks the op list in three modes that differ only in the primitives it is handed:
+  float32 inference (eval mode or grad disabled): Dropout is the identity, BatchNormalization uses its moving statistics; with
+               `fold_head` the first layer's max-pooling, the last decoder convolution and the soft-max head fold into their neighbours
+  float32 training (`model.train()` with grad enabled): every op is recorded through the autograd functions below (csrc/conv_bwd.hip),
+               Dropout draws, BatchNormalization uses and updates the batch statistics
+  bfloat16 inference: the same glue wrappers, which pick the *_bf16 entry points from the tensor's dtype
 
 bfloat16 inference (csrc/conv_bf16.hip): a ConvNet whose parameters and buffers are all torch.bfloat16 (`net.bfloat16()`,
 `net.to(dev, torch.bfloat16)`), in eval mode or with grad disabled, runs on bf16 kernels end to end with the semantics of
@@ -38,6 +44,7 @@ import inspect
 import json
 import math
 import sys
+import types
 import warnings
 
 import numpy as np
@@ -53,8 +60,7 @@ __all__ = ['unet', 'conv_enc', 'conv_dec', 'conv_block', 'ConvNet', 'labels_to_i
 # element-wise activations, codes of include/neurite_amd.h (nrt_activation); definitions follow tf.keras.activations -- the reference
 # hands the string straight to Keras (neurite/tf/models.py:1346, 1429, 1507, 1588)
 _ACTS = {None: 0, 'linear': 0, 'elu': 1, 'relu': 2, 'sigmoid': 3, 'tanh': 4, 'softplus': 5, 'softsign': 6, 'selu': 7,
-         'exponential': 8, 'hard_sigmoid': 9, 'leaky_relu': 10}
-_EW_ACTS = _ACTS                              # stand-alone Activation layers (nrt_add_act_affine_f32) take the same set
+         'exponential': 8, 'hard_sigmoid': 9, 'leaky_relu': 10}  # stand-alone Activation layers (nrt_add_act_affine_*) take the same set
 _ACT_MUL_B = 0x100
 _ACT_LAST_FUSED = 2          # elu, relu are fused into the conv / LocallyConnected3D epilogues; the others run as an element-wise pass
 
@@ -80,6 +86,18 @@ def _pbf(t):
     if t is not None and t.dtype != torch.bfloat16:
         raise NotImplementedError('the bf16 kernels take bfloat16 tensors, got %s' % t.dtype)
     return _lib.ptr(t)
+
+
+# the glue kernels exist once per compute dtype: entry-point suffix and the pointer check of that dtype's tensors
+_BY_DTYPE = {torch.float32: ('_f32', _p32), torch.bfloat16: ('_bf16', _pbf)}
+
+
+def _glue(stem, t):
+    """(entry point, its name, pointer check) of the glue kernel `stem` for the dtype of tensor `t`; outputs take t's dtype"""
+    if t.dtype not in _BY_DTYPE:
+        _p32(t)                                   # raises: no kernel family takes this dtype
+    suffix, p = _BY_DTYPE[t.dtype]
+    return getattr(_lib.lib(), stem + suffix), stem + suffix, p
 
 
 def _triple(v, ndims, what):
@@ -219,12 +237,7 @@ class _Conv(nn.Module):
         limit = math.sqrt(6.0 / (fan * self.cin + fan * self.cout))
         self.kernel = nn.Parameter((torch.rand(*k, self.cin, self.cout) * 2 - 1) * limit)
         self.bias = nn.Parameter(torch.zeros(self.cout))
-        self._packed = None
-        self._packed_version = None
-        self._packed_up2 = None                      # folded weights of the decoder form (see _run), keyed like _packed + c0
-        self._packed_up2_version = None
-        self._packed_bf16 = None                     # bf16 weights in v_mfma_f32_16x16x32_bf16 operand order (run_bf16)
-        self._packed_bf16_version = None
+        self._packs = {}                             # {slot: (key, tensor)} of the kernel-ready weight copies, see _pack
         self.fold_backward = True                    # decoder form: differentiate the up-sampled channels on the low-resolution grid
         self.max_norm = None                         # Keras kernel_constraint=MaxNorm(max_norm, axis=0); ConvNet.apply_constraints
 
@@ -233,12 +246,7 @@ class _Conv(nn.Module):
         (`_version`), a new storage and a device move; writes through `.data` (EMA / weight averaging: `p.data.mul_()`)
         bump no version, so the copy is also dropped on every `train()` / `eval()` switch, `set_weights`, `load_weights` and
         `load_state_dict`, and it is never used while the model is in training mode."""
-        self._packed = None
-        self._packed_version = None
-        self._packed_up2 = None
-        self._packed_up2_version = None
-        self._packed_bf16 = None
-        self._packed_bf16_version = None
+        self._packs.clear()
 
     def train(self, mode=True):
         self.invalidate_packed()
@@ -248,11 +256,21 @@ class _Conv(nn.Module):
         self.invalidate_packed()
         return super()._load_from_state_dict(*args, **kwargs)
 
+    def _pack(self, slot, key, build, while_training=False):
+        """the tensor cached in `slot` if it was built for `key`, else `build()`, cached under `key`.  The copies derived from this
+        layer's kernel are never served in training mode (training loops may write through .data between steps)."""
+        if self.training and not while_training:
+            self._packs.pop(slot, None)
+        hit = self._packs.get(slot)
+        if hit is None or hit[0] != key:
+            hit = self._packs[slot] = (key, build())
+        return hit[1]
+
+    def _kernel_key(self, *more):
+        return (self.kernel._version, self.kernel.data_ptr(), self.kernel.device) + more
+
     def _packed_weights(self):
-        ver = (self.kernel._version, self.kernel.data_ptr(), self.kernel.device)
-        if self.training:
-            self._packed = None                       # training loops may write through .data between steps
-        if self._packed is None or self._packed_version != ver:
+        def build():
             lib = _lib.lib()
             dev = self.kernel.device
             n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(self.ksize3), self.cin, self.cout)
@@ -261,16 +279,13 @@ class _Conv(nn.Module):
                 rc = lib.nrt_conv3d_pack_weights_f32(_p32(self.kernel.detach().contiguous()), _lib.ints(self.ksize3),
                                                      self.cin, self.cout, _p32(packed), _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-            self._packed, self._packed_version = packed, ver
-        return self._packed
+            return packed
+        return self._pack('packed', self._kernel_key(), build)
 
     def _packed_weights_up2(self, c0):
         """the kernel folded for nrt_conv3d_up2_f32: skip channels [0, c0) keep their 27 taps, the up-sampled channels
         get 8 parity classes x 8 taps of pre-summed weights"""
-        ver = (self.kernel._version, self.kernel.data_ptr(), self.kernel.device, int(c0))
-        if self.training:
-            self._packed_up2 = None
-        if self._packed_up2 is None or self._packed_up2_version != ver:
+        def build():
             lib = _lib.lib()
             dev = self.kernel.device
             n = lib.nrt_conv3d_up2_packed_weight_floats(int(c0), self.cin - int(c0), self.cout)
@@ -279,8 +294,8 @@ class _Conv(nn.Module):
                 rc = lib.nrt_conv3d_up2_pack_weights_f32(_p32(self.kernel.detach().contiguous()), int(c0), self.cin - int(c0),
                                                          self.cout, _p32(packed), _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_up2_pack_weights_f32')
-            self._packed_up2, self._packed_up2_version = packed, ver
-        return self._packed_up2
+            return packed
+        return self._pack('up2', self._kernel_key(int(c0)), build)
 
     def forward(self, x, lo=None, up=None, variant=0):
         """x [B, X, Y, Z, c0]; optional lo [B, X/up, Y/up, Z/up, c1] is nearest-upsampled and concatenated after x.
@@ -331,16 +346,16 @@ class _Conv(nn.Module):
 
     def _packed_head(self, head_kernel, labels, dev):
         """the head's kernel in matrix-core fragment order, repacked when the parameter changes (version counter)"""
-        key = (head_kernel.data_ptr(), head_kernel._version, str(dev))
-        if getattr(self, '_head_pack_key', None) != key:
+        def build():
             lib = _lib.lib()
             src = head_kernel.detach().reshape(-1, labels).contiguous()
             packed = torch.empty(16 * labels, dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(lib.nrt_conv3d_up2_head_pack_f32(_p32(src), labels, _p32(packed), _lib.stream_ptr(dev)),
                            'nrt_conv3d_up2_head_pack_f32')
-            self._head_pack, self._head_pack_key = packed, key
-        return self._head_pack
+            return packed
+        # keyed by the head's kernel, not this layer's: served in any mode (run_with_head is inference only)
+        return self._pack('head', (head_kernel.data_ptr(), head_kernel._version, str(dev)), build, while_training=True)
 
     def run_with_head(self, x, lo, head_kernel, head_bias):
         """softmax(act(this decoder convolution) @ head_kernel + head_bias) in one kernel (nrt_conv3d_up2_head_f32); the caller has
@@ -362,11 +377,8 @@ class _Conv(nn.Module):
 
     def _packed_weights_bf16(self):
         """the bf16 kernel in the A-operand order of v_mfma_f32_16x16x32_bf16 (nrt_conv3d_pack_weights_bf16); keyed and dropped
-        like _packed (invalidate_packed), plus the dtype"""
-        ver = (self.kernel._version, self.kernel.data_ptr(), self.kernel.device, self.kernel.dtype)
-        if self.training:
-            self._packed_bf16 = None
-        if self._packed_bf16 is None or self._packed_bf16_version != ver:
+        like the 'packed' slot (_pack, invalidate_packed), plus the dtype"""
+        def build():
             lib = _lib.lib()
             dev = self.kernel.device
             n = lib.nrt_conv3d_packed_weight_bytes_bf16(_lib.ints(self.ksize3), self.cin, self.cout)
@@ -375,14 +387,12 @@ class _Conv(nn.Module):
                 rc = lib.nrt_conv3d_pack_weights_bf16(_pbf(self.kernel.detach().contiguous()), _lib.DT_BF16, _lib.ints(self.ksize3),
                                                       self.cin, self.cout, _lib.ptr(packed), _lib.stream_ptr(dev))
             _lib.check(rc, 'nrt_conv3d_pack_weights_bf16')
-            self._packed_bf16, self._packed_bf16_version = packed, ver
-        return self._packed_bf16
+            return packed
+        return self._pack('bf16', self._kernel_key(self.kernel.dtype), build)
 
-    def run_bf16(self, x, lo=None, up=None):
-        """act(conv(concat(x, upsample(lo)))) on bf16 tensors (nrt_conv3d_bf16): exact products, float32 accumulation, bias and
-        ELU / ReLU in float32, one rounding; any other activation as a pass of its own, a softmax activation as its own kernel"""
-        lib = _lib.lib()
-        dev = _lib.require_device(x, lo, self.kernel)
+    def _geometry(self, x, lo, up):
+        """what _run and run_bf16 check before they launch: (x, lo) contiguous, their channel counts c0, c1, batch B, input size S
+        and output size O"""
         x = x.contiguous()
         c0 = x.shape[-1]
         c1 = 0 if lo is None else lo.shape[-1]
@@ -395,6 +405,14 @@ class _Conv(nn.Module):
                 raise ValueError('%s: skip %s and up-sampled %s x %s shapes do not match'
                                  % (self.layer_name, S, list(lo.shape[1:4]), up))
         O = S if self.padding == 'same' else [S[d] - (self.ksize3[d] - 1) * self.dilation for d in range(3)]
+        return x, lo, c0, c1, B, S, O
+
+    def run_bf16(self, x, lo=None, up=None):
+        """act(conv(concat(x, upsample(lo)))) on bf16 tensors (nrt_conv3d_bf16): exact products, float32 accumulation, bias and
+        ELU / ReLU in float32, one rounding; any other activation as a pass of its own, a softmax activation as its own kernel"""
+        lib = _lib.lib()
+        dev = _lib.require_device(x, lo, self.kernel)
+        x, lo, c0, c1, B, S, O = self._geometry(x, lo, up)
         out = torch.empty([B] + O + [self.cout], dtype=torch.bfloat16, device=dev)
         bias = self.bias.detach().to(torch.float32).contiguous()          # exact: every bf16 value is a float32
         with torch.cuda.device(dev):
@@ -404,9 +422,9 @@ class _Conv(nn.Module):
                                      self.act if self.act <= _ACT_LAST_FUSED else 0, _lib.stream_ptr(dev))
         _lib.check(rc, 'nrt_conv3d_bf16')
         if self.act > _ACT_LAST_FUSED:
-            out = _elementwise_bf16(out, act=self.act)
+            out = _elementwise(out, act=self.act)
         if self.post_softmax:
-            out = _softmax_bf16(out)
+            out = _softmax(out)
         return out
 
     def _run(self, x, lo=None, up=None, variant=0):
@@ -414,21 +432,7 @@ class _Conv(nn.Module):
         dev = _lib.require_device(x, lo, self.kernel)
         if x.dtype != torch.float32:
             raise NotImplementedError('the HIP conv path is float32')
-        x = x.contiguous()
-        c0 = x.shape[-1]
-        c1 = 0 if lo is None else lo.shape[-1]
-        if c0 + c1 != self.cin:
-            raise ValueError('%s expects %d input channels, got %d' % (self.layer_name, self.cin, c0 + c1))
-        B, S = x.shape[0], list(x.shape[1:4])
-        if lo is not None:
-            lo = lo.contiguous()
-            if [S[d] // up[d] for d in range(3)] != list(lo.shape[1:4]) or any(S[d] % up[d] for d in range(3)):
-                raise ValueError('%s: skip %s and up-sampled %s x %s shapes do not match'
-                                 % (self.layer_name, S, list(lo.shape[1:4]), up))
-        if self.padding == 'same':
-            O = S
-        else:
-            O = [S[d] - (self.ksize3[d] - 1) * self.dilation for d in range(3)]
+        x, lo, c0, c1, B, S, O = self._geometry(x, lo, up)
         out = torch.empty([B] + O + [self.cout], dtype=torch.float32, device=dev)
         w = self.kernel.detach().contiguous()
         # decoder form (UpSampling3D(2) + concatenate + 3x3x3 SAME): the up-sampled half runs as 8 folded taps on the
@@ -571,19 +575,20 @@ class _BatchNorm(nn.Module):
         self.register_buffer('moving_variance', torch.ones(channels))
 
 
+# The glue layers, float32 or bf16 by the dtype of their first tensor (_glue; bf16 forms in csrc/conv_bf16.hip: float32 arithmetic
+# from the bf16 operands, one rounding; pooling and up-sampling exact).  scale, shift and bias are float32 for both.
 def _elementwise(a, b=None, scale=None, shift=None, act=0, mul=False):
     """act(a + b) * scale + shift, or with mul act(a) * b"""
     if mul:
         act = int(act) | _ACT_MUL_B
-    lib = _lib.lib()
     dev = _lib.require_device(a, b)
+    fn, what, p = _glue('nrt_add_act_affine', a)
     a = a.contiguous()
     b = None if b is None else b.contiguous()
     y = torch.empty_like(a)
     with torch.cuda.device(dev):
-        rc = lib.nrt_add_act_affine_f32(_p32(a), _p32(b), _p32(scale), _p32(shift), _p32(y),
-                                        a.numel(), a.shape[-1], int(act), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_add_act_affine_f32')
+        rc = fn(p(a), p(b), _p32(scale), _p32(shift), p(y), a.numel(), a.shape[-1], int(act), _lib.stream_ptr(dev))
+    _lib.check(rc, what)
     return y
 
 
@@ -683,23 +688,22 @@ def _maxnorm(w, max_value, eps=1e-7):
 
 
 def _maxpool(x, pool3, padding):
-    lib = _lib.lib()
     dev = _lib.require_device(x)
+    fn, what, p = _glue('nrt_maxpool3d', x)
     x = x.contiguous()
     B, S, C = x.shape[0], list(x.shape[1:4]), x.shape[-1]
     same = padding == 'same'
     O = [(S[d] + pool3[d] - 1) // pool3[d] if same else S[d] // pool3[d] for d in range(3)]
-    y = torch.empty([B] + O + [C], dtype=torch.float32, device=dev)
+    y = torch.empty([B] + O + [C], dtype=x.dtype, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_maxpool3d_f32(_p32(x), _p32(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same),
-                                   _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_maxpool3d_f32')
+        rc = fn(p(x), p(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same), _lib.stream_ptr(dev))
+    _lib.check(rc, what)
     return y
 
 
 def _upsample_concat(skip, lo, up3):
-    lib = _lib.lib()
     dev = _lib.require_device(skip, lo)
+    fn, what, p = _glue('nrt_upsample_concat', lo)
     lo = lo.contiguous()
     B, S1, c1 = lo.shape[0], list(lo.shape[1:4]), lo.shape[-1]
     S = [S1[d] * up3[d] for d in range(3)]
@@ -708,117 +712,39 @@ def _upsample_concat(skip, lo, up3):
         skip = skip.contiguous()
         if list(skip.shape[1:4]) != S:
             raise ValueError('concatenate: shapes %s and %s do not match' % (list(skip.shape[1:4]), S))
-    y = torch.empty([B] + S + [c0 + c1], dtype=torch.float32, device=dev)
+    y = torch.empty([B] + S + [c0 + c1], dtype=lo.dtype, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.nrt_upsample_concat_f32(_p32(skip), c0, _p32(lo), c1, _p32(y), B, _lib.ints(S),
-                                         _lib.ints(up3), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_upsample_concat_f32')
+        rc = fn(p(skip), c0, p(lo), c1, p(y), B, _lib.ints(S), _lib.ints(up3), _lib.stream_ptr(dev))
+    _lib.check(rc, what)
     return y
 
 
-def _conv1x1_softmax(x, kernel, bias, softmax, act):
-    lib = _lib.lib()
+def _conv1x1_softmax(x, kernel, bias, softmax, act=0):
+    """a 1x1x1 convolution (the likelihood layer, cout <= 64) with the channel softmax optionally fused: float32 logits"""
     dev = _lib.require_device(x, kernel)
+    fn, what, p = _glue('nrt_conv1x1_softmax', x)
     x = x.contiguous()
     cin, cout = kernel.shape[-2], kernel.shape[-1]
-    y = torch.empty(list(x.shape[:-1]) + [cout], dtype=torch.float32, device=dev)
+    y = torch.empty(list(x.shape[:-1]) + [cout], dtype=x.dtype, device=dev)
     w = kernel.detach().reshape(cin, cout).contiguous()
+    b = bias.detach().to(torch.float32).contiguous()             # (itself for a float32 bias; exact: every bf16 value is a float32)
     fused = int(act) if int(act) <= _ACT_LAST_FUSED else 0       # elu / relu ride in the epilogue, the others as a pass of their own
     if softmax and fused != int(act):
         raise NotImplementedError('a 1x1x1 convolution with a non-fused activation followed by the channel softmax')
     with torch.cuda.device(dev):
-        rc = lib.nrt_conv1x1_softmax_f32(_p32(x), _p32(w), _p32(bias.detach()), _p32(y),
-                                         x.numel() // cin, cin, cout, int(softmax), fused, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv1x1_softmax_f32')
+        rc = fn(p(x), p(w), _p32(b), p(y), x.numel() // cin, cin, cout, int(softmax), fused, _lib.stream_ptr(dev))
+    _lib.check(rc, what)
     return y if fused == int(act) else _elementwise(y, act=int(act))
 
 
 def _softmax(x):
-    lib = _lib.lib()
     dev = _lib.require_device(x)
+    fn, what, p = _glue('nrt_softmax_lastdim', x)
     x = x.contiguous()
     y = torch.empty_like(x)
     with torch.cuda.device(dev):
-        rc = lib.nrt_softmax_lastdim_f32(_p32(x), _p32(y), x.numel() // x.shape[-1], x.shape[-1],
-                                         _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_softmax_lastdim_f32')
-    return y
-
-
-# bf16 forms of the glue layers (csrc/conv_bf16.hip): float32 arithmetic from the bf16 operands, one rounding; pooling and
-# up-sampling exact
-def _elementwise_bf16(a, b=None, scale=None, shift=None, act=0, mul=False):
-    """act(a + b) * scale + shift, or with mul act(a) * b; scale / shift float32"""
-    if mul:
-        act = int(act) | _ACT_MUL_B
-    lib = _lib.lib()
-    dev = _lib.require_device(a, b)
-    a = a.contiguous()
-    b = None if b is None else b.contiguous()
-    y = torch.empty_like(a)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_add_act_affine_bf16(_pbf(a), _pbf(b), _p32(scale), _p32(shift), _pbf(y), a.numel(), a.shape[-1], int(act),
-                                         _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_add_act_affine_bf16')
-    return y
-
-
-def _maxpool_bf16(x, pool3, padding):
-    lib = _lib.lib()
-    dev = _lib.require_device(x)
-    x = x.contiguous()
-    B, S, C = x.shape[0], list(x.shape[1:4]), x.shape[-1]
-    same = padding == 'same'
-    O = [(S[d] + pool3[d] - 1) // pool3[d] if same else S[d] // pool3[d] for d in range(3)]
-    y = torch.empty([B] + O + [C], dtype=torch.bfloat16, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_maxpool3d_bf16(_pbf(x), _pbf(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_maxpool3d_bf16')
-    return y
-
-
-def _upsample_concat_bf16(skip, lo, up3):
-    lib = _lib.lib()
-    dev = _lib.require_device(skip, lo)
-    lo = lo.contiguous()
-    B, S1, c1 = lo.shape[0], list(lo.shape[1:4]), lo.shape[-1]
-    S = [S1[d] * up3[d] for d in range(3)]
-    c0 = 0 if skip is None else skip.shape[-1]
-    if skip is not None:
-        skip = skip.contiguous()
-        if list(skip.shape[1:4]) != S:
-            raise ValueError('concatenate: shapes %s and %s do not match' % (list(skip.shape[1:4]), S))
-    y = torch.empty([B] + S + [c0 + c1], dtype=torch.bfloat16, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_upsample_concat_bf16(_pbf(skip), c0, _pbf(lo), c1, _pbf(y), B, _lib.ints(S), _lib.ints(up3), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_upsample_concat_bf16')
-    return y
-
-
-def _conv1x1_softmax_bf16(x, kernel, bias, softmax):
-    """the likelihood layer (linear 1x1x1 convolution, cout <= 64) with the channel softmax optionally fused: float32 logits"""
-    lib = _lib.lib()
-    dev = _lib.require_device(x, kernel)
-    x = x.contiguous()
-    cin, cout = kernel.shape[-2], kernel.shape[-1]
-    y = torch.empty(list(x.shape[:-1]) + [cout], dtype=torch.bfloat16, device=dev)
-    w = kernel.detach().reshape(cin, cout).contiguous()
-    b = bias.detach().to(torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        rc = lib.nrt_conv1x1_softmax_bf16(_pbf(x), _pbf(w), _lib.ptr(b), _pbf(y), x.numel() // cin, cin, cout, int(softmax), 0,
-                                          _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv1x1_softmax_bf16')
-    return y
-
-
-def _softmax_bf16(x):
-    lib = _lib.lib()
-    dev = _lib.require_device(x)
-    x = x.contiguous()
-    y = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_softmax_lastdim_bf16(_pbf(x), _pbf(y), x.numel() // x.shape[-1], x.shape[-1], _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_softmax_lastdim_bf16')
+        rc = fn(p(x), p(y), x.numel() // x.shape[-1], x.shape[-1], _lib.stream_ptr(dev))
+    _lib.check(rc, what)
     return y
 
 
@@ -1746,11 +1672,6 @@ class ConvNet(nn.Module):
                                               'net.bfloat16())' % (name, t.dtype, first))
         return first or torch.float32
 
-    def _affine(self, bn):
-        scale = bn.gamma.detach() / torch.sqrt(bn.moving_variance + bn.epsilon)
-        shift = bn.beta.detach() - bn.moving_mean * scale
-        return scale.contiguous(), shift.contiguous()
-
     def forward(self, inputs, return_tensors=None, _noise=None):
         """inputs: [B, *spatial, C] (or a list for multi-input nets).  Returns the prediction tensor
         (or a dict of the named intermediate tensors listed in return_tensors).  _noise: {sampling layer name: tensor} replaces the
@@ -1775,78 +1696,77 @@ class ConvNet(nn.Module):
             _lib.require_device(x)
             if tuple(x.shape[1:]) != tuple(shp):
                 raise ValueError('input shape %s does not match the model input %s' % (tuple(x.shape[1:]), tuple(shp)))
+        if bf16:
+            mode = _BF16
+        elif self.training and torch.is_grad_enabled():
+            mode = _TRAIN
+        else:
+            mode = _F32
+        return self._interpret(mode, xs, set(return_tensors or []), return_tensors)
+
+    def _interpret(self, mode, xs, keep, return_tensors):
+        """The one walk over the op list.  `mode` (_F32, _BF16 or _TRAIN below the class) holds what differs between float32
+        inference, bf16 inference (module docstring: rounding points) and autograd recording: the input dtype, one primitive per glue
+        layer, and the conv / likelihood / dropout handlers, which fold, defer or draw in their own ways.  Which tensors an op reads,
+        where its result goes and what `keep` (the names in return_tensors) forces to be materialised is decided here."""
         nd = self.ndims
         t = {}
-        keep = set(return_tensors or [])
-        if bf16:
-            return self._forward_bf16(xs, keep, return_tensors)
-        if self.training and torch.is_grad_enabled():
-            return self._forward_train(xs, keep, return_tensors)
-        with torch.no_grad():
+        if mode.recording:
+            self.last_dropout_scales = {}
+            self.last_dropout_masks = {}
+        with torch.set_grad_enabled(mode.recording):
             for op in self.ops:
                 kind, name = op['kind'], op['name']
                 if kind == 'input':
-                    t[name] = _lift(xs[op['index']].to(torch.float32), nd)
+                    t[name] = _lift(xs[op['index']].to(mode.dtype), nd)
                 elif kind == 'input_concat':
-                    t[name] = torch.cat([t[s] for s in op['src']], -1).contiguous()      # host glue (rare)
+                    t[name] = torch.cat([t[s] for s in op['src']], -1).contiguous()      # host glue (rare), exact
                 elif kind == 'conv':
-                    lo = t[op['lo']] if op.get('lo') else None
-                    head = self._head_of.get(name) if self.fold_head and name not in keep else None
-                    pool = self._pool_of.get(name) if self.fold_head else None
-                    if head is not None and head not in keep and self._head_foldable(name, head, t[op['src']], lo, op.get('up')):
-                        t[name] = _PendingConv(t[op['src']], lo)      # runs inside the likelihood op below: one kernel, no feature tensor
-                    elif pool is not None and lo is None and self.layers_by_name[name].pool_foldable(t[op['src']], self.conv_variant):
-                        t[name], t[pool] = self.layers_by_name[name].run_with_pool(t[op['src']])   # the pooled tensor from the same kernel
-                    else:
-                        t[name] = self.layers_by_name[name](t[op['src']], lo=lo, up=op.get('up'),
-                                                            variant=self.conv_variant)
+                    src, lo = t[op['src']], (t[op['lo']] if op.get('lo') else None)
+                    if mode.conv_reads_merge and lo is not None and t.get(op['merge']) is not None:
+                        src, lo = t[op['merge']], None                                    # the materialised concatenation
+                    mode.conv(self, op, src, lo, t, keep)
                 elif kind == 'dropout':
-                    t[name] = t[op['src']]                                                # inference: identity
+                    t[name] = mode.dropout(self, op, t[op['src']])
                 elif kind == 'maxpool':
                     if t.get(name) is None:                                               # (else: produced by the convolution in front of it)
-                        t[name] = _maxpool(t[op['src']], op['pool'], op['padding'])
+                        t[name] = mode.maxpool(t[op['src']], op['pool'], op['padding'])
                 elif kind == 'upsample':
-                    t[name] = _upsample_concat(None, t[op['src']], op['up'])
+                    t[name] = mode.merge(None, t[op['src']], op['up'])
                 elif kind == 'merge':
-                    if op.get('fused') and name not in keep:
+                    if op.get('fused') and name not in keep and (self.fold_head or not mode.merge_needs_fold_head):
                         t[name] = None            # consumed by the next conv's loader (skip + lo), never materialised
                     else:
-                        t[name] = _upsample_concat(t[op['skip']], t[op['lo']], op['up'])
+                        t[name] = mode.merge(t[op['skip']], t[op['lo']], op['up'])
                 elif kind == 'add':
-                    t[name] = _elementwise(t[op['a']], t[op['b']])
+                    t[name] = mode.add_act(t[op['a']], t[op['b']], 0)
                 elif kind == 'activation':
-                    t[name] = _elementwise(t[op['src']], act=_EW_ACTS[op['activation']])
+                    t[name] = mode.add_act(t[op['src']], None, _ACTS[op['activation']])
                 elif kind == 'multiply':
-                    t[name] = _elementwise(t[op['a']], t[op['b']], mul=True)
+                    t[name] = mode.mul(t[op['a']], t[op['b']])
                 elif kind == 'bn':
-                    scale, shift = self._affine(self.layers_by_name[name])
-                    t[name] = _elementwise(t[op['src']], scale=scale, shift=shift)
+                    t[name] = mode.bn(t[op['src']], self.layers_by_name[name])
                 elif kind == 'likelihood':
-                    m = self.layers_by_name[name]
-                    if isinstance(t[op['src']], _PendingConv):
-                        pc = t[op['src']]
-                        t[name] = None
-                        t[op['pred_name']] = self.layers_by_name[op['src']].run_with_head(pc.x, pc.lo, m.kernel, m.bias)
-                        t[op['src']] = None
-                    elif op.get('fuse_softmax'):
-                        t[name] = _conv1x1_softmax(t[op['src']], m.kernel, m.bias, False, 0) if name in keep else None
-                        t[op['pred_name']] = _conv1x1_softmax(t[op['src']], m.kernel, m.bias, True, 0)
-                    else:
-                        t[name] = _conv1x1_softmax(t[op['src']], m.kernel, m.bias, False, 0) \
-                            if m.cout <= 64 else m(t[op['src']])
+                    mode.likelihood(self, op, t, keep)
                 elif kind == 'prediction':
-                    if name in t and t[name] is not None:
+                    if t.get(name) is not None:
                         pass                                    # produced by the fused likelihood
                     elif op['activation'] == 'softmax':
-                        t[name] = _softmax(t[op['src']])
+                        t[name] = mode.softmax(t[op['src']])
+                    elif mode.recording and op['activation'] in (None, 'linear'):
+                        t[name] = t[op['src']]                  # (inference copies instead: the prediction is a tensor of its own)
                     else:
-                        t[name] = _elementwise(t[op['src']], act=_act_code(op['activation']))
+                        t[name] = mode.add_act(t[op['src']], None, _act_code(op['activation']))
                 elif kind in _AE_KINDS:
                     self._ae_op(op, t)
                 elif kind in _CLS_KINDS:
-                    self._cls_op(op, t, False)
+                    self._cls_op(op, t, mode.recording)
+                elif mode.recording:
+                    raise NotImplementedError('neurite_amd: training through %r layers (%s) is not implemented' % (kind, name))
                 else:
                     raise RuntimeError('unknown op ' + kind)
+        # (bf16 included: every builder that marks an op 'flat' or gives it a 'keras_shape' also adds an auto-encoder or classifier
+        # op, and forward() refuses those for a bf16 network)
         if return_tensors:
             return {k: self._unlift_named(k, t[k]) for k in keep}
         return self._unlift_named(self.output_name, t[self.output_name])
@@ -1918,144 +1838,95 @@ class ConvNet(nn.Module):
         else:
             raise RuntimeError('unknown op ' + kind)
 
-    def _forward_bf16(self, xs, keep, return_tensors):
-        """inference of a bf16 network on the bf16 kernels (module docstring: rounding points).  With fold_head every merge whose
-        only reader is the next convolution runs in that convolution's loader and the likelihood + softmax as one kernel; without
-        it every layer is materialised."""
-        nd = self.ndims
-        t = {}
-        fold = self.fold_head
-        with torch.no_grad():
-            for op in self.ops:
-                kind, name = op['kind'], op['name']
-                if kind == 'input':
-                    t[name] = _lift(xs[op['index']].to(torch.bfloat16), nd)
-                elif kind == 'input_concat':
-                    t[name] = torch.cat([t[s] for s in op['src']], -1).contiguous()      # host glue (rare), exact
-                elif kind == 'conv':
-                    m = self.layers_by_name[name]
-                    src, lo = t[op['src']], (t[op['lo']] if op.get('lo') else None)
-                    if lo is not None and t.get(op['merge']) is not None:
-                        src, lo = t[op['merge']], None                                    # the materialised concatenation
-                    t[name] = m.run_bf16(src, lo, op.get('up'))
-                elif kind == 'dropout':
-                    t[name] = t[op['src']]
-                elif kind == 'maxpool':
-                    t[name] = _maxpool_bf16(t[op['src']], op['pool'], op['padding'])
-                elif kind == 'upsample':
-                    t[name] = _upsample_concat_bf16(None, t[op['src']], op['up'])
-                elif kind == 'merge':
-                    if op.get('fused') and fold and name not in keep:
-                        t[name] = None            # read by the next convolution's loader
-                    else:
-                        t[name] = _upsample_concat_bf16(t[op['skip']], t[op['lo']], op['up'])
-                elif kind == 'add':
-                    t[name] = _elementwise_bf16(t[op['a']], t[op['b']])
-                elif kind == 'activation':
-                    t[name] = _elementwise_bf16(t[op['src']], act=_EW_ACTS[op['activation']])
-                elif kind == 'multiply':
-                    t[name] = _elementwise_bf16(t[op['a']], t[op['b']], mul=True)
-                elif kind == 'bn':
-                    bn = self.layers_by_name[name]
-                    scale = bn.gamma.detach().float() / torch.sqrt(bn.moving_variance.float() + bn.epsilon)
-                    shift = bn.beta.detach().float() - bn.moving_mean.float() * scale
-                    t[name] = _elementwise_bf16(t[op['src']], scale=scale.contiguous(), shift=shift.contiguous())
-                elif kind == 'likelihood':
-                    m = self.layers_by_name[name]
-                    if op.get('fuse_softmax') and fold and name not in keep:
-                        t[name] = None
-                        t[op['pred_name']] = _conv1x1_softmax_bf16(t[op['src']], m.kernel, m.bias, True)
-                    elif m.cout <= 64 and tuple(m.ksize3) == (1, 1, 1):
-                        t[name] = _conv1x1_softmax_bf16(t[op['src']], m.kernel, m.bias, False)
-                    else:
-                        t[name] = m.run_bf16(t[op['src']])
-                elif kind == 'prediction':
-                    if name in t and t[name] is not None:
-                        pass                                    # produced by the fused likelihood
-                    elif op['activation'] == 'softmax':
-                        t[name] = _softmax_bf16(t[op['src']])
-                    else:
-                        t[name] = _elementwise_bf16(t[op['src']], act=_act_code(op['activation']))
-                elif kind in _AE_KINDS or kind in _CLS_KINDS:   # (refused in forward(): no bf16 kernels behind these)
-                    raise NotImplementedError('%s: %s layers have no bfloat16 kernel' % (name, kind))
-                else:
-                    raise RuntimeError('unknown op ' + kind)
-        if return_tensors:
-            return {k: _unlift(t[k], nd) for k in keep}
-        return _unlift(t[self.output_name], nd)
+    # ---- the ops that differ per mode: handlers of _F32 / _BF16 / _TRAIN, called from _interpret ----
+    def _conv_f32(self, op, src, lo, t, keep):
+        name, m = op['name'], self.layers_by_name[op['name']]
+        head = self._head_of.get(name) if self.fold_head and name not in keep else None
+        pool = self._pool_of.get(name) if self.fold_head else None
+        if head is not None and head not in keep and self._head_foldable(name, head, src, lo, op.get('up')):
+            t[name] = _PendingConv(src, lo)               # runs inside the likelihood op: one kernel, no feature tensor
+        elif pool is not None and lo is None and m.pool_foldable(src, self.conv_variant):
+            t[name], t[pool] = m.run_with_pool(src)       # the pooled tensor from the same kernel
+        else:
+            t[name] = m(src, lo=lo, up=op.get('up'), variant=self.conv_variant)
 
-    def _forward_train(self, xs, keep, return_tensors):
-        """model.train(): the same graph with every op recorded for autograd (csrc/conv_bwd.hip); the likelihood conv
-        and the softmax run unfused so that the logits are available to the backward."""
-        nd = self.ndims
-        t = {}
-        self.last_dropout_scales = {}
-        self.last_dropout_masks = {}
-        for op in self.ops:
-            kind, name = op['kind'], op['name']
-            if kind == 'input':
-                t[name] = _lift(xs[op['index']].to(torch.float32), nd)
-            elif kind == 'input_concat':
-                t[name] = torch.cat([t[s] for s in op['src']], -1).contiguous()
-            elif kind == 'conv':
-                lo = t[op['lo']] if op.get('lo') else None
-                m = self.layers_by_name[name]
-                t[name] = _ConvFn.apply(t[op['src']], lo, m.kernel, m.bias, m, op.get('up'), self.conv_variant, False)
-            elif kind == 'dropout':
-                rate = float(op.get('rate', 0))
-                if rate > 0:
-                    src = t[op['src']]
-                    kept = (torch.rand((src.shape[0], src.shape[-1]), device=src.device) >= rate).to(torch.float32)
-                    scale = (kept / (1.0 - rate)).contiguous()          # [B, C] numbers: the draw is plumbing, the scaling a kernel
-                    self.last_dropout_scales[name] = scale
-                    t[name] = _ChannelScaleFn.apply(src, scale)
-                else:
-                    t[name] = t[op['src']]
-            elif kind == 'maxpool':
-                t[name] = _MaxPoolFn.apply(t[op['src']], op['pool'], op['padding'])
-            elif kind == 'upsample':
-                t[name] = _MergeFn.apply(None, t[op['src']], op['up'])
-            elif kind == 'merge':
-                if op.get('fused') and name not in keep:
-                    t[name] = None
-                else:
-                    t[name] = _MergeFn.apply(t[op['skip']], t[op['lo']], op['up'])
-            elif kind == 'bn':
-                m = self.layers_by_name[name]
-                t[name] = _BatchNormFn.apply(t[op['src']], m.gamma, m.beta, m)
-            elif kind == 'add':
-                t[name] = _AddActFn.apply(t[op['a']], t[op['b']], 0)
-            elif kind == 'activation':
-                t[name] = _AddActFn.apply(t[op['src']], None, _EW_ACTS[op['activation']])
-            elif kind == 'multiply':
-                t[name] = _MulFn.apply(t[op['a']], t[op['b']])
-            elif kind == 'likelihood':
-                m = self.layers_by_name[name]
-                if op.get('fuse_softmax') and name not in keep and m.cout <= 64 and tuple(m.ksize3) == (1, 1, 1):
-                    t[name] = None
-                    t[op['pred_name']] = _head(t[op['src']], m.kernel, m.bias, m)
-                elif m.cout <= 64:
-                    t[name] = _ConvFn.apply(t[op['src']], None, m.kernel, m.bias, m, None, 0, True)
-                else:
-                    t[name] = _ConvFn.apply(t[op['src']], None, m.kernel, m.bias, m, None, self.conv_variant, False)
-            elif kind == 'prediction':
-                if name in t and t[name] is not None:
-                    pass                                    # produced by the fused head
-                elif op['activation'] == 'softmax':
-                    t[name] = _softmax_with_grad(t[op['src']])
-                elif op['activation'] in (None, 'linear'):
-                    t[name] = t[op['src']]
-                else:
-                    t[name] = _AddActFn.apply(t[op['src']], None, _act_code(op['activation']))
-            elif kind in _AE_KINDS:
-                self._ae_op(op, t)
-            elif kind in _CLS_KINDS:
-                self._cls_op(op, t, True)
-            else:
-                raise NotImplementedError('neurite_amd: training through %r layers (%s) is not implemented' % (kind, name))
-        if return_tensors:
-            return {k: self._unlift_named(k, t[k]) for k in keep}
-        return self._unlift_named(self.output_name, t[self.output_name])
+    def _conv_bf16(self, op, src, lo, t, keep):
+        t[op['name']] = self.layers_by_name[op['name']].run_bf16(src, lo, op.get('up'))
+
+    def _conv_train(self, op, src, lo, t, keep):
+        m = self.layers_by_name[op['name']]
+        t[op['name']] = _ConvFn.apply(src, lo, m.kernel, m.bias, m, op.get('up'), self.conv_variant, False)
+
+    def _likelihood_f32(self, op, t, keep):
+        name, m, src = op['name'], self.layers_by_name[op['name']], t[op['src']]
+        if isinstance(src, _PendingConv):
+            t[name] = None
+            t[op['pred_name']] = self.layers_by_name[op['src']].run_with_head(src.x, src.lo, m.kernel, m.bias)
+            t[op['src']] = None
+        elif op.get('fuse_softmax'):
+            t[name] = _conv1x1_softmax(src, m.kernel, m.bias, False) if name in keep else None
+            t[op['pred_name']] = _conv1x1_softmax(src, m.kernel, m.bias, True)
+        else:
+            t[name] = _conv1x1_softmax(src, m.kernel, m.bias, False) if m.cout <= 64 else m(src)
+
+    def _likelihood_bf16(self, op, t, keep):
+        """with fold_head the likelihood + softmax run as one kernel; without it every layer is materialised"""
+        name, m, src = op['name'], self.layers_by_name[op['name']], t[op['src']]
+        if op.get('fuse_softmax') and self.fold_head and name not in keep:
+            t[name] = None
+            t[op['pred_name']] = _conv1x1_softmax(src, m.kernel, m.bias, True)
+        elif m.cout <= 64 and tuple(m.ksize3) == (1, 1, 1):
+            t[name] = _conv1x1_softmax(src, m.kernel, m.bias, False)
+        else:
+            t[name] = m.run_bf16(src)
+
+    def _likelihood_train(self, op, t, keep):
+        """the fused head has its own backward from the prediction alone (_HeadFn); kept logits run unfused"""
+        name, m, src = op['name'], self.layers_by_name[op['name']], t[op['src']]
+        if op.get('fuse_softmax') and name not in keep and m.cout <= 64 and tuple(m.ksize3) == (1, 1, 1):
+            t[name] = None
+            t[op['pred_name']] = _head(src, m.kernel, m.bias, m)
+        elif m.cout <= 64:
+            t[name] = _ConvFn.apply(src, None, m.kernel, m.bias, m, None, 0, True)
+        else:
+            t[name] = _ConvFn.apply(src, None, m.kernel, m.bias, m, None, self.conv_variant, False)
+
+    def _dropout_train(self, op, src):
+        rate = float(op.get('rate', 0))
+        if rate <= 0:
+            return src
+        kept = (torch.rand((src.shape[0], src.shape[-1]), device=src.device) >= rate).to(torch.float32)
+        scale = (kept / (1.0 - rate)).contiguous()          # [B, C] numbers: the draw is plumbing, the scaling a kernel
+        self.last_dropout_scales[op['name']] = scale
+        return _ChannelScaleFn.apply(src, scale)
+
+
+def _affine(bn):
+    """inference BatchNormalization as a per-channel scale and shift, formed in float32 from parameters of either dtype"""
+    scale = bn.gamma.detach().float() / torch.sqrt(bn.moving_variance.float() + bn.epsilon)
+    shift = bn.beta.detach().float() - bn.moving_mean.float() * scale
+    return scale.contiguous(), shift.contiguous()
+
+
+def _bn_inference(x, bn):
+    scale, shift = _affine(bn)
+    return _elementwise(x, scale=scale, shift=shift)
+
+
+# The three modes of ConvNet._interpret.  Inference takes the glue wrappers, which pick the float32 or bf16 kernel from the tensor;
+# recording takes the autograd functions.  bf16 materialises every merge unless fold_head, and its convolutions read a materialised
+# merge instead of repeating it in their loader.
+_INFERENCE = dict(recording=False, maxpool=_maxpool, merge=_upsample_concat, bn=_bn_inference, softmax=_softmax,
+                  add_act=lambda a, b, act: _elementwise(a, b, act=act), mul=lambda a, b: _elementwise(a, b, mul=True),
+                  dropout=lambda net, op, src: src)
+_F32 = types.SimpleNamespace(dtype=torch.float32, merge_needs_fold_head=False, conv_reads_merge=False,
+                             conv=ConvNet._conv_f32, likelihood=ConvNet._likelihood_f32, **_INFERENCE)
+_BF16 = types.SimpleNamespace(dtype=torch.bfloat16, merge_needs_fold_head=True, conv_reads_merge=True,
+                              conv=ConvNet._conv_bf16, likelihood=ConvNet._likelihood_bf16, **_INFERENCE)
+_TRAIN = types.SimpleNamespace(dtype=torch.float32, merge_needs_fold_head=False, conv_reads_merge=False, recording=True,
+                               maxpool=_MaxPoolFn.apply, merge=_MergeFn.apply, add_act=_AddActFn.apply, mul=_MulFn.apply,
+                               bn=lambda x, bn: _BatchNormFn.apply(x, bn.gamma, bn.beta, bn), softmax=_softmax_with_grad,
+                               dropout=ConvNet._dropout_train, conv=ConvNet._conv_train, likelihood=ConvNet._likelihood_train)
 
 
 # --------------------------------------------------------------------------------------

@@ -72,15 +72,24 @@ def test_bf16_model_refusals_come_before_any_device_use():
 def test_bf16_weight_cache_is_dropped_like_the_float32_one():
     m = _unet(torch.bfloat16)
     c = m.get_layer('unet_conv_downarm_0_0')
-    c._packed_bf16, c._packed_bf16_version = torch.zeros(1), ('stale',)
+    stale = torch.zeros(1)
+
+    def plant():
+        c._packs['bf16'] = (c._kernel_key(c.kernel.dtype), stale)
+
+    plant()
     m.eval()
-    assert c._packed_bf16 is None
-    c._packed_bf16 = torch.zeros(1)
+    assert 'bf16' not in c._packs
+    plant()
     m.load_state_dict(m.state_dict())
-    assert c._packed_bf16 is None
-    c._packed_bf16 = torch.zeros(1)
+    assert 'bf16' not in c._packs
+    plant()
     m.set_weights([np.zeros(tuple(t.shape), np.float32) for _, t, _ in m._weight_tensors()])
-    assert c._packed_bf16 is None
+    assert 'bf16' not in c._packs
+    plant()                                                 # a dtype change moves the key: the entry is rebuilt, not served
+    assert c._pack('bf16', c._kernel_key(c.kernel.dtype), lambda: 'fresh') is stale
+    m.float()
+    assert c._pack('bf16', c._kernel_key(c.kernel.dtype), lambda: 'fresh') == 'fresh'
 
 
 def test_end_to_end_check_rejects_a_dropped_tap():

@@ -223,10 +223,10 @@ def test_glue_kernels_bf16(dev):
     for C in (5, 16):
         x = bfr(rng.standard_normal((2, 9, 8, 7, C)))
         for pool in ((2, 2, 2), (3, 1, 2), (1, 2, 4)):
-            got = N(nm._maxpool_bf16(GB(x, dev), pool, 'same'))
+            got = N(nm._maxpool(GB(x, dev), pool, 'same'))
             for b in range(2):
                 assert np.array_equal(got[b], uo.maxpool_same(x[b], pool))
-            gotv = N(nm._maxpool_bf16(GB(x, dev), pool, 'valid'))
+            gotv = N(nm._maxpool(GB(x, dev), pool, 'valid'))
             ox, oy, oz = [s // p for s, p in zip(x.shape[1:4], pool)]
             ref = x[:, :ox * pool[0], :oy * pool[1], :oz * pool[2]].reshape(2, ox, pool[0], oy, pool[1], oz, pool[2], C).max((2, 4, 6))
             assert np.array_equal(gotv, ref)
@@ -234,7 +234,7 @@ def test_glue_kernels_bf16(dev):
         lo = bfr(rng.standard_normal((2, 3, 4, 2, c1)))
         S = [s * u for s, u in zip(lo.shape[1:4], up)]
         skip = bfr(rng.standard_normal([2] + S + [c0])) if c0 else None
-        got = N(nm._upsample_concat_bf16(GB(skip, dev) if c0 else None, GB(lo, dev), up))
+        got = N(nm._upsample_concat(GB(skip, dev) if c0 else None, GB(lo, dev), up))
         for b in range(2):
             want = uo.upsample(lo[b], up) if not c0 else np.concatenate([skip[b], uo.upsample(lo[b], up)], -1)
             assert np.array_equal(got[b], want)
@@ -242,11 +242,11 @@ def test_glue_kernels_bf16(dev):
     for C in (6, 16):
         a, b2 = bfr(rng.standard_normal((2, 4, 4, 4, C))), bfr(rng.standard_normal((2, 4, 4, 4, C)))
         sc, sh = rng.standard_normal(C).astype(F), rng.standard_normal(C).astype(F)
-        for got, want in ((nm._elementwise_bf16(GB(a, dev), GB(b2, dev), act=1), uo.elu(a.astype(np.float64) + b2)),
-                          (nm._elementwise_bf16(GB(a, dev), scale=G32(sc, dev), shift=G32(sh, dev)), a.astype(np.float64) * sc + sh),
-                          (nm._elementwise_bf16(GB(a, dev), act=3), 1 / (1 + np.exp(-a.astype(np.float64)))),
-                          (nm._elementwise_bf16(GB(a, dev), GB(b2, dev), mul=True), a.astype(np.float64) * b2),
-                          (nm._elementwise_bf16(GB(a, dev), GB(b2, dev)), a.astype(np.float64) + b2)):
+        for got, want in ((nm._elementwise(GB(a, dev), GB(b2, dev), act=1), uo.elu(a.astype(np.float64) + b2)),
+                          (nm._elementwise(GB(a, dev), scale=G32(sc, dev), shift=G32(sh, dev)), a.astype(np.float64) * sc + sh),
+                          (nm._elementwise(GB(a, dev), act=3), 1 / (1 + np.exp(-a.astype(np.float64)))),
+                          (nm._elementwise(GB(a, dev), GB(b2, dev), mul=True), a.astype(np.float64) * b2),
+                          (nm._elementwise(GB(a, dev), GB(b2, dev)), a.astype(np.float64) + b2)):
             assert got.dtype == BF
             err = np.abs(N(got) - want)
             assert np.all(err <= rel * np.abs(want) + 4e-7 * (1 + np.abs(want))), float(err.max())
@@ -254,7 +254,7 @@ def test_glue_kernels_bf16(dev):
         z = bfr(rng.standard_normal((3, 11, 13, C)) * 4)
         e = np.exp(z.astype(np.float64) - z.max(-1, keepdims=True))
         p = e / e.sum(-1, keepdims=True)
-        y = N(nm._softmax_bf16(GB(z, dev)))
+        y = N(nm._softmax(GB(z, dev)))
         assert np.all(np.abs(y - p) <= rel * p + 1e-6)
         assert np.all(np.abs(y.astype(np.float64).sum(-1) - 1) <= rel + 1e-6)
     for cin, cout in ((16, 32), (16, 4), (7, 50)):
@@ -263,11 +263,11 @@ def test_glue_kernels_bf16(dev):
         xin = bfr(rng.standard_normal((2, 5, 6, 7, cin)))
         lin = xin.astype(np.float64) @ k.reshape(cin, cout).astype(np.float64) + bb
         S = np.abs(xin.astype(np.float64)) @ np.abs(k.reshape(cin, cout)) + np.abs(bb)
-        got = N(nm._conv1x1_softmax_bf16(GB(xin, dev), GB(k, dev), GB(bb, dev), False))
+        got = N(nm._conv1x1_softmax(GB(xin, dev), GB(k, dev), GB(bb, dev), False))
         assert np.all(np.abs(got - lin) <= rel * np.abs(lin) + 9 * 2.0 ** -24 * S)
         e = np.exp(lin - lin.max(-1, keepdims=True))
         p = e / e.sum(-1, keepdims=True)
-        got = N(nm._conv1x1_softmax_bf16(GB(xin, dev), GB(k, dev), GB(bb, dev), True))
+        got = N(nm._conv1x1_softmax(GB(xin, dev), GB(k, dev), GB(bb, dev), True))
         assert np.all(np.abs(got - p) <= rel * p + 1e-6)
 
 
@@ -410,8 +410,15 @@ def test_refusals_before_launch(dev):
     with pytest.raises(NotImplementedError, match='unet_conv_uparm_3_0'):
         mixed(x)
     conv = nm._Conv('c', 4, 8, (3, 3, 3)).to(dev, BF)
+    f32, b16 = torch.zeros(8, device=dev), torch.zeros(8, device=dev, dtype=BF)
     with pytest.raises(NotImplementedError):
-        nm._elementwise(torch.zeros(8, device=dev, dtype=BF))           # a bf16 buffer never reaches an _f32 entry point
+        nm._elementwise(f32, b16)                                       # a bf16 buffer never reaches an _f32 entry point
+    with pytest.raises(NotImplementedError):
+        nm._elementwise(b16, f32)                                       # nor a float32 one a _bf16 entry point
+    with pytest.raises(NotImplementedError):
+        nm._elementwise(b16, scale=b16[:1], shift=b16[:1])              # scale and shift are float32 for both
+    with pytest.raises(NotImplementedError):
+        nm._elementwise(torch.zeros(8, device=dev, dtype=torch.float16))    # no kernel family takes any other dtype
     with pytest.raises(NotImplementedError):
         conv._run(torch.zeros(1, 4, 4, 4, 4, device=dev))
     torch.cuda.synchronize()

@@ -608,18 +608,30 @@ def test_packed_weight_cache_is_dropped_when_weights_may_have_changed():
     import contextlib, io
     with contextlib.redirect_stdout(io.StringIO()):
         net = ne.models.unet(4, (8, 8, 8, 1), 2, 3, 2)
-    convs = [m for m in net.layers_by_name.values() if hasattr(m, '_packed')]
+    convs = [m for m in net.layers_by_name.values() if hasattr(m, '_packs')]
     assert convs
 
     def poison():
-        for m in convs:
-            m._packed, m._packed_version = 'stale', (m.kernel._version, m.kernel.data_ptr(), m.kernel.device)
+        for m in convs:                                   # entries under the keys their slots are looked up with
+            key = (m.kernel._version, m.kernel.data_ptr(), m.kernel.device)
+            m._packs['packed'] = (key, 'stale')
+            m._packs['up2'] = (key + (4,), 'stale')
+            m._packs['head'] = ((m.kernel.data_ptr(), m.kernel._version, str(m.kernel.device)), 'stale')
 
     for action in (lambda: net.train(), lambda: net.eval(), lambda: net.set_weights(net.get_weights()),
                    lambda: net.load_state_dict(net.state_dict())):
         poison()
         action()
-        assert all(m._packed is None for m in convs)
+        assert all(not m._packs for m in convs)
+    # between those events: a kernel-derived slot is rebuilt for a key that moved and never served in training mode; the head's is
+    m = convs[0].eval()
+    poison()
+    key = m._packs['packed'][0]
+    assert m._pack('packed', key, lambda: 'fresh') == 'stale'
+    assert m._pack('up2', key + (8,), lambda: 'fresh') == 'fresh' and m._packs['up2'] == (key + (8,), 'fresh')
+    m.training = True                                     # (the flag alone: _Conv.train() would drop everything)
+    assert m._pack('packed', key, lambda: 'fresh') == 'fresh'
+    assert m._pack('head', m._packs['head'][0], lambda: 'fresh', while_training=True) == 'stale'
 
 
 def test_lc3d_relayout_plan_reproduces_the_reference_layer():

@@ -98,15 +98,15 @@ def layer_table(m16, x16, reps, warmup):
 
     conv('unet_conv_downarm_0_0', t['unet_input'], hbm=True)
     a = t['unet_conv_downarm_0_0']
-    mem('unet_maxpool_0', lambda: nm._maxpool_bf16(a, (2, 2, 2), 'same'), 2 * (a.numel() + a.numel() / 8))
+    mem('unet_maxpool_0', lambda: nm._maxpool(a, (2, 2, 2), 'same'), 2 * (a.numel() + a.numel() / 8))
     conv('unet_conv_downarm_1_0', t['unet_maxpool_0'])
     b = t['unet_conv_downarm_1_0']
-    mem('unet_maxpool_1', lambda: nm._maxpool_bf16(b, (2, 2, 2), 'same'), 2 * (b.numel() + b.numel() / 8))
+    mem('unet_maxpool_1', lambda: nm._maxpool(b, (2, 2, 2), 'same'), 2 * (b.numel() + b.numel() / 8))
     conv('unet_conv_downarm_2_0', t['unet_maxpool_1'])
     conv('unet_conv_uparm_3_0', t['unet_conv_downarm_1_0'], t['unet_conv_downarm_2_0'], (2, 2, 2))
     conv('unet_conv_uparm_4_0', t['unet_conv_downarm_0_0'], t['unet_conv_uparm_3_0'], (2, 2, 2))
     h, f = L['unet_likelihood'], t['unet_conv_uparm_4_0']
-    mem('unet_likelihood+prediction', lambda: nm._conv1x1_softmax_bf16(f, h.kernel, h.bias, True), 2 * (f.numel() + V * h.cout))
+    mem('unet_likelihood+prediction', lambda: nm._conv1x1_softmax(f, h.kernel, h.bias, True), 2 * (f.numel() + V * h.cout))
     return rows
 
 
