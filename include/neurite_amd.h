@@ -864,6 +864,45 @@ int nrt_patch_extract(const void *vol, int dtype, int ndim, const int *vol_shape
 int nrt_patch_quilt(const void *patches, int dtype, int ndim, const int *patch_size, const int *patch_stride, const int *grid_size,
                     int channels, int reduce, float *vol, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The registration losses of VoxelMorph (csrc/vxmloss.hip): the windowed normalised cross-correlation of two images (vxm.losses.NCC)
+ * and the smoothness penalty on a displacement field (vxm.losses.Grad), each with its gradient.  voxelmorph is not in the reference
+ * tree: the semantics are restated, not pinned.  float32, channels-last [batch, *shape, channels]; shape has three extents,
+ * a spatial rank below 3 arrives with leading extents of 1 (and window 1).  An extent smaller than the window is legal.
+ *   nrt_ncc_f32        n = prod(win) * channels.  Box sums S_I, S_J, S_II, S_JJ, S_IJ of I, J, I I, J J, I J over the window and all channels,
+ *                      stride 1, zero padded as TensorFlow's 'SAME' pads ((w - 1) / 2 zeros in front; even windows allowed); each is a plain
+ *                      sum of its terms (no running add-and-subtract: exact on small-integer images).  Then, one float32 rounding per
+ *                      operation:  uI = S_I / n, uJ = S_J / n, cross = max(((S_IJ - uJ S_I) - uI S_J) + (uI uJ) n, eps),
+ *                      Ivar = max((S_II - (2 uI) S_I) + (uI uI) n, eps), Jvar likewise, cc = (cross / Ivar) (cross / Jvar).
+ *                      sums [batch, V, 5] (the five sums as the epilogue sees them), cc [batch, V], loss [batch] = -mean(cc): each may be
+ *                      NULL, not all three.  One launch, and a tiny second one for `loss`.
+ *   nrt_ncc_bwd_f32    gcc [batch, V] (the upstream gradient of cc) and / or gloss [batch] (that of loss): at least one.  gI, gJ (the
+ *                      layout of I, J): either may be NULL, not both.  max passes its gradient where the unclamped value >= eps and
+ *                      nothing below.  Two launches of the forward's box-sum kernel; nothing of the forward is kept but I and J.
+ *   nrt_ncc_workspace_bytes   what both calls need at most (the backward: 20 bytes per voxel); 0 for a geometry they refuse.  The
+ *                      forward needs a workspace only for `loss`.
+ *   nrt_grad_loss_f32  d_i = y[.., 1:, ..] - y[.., :-1, ..] along each of the last nd (1 .. 3) extents of shape; m_i = the mean over everything
+ *                      but the batch of |d_i| (penalty 1) or d_i^2 (penalty 2); loss [batch] = ((m_0 + m_1) + m_2) / nd * loss_mult (pass 1
+ *                      for none).  An axis of extent 1 has no differences: its mean is 0 / 0.  Workspace: batch * 6144 bytes.
+ *   nrt_grad_loss_bwd_f32   gy_q = sum_i s_i (phi(y_q - y_{q - e_i}) - phi(y_{q + e_i} - y_q)), phi = sign (penalty 1, sign(0) = 0) or 2 d
+ *                      (penalty 2), s_i = gloss[b] loss_mult / (nd count_i).  One pass, no workspace.
+ * No atomics, no host synchronisation (every call captures into a graph); every sum has a fixed partition and order: run-to-run
+ * bit-identical.  Base pointers and the workspace need 4-byte alignment only (the Grad kernels use 16-byte accesses where
+ * channels % 4 == 0 and the pointers allow).  Checked before any launch: NRT_ERR_INVALID_ARG for a NULL tensor, shape or win that is not
+ * optional, batch or an extent < 1, a NaN or negative eps, nd outside 1 .. 3 or a leading extent != 1 beyond nd, another penalty;
+ * NRT_ERR_UNSUPPORTED for a window outside 1 .. 15, channels outside 1 .. 16 (NCC) and 2^31 or more elements in a tensor;
+ * NRT_ERR_WORKSPACE for a missing or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_ncc_workspace_bytes(int batch, const int *shape, int channels, const int *win);
+int nrt_ncc_f32(const float *I, const float *J, int batch, const int *shape, int channels, const int *win, float eps, float *sums,
+                float *cc, float *loss, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_ncc_bwd_f32(const float *I, const float *J, const float *gcc, const float *gloss, int batch, const int *shape, int channels,
+                    const int *win, float eps, float *gI, float *gJ, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_grad_loss_f32(const float *y, int batch, const int *shape, int nd, int channels, int penalty, float loss_mult, float *loss,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int nrt_grad_loss_bwd_f32(const float *y, const float *gloss, int batch, const int *shape, int nd, int channels, int penalty,
+                          float loss_mult, float *gy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,11 @@ _SIGNATURES = {
     'nrt_seg_recode': (_i, [_vp, _i, _ll, _vp, _ll, _vp, _vp]),
     'nrt_patch_extract': (_i, [_vp, _i, _i, _ip, _i, _ip, _ip, _ip, _ll, _ll, _vp, _vp]),
     'nrt_patch_quilt': (_i, [_vp, _i, _i, _ip, _ip, _ip, _i, _i, _vp, _vp]),
+    'nrt_ncc_workspace_bytes': (_sz, [_i, _ip, _i, _ip]),
+    'nrt_ncc_f32': (_i, [_vp, _vp, _i, _ip, _i, _ip, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_ncc_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _i, _ip, _f, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_grad_loss_f32': (_i, [_vp, _i, _ip, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    'nrt_grad_loss_bwd_f32': (_i, [_vp, _vp, _i, _ip, _i, _i, _i, _f, _vp, _vp]),
 }
 
 
