@@ -252,6 +252,34 @@ const char *nrt_warp_dice_kernel_name(const int *out_shape, const int *vol_shape
                                       int store, int want_minmax, int tune);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused SpatialTransformer + soft Dice on integer LABEL MAPS  (csrc/warp_labels.hip)
+ * An extension of this package: the reference has no fused form and no soft Dice on label ids.  With M = one_hot(moving, nlabels)
+ * and F = one_hot(fixed, nlabels) in float32 (an id outside [0, nlabels) gives an all-zero row, as tf.one_hot does) the results
+ * are those of nrt_warp_dice_soft_f32 on M and F, without the one-hot tensors: the tri-linear warp of a one-hot map has at most
+ * 8 non-zero values per voxel, the sums of the weights of the corners that carry each label.
+ *   moving [batch, vol_shape] int32, loc [batch, out_shape, 3], fixed [batch, out_shape] int32;
+ *   warped [batch, out_shape, nlabels] float32 or NULL (not written): bit-identical to nrt_interpn_f32 on M;
+ *   sums [batch, 3, nlabels] (sum t p, sum t^2, sum p^2), dice [batch, nlabels] as nrt_dice_soft_f32.
+ * nlabels 1 ... 256 (no multiple-of-4 rule).  loc_mode NRT_LOC_SHIFT or NRT_LOC_ABSOLUTE (NRT_LOC_LINSPACE: NRT_ERR_INVALID_ARG);
+ * loc_batch_stride = 0: one transform for every batch entry.  has_fill: fill_value must be 0 (an out-of-bounds voxel contributes
+ * p = 0 for every label).  No atomics: results are run-to-run bit-identical.  No host synchronisation.
+ * Size limits (NRT_ERR_UNSUPPORTED beyond them): 3-D, batch <= 65535, fewer than 2^31 voxels per volume and per output, one batch
+ * entry of `warped` below 4 GiB.
+ * The backward is wrt loc only: grad_loc [batch, out_shape, 3] from the forward's sums and grad_dice [batch, nlabels]; it is 0 for
+ * out-of-bounds voxels when has_fill is set, and for a label whose denominator is 0.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_warp_dice_labels_workspace_bytes(const int *out_shape, int nlabels, int batch);
+int nrt_warp_dice_labels_f32(const int32_t *moving, const float *loc, const int32_t *fixed, float *warped /* or NULL */,
+                             const int *vol_shape, const int *out_shape, int nlabels, int batch,
+                             long long loc_batch_stride, int loc_mode, int has_fill, float fill_value,
+                             float laplace_smoothing, float *sums, float *dice,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int nrt_warp_dice_labels_bwd_f32(const int32_t *moving, const float *loc, const int32_t *fixed, const float *sums,
+                                 const float *grad_dice, float *grad_loc, const int *vol_shape, const int *out_shape,
+                                 int nlabels, int batch, long long loc_batch_stride, int loc_mode, int has_fill,
+                                 float laplace_smoothing, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Label-weighted categorical cross-entropy
  * replaces: neurite/tf/metrics.py:640-650 + tf.keras.losses.CategoricalCrossentropy
  * ------------------------------------------------------------------------------------------ */

@@ -7,6 +7,9 @@ is numerically the pipeline
 (neurite/tf/models.py:806-807 + neurite/tf/metrics.py:415-482) but never writes `warped`: the blended row is
 consumed in registers (csrc/fused.hip).  This is the Dice-of-a-warped-segmentation loss/metric of
 VoxelMorph-style training; the reference has no fused form (TensorFlow materialises every intermediate).
+
+    d = ne.fused.warp_dice_labels(moving_ids, trf, fixed_ids, nb_labels)      # [B, L]
+is the same pipeline on the one-hot maps of two integer label maps, without building them (csrc/warp_labels.hip).
 """
 
 import torch
@@ -15,7 +18,7 @@ from . import _lib
 from . import utils
 from .errors import InvalidArgumentError
 
-__all__ = ['warp_dice']
+__all__ = ['warp_dice', 'warp_dice_labels']
 
 
 class _WarpDiceFn(torch.autograd.Function):
@@ -130,6 +133,106 @@ def warp_dice(moving, trf, fixed, indexing='ij', single_transform=False, fill_va
     if torch.is_grad_enabled() and shift.requires_grad:
         if check_input_limits == 'deferred':
             check_input_limits = True                  # (a graph is being recorded: the assert is looked at before the node exists)
+        d = _WarpDiceFn.apply(shift, run, run_backward)
+    else:
+        d = run()
+    out = (d,)
+    if return_warped:
+        out += (warped,)
+    if return_sums:
+        out += (sums,)
+    return out[0] if len(out) == 1 else out
+
+
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _label_map(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('expected a torch.Tensor, got %s' % type(t).__name__)
+    if t.dtype not in _INT_DTYPES:
+        raise TypeError('warp_dice_labels: %s must hold integer label ids, got %s' % (name, t.dtype))
+    if t.dim() == 5 and t.shape[-1] == 1:
+        t = t[..., 0]
+    if t.dim() != 4:
+        raise Exception('warp_dice_labels expects 3-D label maps [B, X, Y, Z] (or [B, X, Y, Z, 1])')
+    return t
+
+
+def warp_dice_labels(moving, trf, fixed, nb_labels, indexing='ij', single_transform=False, fill_value=None,
+                     laplace_smoothing=0., return_warped=False, return_sums=False):
+    """
+    warp_dice on the one-hot maps of two integer label maps, without building them: moving [B, X, Y, Z] and fixed [B, X', Y', Z']
+    (or with a trailing axis of 1) of any torch integer dtype (int32 is used as is, the others are converted once), trf
+    [B, X', Y', Z', 3] (voxel displacements), nb_labels = L in [1, 256] (any count).  With M = one_hot(moving, L), F = one_hot(fixed, L)
+    in float32 -- an id outside [0, L) gives an all-zero row, as tf.one_hot does -- this returns what
+        SpatialTransformer('linear', indexing, single_transform, fill_value)([M, trf]) -> Dice(laplace_smoothing).dice(F, warped)
+    returns: dice [B, L], optionally the warped soft labels [B, X', Y', Z', L] (bit-identical to that pipeline's) and the sums
+    [B, 3, L] (sum t p, sum t^2, sum p^2; the counts sum t^2 are exact).  The tri-linear warp of a one-hot map has at most 8 non-zero
+    values per voxel, so the kernel reads 8 ids per voxel and no rows (csrc/warp_labels.hip).  Differentiable in trf only; with
+    single_transform the gradient is summed over the batch.  fill_value: None or 0 (an out-of-bounds voxel then counts as p = 0 for every
+    label); any other value raises NotImplementedError.  There is no check_input_limits argument: the inputs are label ids, not
+    probabilities, and there is nothing to check.
+    Measured on the bench field at 4 x 160^3 x 32 (tools/warp_dice_labels_bench.py, medians): forward 0.478 ms against 0.863 ms for
+    warp_dice on prebuilt float32 one-hot maps, forward + backward 0.774 against 2.067.  It loses on i.i.d. label ids, where every wave
+    meets every label in every step: forward 1.153 ms against 0.857 (1.34 x; with the backward 1.50 against 2.01), and at 4 labels the
+    forward only ties with warp_dice on bfloat16 maps (0.285 against 0.288 ms).
+    """
+    mov = _label_map(moving, 'moving')
+    fix = _label_map(fixed, 'fixed')
+    L = int(nb_labels)
+    if not 1 <= L <= 256:
+        raise NotImplementedError('warp_dice_labels: nb_labels must lie in [1, 256], got %d' % L)
+    has_fill = fill_value is not None
+    if has_fill and not float(fill_value) == 0.0:
+        raise NotImplementedError('warp_dice_labels: fill_value must be None or 0 (a non-zero fill makes every row of a label map dense)')
+    dev = _lib.require_device(mov, trf, fix)
+    lib = _lib.lib()
+    if trf.dim() != 5 or trf.shape[-1] != 3:
+        raise Exception('warp_dice_labels expects 3-D label maps [B, X, Y, Z] and a displacement field [B, X, Y, Z, 3]')
+    if indexing not in ('ij', 'xy'):
+        raise ValueError("indexing has to be 'ij' (matrix) or 'xy' (cartesian)")
+    B = mov.shape[0]
+    if fix.shape[0] != B or tuple(fix.shape[1:]) != tuple(trf.shape[1:-1]):
+        raise ValueError('fixed must be [B, *trf_spatial]')
+    if not single_transform and trf.shape[0] != B:
+        raise ValueError('batch size of the transform does not match the volume')
+    # (an int64 id beyond int32 stays outside [0, L) instead of wrapping into it)
+    mov = (mov.clamp(-1, L) if mov.dtype == torch.int64 else mov).to(torch.int32).contiguous()
+    fix = (fix.clamp(-1, L) if fix.dtype == torch.int64 else fix).to(torch.int32).contiguous()
+    shift = trf.to(torch.float32)
+    if indexing == 'xy':
+        shift = torch.cat([shift[..., 1:2], shift[..., 0:1], shift[..., 2:]], -1)
+    shift = (shift[:1] if single_transform else shift).contiguous()
+    S = list(mov.shape[1:])
+    O = list(fix.shape[1:])
+    sums = torch.empty((B, 3, L), dtype=torch.float32, device=dev)
+    dice = torch.empty((B, L), dtype=torch.float32, device=dev)
+    warped = torch.empty(tuple(fix.shape) + (L,), dtype=torch.float32, device=dev) if return_warped else None
+    o_shape = _lib.ints(O)
+    nws = lib.nrt_warp_dice_labels_workspace_bytes(o_shape, L, B)
+    ws = _lib.workspace(dev, nws)
+    loc_bs = 0 if single_transform else shift[0].numel()
+
+    def run():
+        with torch.cuda.device(dev):
+            rc = lib.nrt_warp_dice_labels_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(warped), _lib.ints(S), o_shape, L, B,
+                                              loc_bs, _lib.LOC_SHIFT, int(has_fill), 0.0, float(laplace_smoothing), _lib.ptr(sums),
+                                              _lib.ptr(dice), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_warp_dice_labels_f32')
+        return dice
+
+    def run_backward(grad_dice):
+        gshift = torch.empty((B,) + tuple(shift.shape[1:]), dtype=torch.float32, device=dev)
+        g = grad_dice.to(torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            rc = lib.nrt_warp_dice_labels_bwd_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(sums), _lib.ptr(g),
+                                                  _lib.ptr(gshift), _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill),
+                                                  float(laplace_smoothing), _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_warp_dice_labels_bwd_f32')
+        return gshift.sum(0, keepdim=True) if single_transform else gshift
+
+    if torch.is_grad_enabled() and shift.requires_grad:
         d = _WarpDiceFn.apply(shift, run, run_backward)
     else:
         d = run()
