@@ -1,7 +1,7 @@
 """
 Guarded device buffers for the tests that call the C ABI directly (tests/test_gpu_dispatch_arms.py,
-tests/test_gpu_warp_backward_arms.py, tests/test_gpu_filter_arms.py, tests/test_gpu_conv_fwd_arms.py): the alignment of every pointer
-is exact, and a write outside an output is caught.
+tests/test_gpu_warp_backward_arms.py, tests/test_gpu_filter_arms.py, tests/test_gpu_conv_fwd_arms.py, tests/test_gpu_lc3d_arms.py): the
+alignment of every pointer is exact, and a write outside an output is caught.
 """
 
 import numpy as np
@@ -64,6 +64,45 @@ class Bytes:
         """nothing outside the n bytes was written"""
         w = N(self.whole)
         assert (w[:self.GUARD] == self.MARK).all() and (w[self.GUARD + self.n:] == self.MARK).all(), 'a write outside the workspace'
+
+
+class Raw:
+    """n bytes of any element type (float32, bfloat16 as bits, 16- or 32-bit patterns) with GUARD guard bytes on each side, compared
+    byte for byte.  off = 0: the payload starts 16-byte aligned; off = k: k bytes later.  data: a numpy array whose bytes fill the
+    payload; without it the payload holds MARK bytes like the guards, so `untouched` can tell that nothing was written at all."""
+
+    GUARD, MARK = 64, 0xA5
+
+    def __init__(self, dev, n, off=0, data=None):
+        _lib.require_device(torch.empty(1, device=dev))
+        self.whole = torch.full((n + 2 * self.GUARD + 16,), self.MARK, dtype=torch.uint8, device=dev)
+        assert self.whole.data_ptr() % 16 == 0 and 0 <= off < 16
+        self.lo, self.n = self.GUARD + off, n
+        self.t = self.whole[self.lo:self.lo + n]
+        assert self.t.data_ptr() % 16 == off
+        if data is not None:
+            raw = np.frombuffer(np.ascontiguousarray(data).tobytes(), np.uint8)
+            assert raw.size == n, (raw.size, n)
+            self.t.copy_(torch.from_numpy(raw.copy()))
+
+    @property
+    def p(self):
+        return _lib.ptr(self.t)
+
+    def zero(self):
+        self.t.zero_()
+        return self
+
+    def get(self, dtype, shape=None):
+        """the payload as `dtype`, after checking that nothing outside it was written"""
+        w = N(self.whole)
+        assert (w[:self.lo] == self.MARK).all() and (w[self.lo + self.n:] == self.MARK).all(), 'a write outside the output'
+        out = np.frombuffer(w[self.lo:self.lo + self.n].tobytes(), dtype)
+        return out.reshape(shape) if shape is not None else out
+
+    def untouched(self):
+        """not one byte of the buffer, payload included, was written (the buffer was created without data)"""
+        return bool((N(self.whole) == self.MARK).all())
 
 
 def call(dev, name, *args):

@@ -22,6 +22,9 @@ one, which is reported and exits 1.
 --families conv_fwd checks the convolution forward kernels of csrc/conv.hip, conv_p27.h and conv_up2.h with space_to_depth2 and the
 weight-pack kernels (tests/test_gpu_conv_fwd_arms.py; kernel table profiles/dispatch_arms/conv_kernels.txt).  Every instance is
 reachable.
+
+--families lc3d checks the LocallyConnected3D kernels of csrc/lc3d.hip and pad3d_rows (tests/test_gpu_lc3d_arms.py; kernel table
+profiles/dispatch_arms/lc3d_kernels.txt).  The four bfloat16 lc3d_fwd_mfma<..., NPC = 2> instances are unreachable.
 """
 import argparse
 import csv
@@ -49,10 +52,18 @@ CONV_WGRAD_FAMILIES = [r'conv3d_wgrad<\d+,\d+,\d+,\d+,(?:false|true)>', r'conv3d
 CONV_FWD_FAMILIES = [r'conv3d_mfma<\d+,(?:false|true),(?:false|true),(?:false|true)>', r'conv3d_p27_mfma<\d+,(?:false|true),(?:false|true)>',
                      r'conv3d_up2_mfma<\d+,0>', r'conv3d_mfma_k2<\d+>', r'conv3d_direct<(?:false|true)>', r'space_to_depth2',
                      r'conv3d_pack_weights', r'conv3d_pack_weights_batched<(?:false|true)>', r'conv3d_pack_weights_up2']
-FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES}
+# the dispatchers of nrt_lc3d_f, nrt_lc3d_bwd_f and nrt_pad3d (csrc/lc3d.hip): the whole translation unit but nrt_zero_words
+_T = r'(?:float|unsignedshort)'
+LC3D_FAMILIES = [r'lc3d_fwd<%s,\d+,\d+,(?:false|true),\d+>' % _T, r'lc3d_bwd<%s,\d+,\d+,(?:false|true),\d+>' % _T,
+                 r'lc3d_fwd_mfma<%s,\d+,\d+,\d+,\d+>' % _T, r'lc3d_fwd_mfma_blk<%s,\d+,\d+,\d+,\d+>' % _T, r'lc3d_generic<%s>' % _T,
+                 r'pad3d_rows<(?:unsignedint|unsignedshort)>']
+FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
+               'lc3d': LC3D_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
-# aligned, which include/neurite_amd.h rules out
-UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': []}
+# aligned, which include/neurite_amd.h rules out; a bfloat16 patch the matrix-core forward accepts has at most 56 16-byte pieces, so
+# its two-pieces-per-lane form (NPC = 2, more than 64) never runs (profiles/dispatch_arms/README.md)
+UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
+               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>']}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
