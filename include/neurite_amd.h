@@ -632,6 +632,35 @@ int nrt_seg_loss_bwd_f32(const float *y_true, const float *y_pred, const float *
                          float label_smoothing, float laplace_smoothing, int through_softmax, float *grad, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same segmentation loss with an integer LABEL MAP as y_true  (csrc/segloss_labels.hip)
+ * An extension of this package: the reference builds the float one-hot map on the host (neurite/tf/generators.py:1024-1049).  With
+ * T = one_hot(labels, nlabels) in float32 -- an id outside [0, nlabels) gives an all-zero row, as tf.one_hot does; an id is compared
+ * with the labels and never used as an index -- the results are those of nrt_seg_loss_f32 / nrt_seg_loss_bwd_f32 on T and y_pred,
+ * without T: 4 bytes of id per voxel stand in for 4 nlabels bytes of row.
+ *   labels [batch, nvox] int32, y_pred [batch, nvox, nlabels] float32; nlabels 1 ... 256 (nrt_seg_loss_labels_supported).
+ *   Multiples of 4 with 16-byte aligned rows run on lane groups (padded to the next power of two), everything else on a generic kernel.
+ *   want: NRT_SEG_WANT_DICE, NRT_SEG_WANT_CCE or both; the kernel of a single loss does no work for the other.
+ *     Dice:  sums [batch, 3, L] (the counts sum t^2 are exact), dice [batch, L], minmax [4] or NULL = (0, 1, min y_pred, max y_pred):
+ *            the first two are the bounds of a one-hot row.  Without NRT_SEG_WANT_DICE sums and dice may be NULL and minmax must be.
+ *     CCE:   cce_sum [1]; may be NULL without NRT_SEG_WANT_CCE.
+ *   nrt_seg_loss_labels_bwd_f32: as nrt_seg_loss_bwd_f32; grad_dice or grad_cce may be NULL (that loss is then left out of the
+ *   kernel), not both; sums is needed with grad_dice only.
+ * NRT_ERR_INVALID_ARG: NULL pointers, nvox < 1, batch < 1, nlabels outside 1 ... 256, want outside 1 ... 3; NRT_ERR_UNSUPPORTED:
+ * batch > 65535; NRT_ERR_WORKSPACE: workspace missing or short.  Every refusal comes before any launch.  No atomics: results are
+ * run-to-run bit-identical.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+#define NRT_SEG_WANT_DICE 1
+#define NRT_SEG_WANT_CCE 2
+int nrt_seg_loss_labels_supported(int nlabels);
+size_t nrt_seg_loss_labels_workspace_bytes(long long nvox, int nlabels, int batch);
+int nrt_seg_loss_labels_f32(const int32_t *labels, const float *y_pred, const float *label_weights, long long nvox, int nlabels,
+                            int batch, int want, float label_smoothing, float laplace_smoothing, float *sums, float *dice,
+                            float *minmax, float *cce_sum, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_seg_loss_labels_bwd_f32(const int32_t *labels, const float *y_pred, const float *label_weights, const float *sums,
+                                const float *grad_dice, const float *grad_cce, long long nvox, int nlabels, int batch,
+                                float label_smoothing, float laplace_smoothing, int through_softmax, float *grad, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Synthesis front-end: separable filtering and min-max normalisation
  *   nrt_conv1d_axis_f32   one pass of utils.separable_conv (neurite/tf/utils/utils.py:665-751) / layers.GaussianBlur
  *                         (layers.py:251-364): the tensor viewed as [outer, axis_len, inner] around the filtered axis,

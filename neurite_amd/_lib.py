@@ -21,6 +21,7 @@ NRT_ERR_INVALID_ARG, NRT_ERR_UNSUPPORTED, NRT_ERR_LAUNCH, NRT_ERR_WORKSPACE = -1
 LOC_ABSOLUTE, LOC_SHIFT, LOC_LINSPACE = 0, 1, 2
 INTERP_LINEAR, INTERP_NEAREST = 0, 1
 DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32 = 0, 1, 2, 3, 4
+SEG_WANT_DICE, SEG_WANT_CCE = 1, 2
 
 _lib = None
 
@@ -57,6 +58,10 @@ _SIGNATURES = {
     'nrt_seg_loss_workspace_bytes': (_sz, [_ll, _i, _i]),
     'nrt_seg_loss_f32': (_i, [_vp, _vp, _vp, _ll, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nrt_seg_loss_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _f, _f, _i, _vp, _vp]),
+    'nrt_seg_loss_labels_supported': (_i, [_i]),
+    'nrt_seg_loss_labels_workspace_bytes': (_sz, [_ll, _i, _i]),
+    'nrt_seg_loss_labels_f32': (_i, [_vp, _vp, _vp, _ll, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_seg_loss_labels_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _f, _f, _i, _vp, _vp]),
     'nrt_warp_dice_workspace_bytes': (_sz, [_ip, _i, _i, _i]),
     'nrt_warp_dice_soft_f32': (_i, [_vp, _vp, _vp, _vp, _ip, _ip, _i, _i, _ll, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     'nrt_warp_dice_kernel_name': (C.c_char_p, [_ip, _ip, _i, _i, _i, _i, _i, _i, _i]),

@@ -10,15 +10,20 @@ VoxelMorph-style training; the reference has no fused form (TensorFlow materiali
 
     d = ne.fused.warp_dice_labels(moving_ids, trf, fixed_ids, nb_labels)      # [B, L]
 is the same pipeline on the one-hot maps of two integer label maps, without building them (csrc/warp_labels.hip).
+
+    cce_sum, dice = ne.fused.seg_loss_labels(label_ids, y_pred)               # [1], [B, L]
+is the segmentation pair -- weighted CCE sum and soft Dice of one_hot(label_ids, L) and y_pred -- from one pass over y_pred and the
+ids (csrc/segloss_labels.hip).
 """
 
+import numpy as np
 import torch
 
 from . import _lib
 from . import utils
 from .errors import InvalidArgumentError
 
-__all__ = ['warp_dice', 'warp_dice_labels']
+__all__ = ['warp_dice', 'warp_dice_labels', 'seg_loss_labels']
 
 
 class _WarpDiceFn(torch.autograd.Function):
@@ -242,3 +247,49 @@ def warp_dice_labels(moving, trf, fixed, nb_labels, indexing='ij', single_transf
     if return_sums:
         out += (sums,)
     return out[0] if len(out) == 1 else out
+
+
+def seg_loss_labels(labels, y_pred, label_weights=None, label_smoothing=0., laplace_smoothing=0., check_input_limits=True):
+    """
+    The segmentation loss pair on an integer label map as y_true, without its one-hot map: labels [B, *S] (or [B, *S, 1]) of any torch
+    integer dtype (int32 is used as is, int64 is clamped to [-1, L] before narrowing, the others are converted once), y_pred [B, *S, L]
+    float32, L in [1, 256].  With T = one_hot(labels, L) in float32 -- an id outside [0, L) gives an all-zero row, as tf.one_hot does --
+    this returns what metrics._SegLossFn returns on (T, y_pred):
+        cce_sum [1]   the SUM over all voxels of the label-weighted categorical cross-entropy of probabilities (metrics.py:619-650:
+                      p / sum p, clipped to [1e-7, 1 - 1e-7], label_weights on T, then label_smoothing); divide by the voxel count for
+                      Keras' default reduction
+        dice [B, L]   soft Dice (metrics.py:415-482) with laplace_smoothing, or divide_no_nan without
+    from one pass over y_pred and 4 bytes of id per voxel (csrc/segloss_labels.hip).  Differentiable in y_pred: one pass back, which
+    runs through the producer of the soft-max when y_pred still is its untouched output (models.SoftmaxSource), exactly as
+    metrics.JointSegLoss does.  check_input_limits looks at y_pred only (one read-back of its extrema): an id cannot leave [0, 1].
+    ne.losses.Dice, ne.losses.CategoricalCrossentropy and their pair inside losses.multiple_losses_decorator take the same integer
+    y_true and end up here.
+    Measured on blob labels at 4 x 160^3 x 32 (tools/seg_loss_labels_bench.py, medians): forward 0.409 ms against 0.699 ms for the pair
+    on a prebuilt float32 one-hot map (1.838 with building it on the device), forward + backward 1.371 against 1.966; 33 labels 0.845 /
+    2.526 against 2.581 / 8.671 for the two separate one-hot losses; a tie at 4 labels (0.123 against 0.129).
+    """
+    from . import metrics
+    if not isinstance(labels, torch.Tensor) or not isinstance(y_pred, torch.Tensor):
+        raise TypeError('seg_loss_labels: expected torch.Tensors, got %s and %s' % (type(labels).__name__, type(y_pred).__name__))
+    if labels.dtype not in _INT_DTYPES:
+        raise TypeError('seg_loss_labels: labels must hold integer label ids, got %s' % labels.dtype)
+    if y_pred.dtype != torch.float32:
+        raise NotImplementedError('seg_loss_labels: y_pred must be float32, got %s (the loss objects take other dtypes, on a one-hot map '
+                                  'built on the device)' % y_pred.dtype)
+    ids = metrics._label_ids(labels, y_pred)                # ValueError on a spatial shape that is not y_pred's
+    L = int(y_pred.shape[-1])
+    if not 1 <= L <= 256:
+        raise NotImplementedError('seg_loss_labels: the number of labels must lie in [1, 256], got %d' % L)
+    if y_pred.numel() == 0 or y_pred.shape[0] > 65535:
+        raise NotImplementedError('seg_loss_labels: y_pred of shape %s (no voxels, or a batch beyond 65535)' % (tuple(y_pred.shape),))
+    w = None
+    if label_weights is not None:
+        w = label_weights if isinstance(label_weights, torch.Tensor) else torch.as_tensor(np.asarray(label_weights, dtype=np.float32))
+        if w.numel() != L:
+            raise ValueError(f'Label weights must be of len {L}, but got {w.numel()}.')
+    dev = _lib.require_device(ids, y_pred)
+    if w is not None:
+        w = w.detach().to(dev, torch.float32).reshape(-1).contiguous()
+    cfg = (float(laplace_smoothing), float(label_smoothing), bool(check_input_limits))
+    cce_sum, dice, _ = metrics._seg_loss_labels(metrics._ids_i32(ids, L), y_pred, w, cfg, _lib.SEG_WANT_DICE | _lib.SEG_WANT_CCE)
+    return cce_sum, dice

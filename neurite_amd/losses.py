@@ -75,7 +75,8 @@ def multiple_losses_decorator(losses, weights=None):
     Weighted sum of several losses of one output (neurite/tf/losses.py:225-246): returns loss(y_true, y_pred).
     When the list holds exactly one soft-Dice method and one CategoricalCrossentropy method of this package -- the segmentation
     pair -- both take their numbers from one pass over the maps, and one pass back that also runs through the soft-max that made
-    y_pred (metrics.JointSegLoss, csrc/segloss.hip); every value is what the two losses return on their own.
+    y_pred (metrics.JointSegLoss, csrc/segloss.hip); every value is what the two losses return on their own.  With an integer label
+    map as y_true the pair runs on csrc/segloss_labels.hip, for any label count up to 256, and no one-hot target exists.
     """
     scale = np.ones(len(losses)) if weights is None else weights
     dice_objs = [o for o in (_owner(f, metrics.Dice, ('loss', 'mean_loss', 'dice', 'mean_dice')) for f in losses) if o is not None]

@@ -245,6 +245,116 @@ class _SegLossFn(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(src.grads_from_dz(grad, ctx.needs_input_grad[5:]))
 
 
+_LABEL_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _is_label_map(y_true, y_pred):
+    """an integer y_true beside a floating-point y_pred [B, ..., L]: label ids that stand for one_hot(y_true, L) in float32"""
+    return isinstance(y_true, torch.Tensor) and isinstance(y_pred, torch.Tensor) and y_true.dtype in _LABEL_DTYPES \
+        and y_pred.dtype.is_floating_point
+
+
+def _label_shape_ok(y_true, y_pred):
+    want = tuple(y_pred.shape[:-1])
+    return y_pred.dim() >= 2 and tuple(y_true.shape) in (want, want + (1,))
+
+
+def _label_ids(y_true, y_pred):
+    """the ids as [B, *S] = y_pred.shape[:-1] (a trailing axis of 1 is dropped)"""
+    if not _label_shape_ok(y_true, y_pred):
+        raise ValueError('an integer y_true (label ids) must have the shape of y_pred without its last axis, %s, or that plus a '
+                         'trailing 1; got %s' % (tuple(y_pred.shape[:-1]), tuple(y_true.shape)))
+    return y_true if y_true.dim() == y_pred.dim() - 1 else y_true[..., 0]
+
+
+def _ids_i32(ids, L):
+    """contiguous int32 ids for the kernels (an int64 id beyond int32 stays outside [0, L) instead of wrapping into it)"""
+    return (ids.clamp(-1, L) if ids.dtype == torch.int64 else ids).to(torch.int32).contiguous()
+
+
+def _one_hot_ids(ids, L):
+    """one_hot(ids, L) in float32 on the ids' device, an all-zero row for an id outside [0, L) (tf.one_hot; torch's one_hot raises):
+    what the configurations without a labels kernel run on"""
+    return (ids.long().unsqueeze(-1) == torch.arange(L, device=ids.device)).to(torch.float32)
+
+
+def _labels_kernel_takes(y_pred):
+    """the prediction as csrc/segloss_labels.hip takes it: a float32 device tensor [B, ..., L] with voxels, 1 <= L <= 256, no pending warp"""
+    from .deferred import DeferredWarp
+    if isinstance(y_pred, DeferredWarp) and y_pred.pending:
+        return False
+    if y_pred.dtype != torch.float32 or y_pred.dim() < 2 or y_pred.numel() == 0 or y_pred.shape[0] > 65535:
+        return False
+    return bool(_lib.lib().nrt_seg_loss_labels_supported(int(y_pred.shape[-1])))
+
+
+class _SegLossLabelsFn(torch.autograd.Function):
+    """
+    _SegLossFn with int32 label ids [B, *S] in place of the one-hot map (csrc/segloss_labels.hip): returns (cce_sum [1], dice [B, L]) of
+    one_hot(ids, L) and p; `want` (_lib.SEG_WANT_DICE | _lib.SEG_WANT_CCE) selects the losses, the one not asked for comes back as None
+    and costs nothing.  `src` as in _SegLossFn.
+    """
+    applications = 0            # evaluations so far (tests check that the labels kernels ran and no one-hot map was built)
+    through_softmax = 0         # ... of which attached to the producer of the soft-max
+
+    @staticmethod
+    def forward(ctx, ids, p, w, cfg, want, src, *src_inputs):
+        eps, smoothing, check_limits = cfg
+        lib = _lib.lib()
+        dev = p.device
+        B, L = p.shape[0], p.shape[-1]
+        V = p.numel() // (B * L)
+        wd, wc = bool(want & _lib.SEG_WANT_DICE), bool(want & _lib.SEG_WANT_CCE)
+        sums = torch.empty((B, 3, L), dtype=torch.float32, device=dev) if wd else None
+        dice = torch.empty((B, L), dtype=torch.float32, device=dev) if wd else None
+        minmax = torch.empty((4,), dtype=torch.float32, device=dev) if wd and check_limits else None
+        cce_sum = torch.empty((1,), dtype=torch.float32, device=dev) if wc else None
+        nws = lib.nrt_seg_loss_labels_workspace_bytes(V, L, B)
+        ws = _lib.workspace(dev, nws)
+        with torch.cuda.device(dev):
+            rc = lib.nrt_seg_loss_labels_f32(_lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), V, L, B, int(want), float(smoothing), float(eps),
+                                             _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(cce_sum), _lib.ptr(ws), nws,
+                                             _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_seg_loss_labels_f32')
+        if minmax is not None:
+            _check_limits(minmax)                      # (0, 1, min p, max p): an id cannot leave [0, 1]
+        ctx.save_for_backward(ids, p, w, sums)
+        ctx.cfg, ctx.src, ctx.want = cfg, src, want
+        return cce_sum, dice
+
+    @staticmethod
+    def backward(ctx, g_cce, g_dice):
+        ids, p, w, sums = ctx.saved_tensors
+        eps, smoothing, _ = ctx.cfg
+        src = ctx.src
+        lib = _lib.lib()
+        dev = p.device
+        B, L = p.shape[0], p.shape[-1]
+        V = p.numel() // (B * L)
+        g_cce = g_cce.to(torch.float32).contiguous() if ctx.want & _lib.SEG_WANT_CCE else None
+        g_dice = g_dice.to(torch.float32).contiguous() if ctx.want & _lib.SEG_WANT_DICE else None
+        grad = torch.empty_like(p)
+        with torch.cuda.device(dev):
+            rc = lib.nrt_seg_loss_labels_bwd_f32(_lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), _lib.ptr(sums), _lib.ptr(g_dice), _lib.ptr(g_cce),
+                                                 V, L, B, float(smoothing), float(eps), int(src is not None), _lib.ptr(grad),
+                                                 _lib.stream_ptr(dev))
+        _lib.check(rc, 'nrt_seg_loss_labels_bwd_f32')
+        if src is None:
+            return (None, grad, None, None, None, None)
+        return (None, None, None, None, None, None) + tuple(src.grads_from_dz(grad, ctx.needs_input_grad[6:]))
+
+
+def _seg_loss_labels(ids, y_pred, w, cfg, want, through_softmax=True):
+    """(cce_sum [1] or None, dice [B, L] or None, went through the soft-max's producer) of int32 ids [B, *S] and the float32 prediction"""
+    p = y_pred.contiguous()
+    src = getattr(y_pred, '_nrt_softmax_src', None) if through_softmax else None
+    _SegLossLabelsFn.applications += 1
+    if src is not None and p is y_pred and src.valid_for(y_pred):
+        _SegLossLabelsFn.through_softmax += 1
+        return _SegLossLabelsFn.apply(ids, p.detach(), w, cfg, want, src, *src.inputs) + (True,)
+    return _SegLossLabelsFn.apply(ids, p, w, cfg, want, None) + (False,)
+
+
 class JointSegLoss:
     """
     One evaluation of a soft Dice object and a CategoricalCrossentropy object on the same (y_true, y_pred) -- the pair of losses
@@ -252,6 +362,8 @@ class JointSegLoss:
     block on this thread), `dice_obj.dice(y_true, y_pred)` and `cce_obj.cce(y_true, y_pred)` called with THESE tensor objects take
     their numbers from one shared _SegLossFn application; everything else those methods do (weights, means, reductions, the finite
     check) is unchanged.  `JointSegLoss.open(...)` returns None when the pair does not qualify (then nothing is intercepted).
+    An integer y_true (label ids, shape y_pred.shape[:-1] or that plus a trailing 1) qualifies for every label count 1 ... 256: the
+    application is then a _SegLossLabelsFn (csrc/segloss_labels.hip) and no one-hot map exists.
     """
     _tls = threading.local()
     applications = 0            # _SegLossFn evaluations so far (tests check that the joint path really ran)
@@ -260,6 +372,7 @@ class JointSegLoss:
     def __init__(self, dice_obj, cce_obj, y_true, y_pred):
         self.dice_obj, self.cce_obj, self.y_true, self.y_pred = dice_obj, cce_obj, y_true, y_pred
         self._result = None
+        self.labels = False         # y_true holds integer label ids
 
     @classmethod
     def open(cls, dice_obj, cce_obj, y_true, y_pred):
@@ -269,18 +382,26 @@ class JointSegLoss:
             return None
         if dice_obj.dice_type != 'soft' or dice_obj.normalize or cce_obj.from_logits or cce_obj.reduction == 'none':
             return None
-        if not y_pred.is_cuda or y_true.device != y_pred.device or y_pred.dtype != torch.float32 or y_true.shape != y_pred.shape:
+        labels = _is_label_map(y_true, y_pred)               # integer ids: the pair runs on csrc/segloss_labels.hip, for any label count
+        if not y_pred.is_cuda or y_true.device != y_pred.device or y_pred.dtype != torch.float32:
             return None
-        if y_pred.dim() < 2 or y_pred.numel() == 0 or not y_true.dtype.is_floating_point or y_true.dtype == torch.float64:
+        if not (_label_shape_ok(y_true, y_pred) if labels else y_true.shape == y_pred.shape):
+            return None
+        if y_pred.dim() < 2 or y_pred.numel() == 0:
+            return None
+        if not labels and (not y_true.dtype.is_floating_point or y_true.dtype == torch.float64):
             return None
         if y_true.requires_grad and torch.is_grad_enabled():
             return None
         L = y_pred.shape[-1]
         if cce_obj.label_weights is not None and cce_obj.label_weights.shape[-1] != L:
             return None                                      # the CCE raises its own error on the ordinary path
-        if not _lib.lib().nrt_seg_loss_supported(L) or y_pred.shape[0] > 65535:
+        supported = _lib.lib().nrt_seg_loss_labels_supported(L) if labels else _lib.lib().nrt_seg_loss_supported(L)
+        if not supported or y_pred.shape[0] > 65535:
             return None
-        return cls(dice_obj, cce_obj, y_true, y_pred)
+        joint = cls(dice_obj, cce_obj, y_true, y_pred)
+        joint.labels = labels
+        return joint
 
     def __enter__(self):
         self._prev = getattr(self._tls, 'current', None)
@@ -300,6 +421,15 @@ class JointSegLoss:
 
     def result(self):
         """(cce_sum [1], dice [B, L]); computed at the first request"""
+        if self._result is None and self.labels:
+            lw = self.cce_obj.label_weights
+            w = None if lw is None else self.cce_obj._weights_on(self.y_pred.device)
+            cfg = (float(self.dice_obj.laplace_smoothing), float(self.cce_obj.label_smoothing), bool(self.dice_obj.check_input_limits))
+            ids = _ids_i32(_label_ids(self.y_true, self.y_pred), self.y_pred.shape[-1])
+            cce_sum, dice, via_src = _seg_loss_labels(ids, self.y_pred, w, cfg, _lib.SEG_WANT_DICE | _lib.SEG_WANT_CCE)
+            JointSegLoss.applications += 1
+            JointSegLoss.through_softmax += int(via_src)
+            self._result = (cce_sum, dice)
         if self._result is None:
             p = self.y_pred.contiguous()
             t = self.y_true.detach().to(torch.float32).contiguous()
@@ -382,6 +512,9 @@ class Dice:
         """
         y_true, y_pred: [B, ..., nb_labels] (prob / one-hot) or [B, ...] (max_label).
         Returns [B, nb_labels] float32 (neurite/tf/metrics.py:415-482).
+        With 'prob' inputs y_true may also be an integer label map of shape y_pred.shape[:-1] (or that plus a trailing 1): it means
+        one_hot(y_true, nb_labels) in float32, an all-zero row for an id outside [0, nb_labels), and is read as ids where a labels
+        kernel exists (soft Dice without normalize on a float32 prediction: csrc/segloss_labels.hip).
         """
         lib = _lib.lib()
         dev = _lib.require_device(y_true, y_pred)
@@ -391,6 +524,15 @@ class Dice:
             joint = JointSegLoss.lookup(self, y_true, y_pred)
             if joint is not None:
                 return joint.result()[1]
+            if _is_label_map(y_true, y_pred):
+                # integer label ids stand for one_hot(y_true, L): read as ids by csrc/segloss_labels.hip, or -- where that has no
+                # kernel (normalize, a pending warp, 16-bit or float64 predictions, L > 256) -- as the float32 map built on the device
+                ids = _label_ids(y_true, y_pred)
+                L = int(y_pred.shape[-1])
+                if not self.normalize and _labels_kernel_takes(y_pred):
+                    cfg = (eps, 0., bool(self.check_input_limits))
+                    return _seg_loss_labels(_ids_i32(ids, L), y_pred, None, cfg, _lib.SEG_WANT_DICE, through_softmax=False)[1]
+                y_true = _one_hot_ids(ids, L)
             if torch.is_grad_enabled() and (y_true.requires_grad or y_pred.requires_grad):
                 from .deferred import materialize
                 return _SoftDiceFn.apply(materialize(y_true), materialize(y_pred), eps, bool(self.normalize),
@@ -409,6 +551,8 @@ class Dice:
                           'and computing *hard* dice. \n For this, we use argmax to'
                           'get the optimal label at each location, which is not'
                           'differentiable. Do not use expecting gradients.')
+            if _is_label_map(y_true, y_pred):       # label ids against probabilities: the float32 one-hot map, built on the device
+                y_true = _one_hot_ids(_label_ids(y_true, y_pred), int(y_pred.shape[-1]))
             t, p, dt = _as_maps(y_true, y_pred)
             if t.shape != p.shape:
                 raise ValueError('y_true and y_pred must have the same shape')
@@ -514,7 +658,9 @@ class CategoricalCrossentropy:
     (neurite/tf/metrics.py:619-650).  Keras keyword arguments honoured: from_logits,
     label_smoothing, reduction ('auto' / 'sum_over_batch_size' / 'sum' / 'none'), name; axis must be -1.
     Inputs may be float32 or bfloat16 (arithmetic is float32 either way); returns a float32 scalar
-    (or the per-element losses for reduction='none').
+    (or the per-element losses for reduction='none').  y_true may also be an integer label map of shape y_pred.shape[:-1] (or that
+    plus a trailing 1), meaning one_hot(y_true, L) in float32 with an all-zero row for an id outside [0, L): probabilities with a
+    'sum' or mean reduction and no sample_weight read the ids themselves (csrc/segloss_labels.hip), everything else the map built on the device.
     """
 
     def __init__(self, label_weights=None, **kwargs):
@@ -575,19 +721,30 @@ class CategoricalCrossentropy:
                 raise ValueError(f'Label weights must be of len {yf}, but got {lf}.')
         lib = _lib.lib()
         dev = _lib.require_device(y_true, y_pred)
-        if y_true.shape != y_pred.shape:
-            raise ValueError('y_true and y_pred must have the same shape')
+        need_pv = sample_weight is not None or self.reduction == 'none'
+        joint = None if need_pv else JointSegLoss.lookup(self, y_true, y_pred)
+        if _is_label_map(y_true, y_pred):
+            # integer label ids stand for one_hot(y_true, L): read as ids by csrc/segloss_labels.hip, or -- where that has no kernel
+            # (logits, per-voxel losses, a pending warp, bfloat16 predictions, L > 256) -- as the float32 map built on the device
+            ids = _label_ids(y_true, y_pred)
+            if joint is None and not need_pv and not self.from_logits and _labels_kernel_takes(y_pred):
+                cfg = (0., self.label_smoothing, False)
+                total = _seg_loss_labels(_ids_i32(ids, yf), y_pred, self._weights_on(dev), cfg, _lib.SEG_WANT_CCE, through_softmax=False)[0]
+                return total[0] if self.reduction == 'sum' else total[0] / (y_pred.numel() // yf)
+            y_true_map = None if joint is not None else _one_hot_ids(ids, yf)
+        else:
+            y_true_map = y_true
+            if y_true.shape != y_pred.shape:
+                raise ValueError('y_true and y_pred must have the same shape')
         if y_pred.dtype not in (torch.float32, torch.bfloat16):
             raise NotImplementedError('CategoricalCrossentropy: float32 or bfloat16 inputs, got %s' % y_pred.dtype)
         p = y_pred.contiguous()
-        t = y_true.to(p.dtype).contiguous()           # keras casts y_true to y_pred's dtype
-        w = self._weights_on(dev)
         N = p.numel() // max(yf, 1)
-        need_pv = sample_weight is not None or self.reduction == 'none'
-        joint = None if need_pv else JointSegLoss.lookup(self, y_true, y_pred)
         if joint is not None:
             res = joint.result()[0]
         else:
+            t = y_true_map.to(p.dtype).contiguous()       # keras casts y_true to y_pred's dtype
+            w = self._weights_on(dev)
             # the mean's division happens in the kernel (one launch per call), with or without an autograd node: one formulation, one value
             mean = not need_pv and self.reduction != 'sum' and N > 0
             if torch.is_grad_enabled() and (p.requires_grad or t.requires_grad):
