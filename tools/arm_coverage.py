@@ -25,6 +25,9 @@ reachable.
 
 --families lc3d checks the LocallyConnected3D kernels of csrc/lc3d.hip and pad3d_rows (tests/test_gpu_lc3d_arms.py; kernel table
 profiles/dispatch_arms/lc3d_kernels.txt).  The four bfloat16 lc3d_fwd_mfma<..., NPC = 2> instances are unreachable.
+
+--families conv_bf16 checks the bfloat16 inference kernels of csrc/conv_bf16.hip (tests/test_gpu_conv_bf16_arms.py; kernel table
+profiles/dispatch_arms/conv_bf16_kernels.txt): 17 instances, every one reachable.
 """
 import argparse
 import csv
@@ -57,13 +60,17 @@ _T = r'(?:float|unsignedshort)'
 LC3D_FAMILIES = [r'lc3d_fwd<%s,\d+,\d+,(?:false|true),\d+>' % _T, r'lc3d_bwd<%s,\d+,\d+,(?:false|true),\d+>' % _T,
                  r'lc3d_fwd_mfma<%s,\d+,\d+,\d+,\d+>' % _T, r'lc3d_fwd_mfma_blk<%s,\d+,\d+,\d+,\d+>' % _T, r'lc3d_generic<%s>' % _T,
                  r'pad3d_rows<(?:unsignedint|unsignedshort)>']
+# the dispatchers of nrt_conv3d_bf16, nrt_conv3d_pack_weights_bf16, nrt_conv1x1_softmax_bf16, nrt_softmax_lastdim_bf16, nrt_maxpool3d_bf16,
+# nrt_upsample_concat_bf16 and nrt_add_act_affine_bf16 (csrc/conv_bf16.hip): the whole translation unit but nrt_zero_words
+CONV_BF16_FAMILIES = [r'conv3d_bf16<\d+>', r'conv3d_pack_bf16<%s>' % _T, r'conv1x1_bf16<\d+>', r'softmax_lastdim_bf16<(?:false|true)>',
+                      r'maxpool3d_bf16<\d+>', r'upsample_concat_bf16<\d+>', r'add_act_affine_bf16<\d+>']
 FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
-               'lc3d': LC3D_FAMILIES}
+               'lc3d': LC3D_FAMILIES, 'conv_bf16': CONV_BF16_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
 # aligned, which include/neurite_amd.h rules out; a bfloat16 patch the matrix-core forward accepts has at most 56 16-byte pieces, so
 # its two-pieces-per-lane form (NPC = 2, more than 64) never runs (profiles/dispatch_arms/README.md)
 UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
-               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>']}
+               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': []}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
