@@ -960,6 +960,35 @@ int nrt_grad_loss_f32(const float *y, int batch, const int *shape, int nd, int c
 int nrt_grad_loss_bwd_f32(const float *y, const float *gloss, int batch, const int *shape, int nd, int channels, int penalty,
                           float loss_mult, float *gy, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Warp by an affine matrix in one kernel, and the gradient wrt the matrix (csrc/affine_warp.hip): SpatialTransformer on an affine
+ * input ('ij' indexing) without the dense displacement field between nrt_affine_to_dense_shift_f32 and nrt_interpn_f32.
+ * float32, channels-last: vol [batch, *vol_shape, channels], matrix [matrix_batch, ndim, ndim + 1] with matrix_batch = batch, or 1 for
+ * one transform shared by the batch; out / grad_out [batch, *out_shape, channels]; ndim 2 or 3; method NRT_INTERP_LINEAR / _NEAREST.
+ *   nrt_affine_warp_f32      the location of output voxel q is formed in registers with the roundings of the two-kernel path:
+ *                            p = (float)q - c (c = (out_shape - 1) / 2 when shift_center, else 0), s_i = (((M_i0 p_0 + M_i1 p_1) + ..) +
+ *                            M_iD) - p_i, loc_i = (float)q_i + s_i, one rounding per operation; then the corner arithmetic, blend order
+ *                            and fill of nrt_interpn_f32.  out is bit for bit what that kernel gives on the materialised field.
+ *   nrt_affine_warp_bwd_f32  grad_matrix [matrix_batch, ndim, ndim + 1] = sum_q gloc_i(q) p_j(q) (p_D = 1; summed over the batch as well
+ *                            when matrix_batch == 1), gloc = d (sum_c grad_out_c out_c) / d loc as nrt_interpn_bwd_f32 defines it (through
+ *                            the clipped location, closed range, masked by 1 - oob under a fill value); all zeros for nearest.  No
+ *                            gradient field is written: every block leaves one row of partial sums in the workspace, a second launch
+ *                            adds the rows in index order in float64.  The gradient wrt vol is nrt_interpn_bwd_f32's on the field.
+ *   nrt_affine_warp_workspace_bytes   what the backward needs; 0 for a geometry it refuses.
+ * No atomics, no host synchronisation (both calls capture into a graph); the grid and the order of every sum depend on the shapes only:
+ * run-to-run bit-identical.  Base pointers need 4-byte alignment only (16-byte accesses are used where channels % 4 == 0 and the
+ * pointers allow).  Checked before any launch: NRT_ERR_INVALID_ARG for a NULL tensor or shape, batch, channels or an extent < 1, a
+ * matrix_batch that is neither 1 nor batch, another method; NRT_ERR_UNSUPPORTED for ndim outside {2, 3}, 2^31 or more elements in a
+ * tensor and batch > 65535; NRT_ERR_WORKSPACE for a missing or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_affine_warp_workspace_bytes(int ndim, const int *out_shape, int channels, int batch);
+int nrt_affine_warp_f32(const float *vol, const float *matrix, float *out, int ndim, const int *vol_shape, const int *out_shape,
+                        int channels, int batch, int matrix_batch, int shift_center, int method, int has_fill, float fill_value,
+                        void *stream);
+int nrt_affine_warp_bwd_f32(const float *vol, const float *matrix, const float *grad_out, float *grad_matrix, int ndim,
+                            const int *vol_shape, const int *out_shape, int channels, int batch, int matrix_batch, int shift_center,
+                            int method, int has_fill, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ _SIGNATURES = {
     'nrt_ncc_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _i, _ip, _f, _vp, _vp, _vp, _sz, _vp]),
     'nrt_grad_loss_f32': (_i, [_vp, _i, _ip, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     'nrt_grad_loss_bwd_f32': (_i, [_vp, _vp, _i, _ip, _i, _i, _i, _f, _vp, _vp]),
+    'nrt_affine_warp_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
+    'nrt_affine_warp_f32': (_i, [_vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    'nrt_affine_warp_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 

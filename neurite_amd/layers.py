@@ -184,8 +184,9 @@ Zoom = Resize
 class SpatialTransformer(_Layer):
     """
     N-D spatial transformer: out[b, x, :] = interpn(vol[b], x + trf[b, x, :]) (pull-back warp with a
-    dense displacement field in voxel units), or an affine [B, D, D+1] first converted to a dense
-    shift.  Accepts the union of voxelmorph's historical constructor arguments.
+    dense displacement field in voxel units), or an affine [B, D, D+1]: warped in one kernel
+    (fused.affine_warp) or first converted to a dense shift, the same bits either way.  Accepts
+    the union of voxelmorph's historical constructor arguments.
 
     call([vol, trf]):  vol [B, *S, C], trf [B, *S', D]  ->  [B, *S', C]
     """
@@ -223,6 +224,15 @@ class SpatialTransformer(_Layer):
         self.ndims = len(input_shape[0]) - 2
         self.built = True
 
+    def _defers(self, vol, D, trf_requires_grad, inference):
+        """Is the warp of non-empty tensors deferred for the fused Dice kernel (see call)?"""
+        L = vol.shape[-1]
+        return (deferred.is_enabled() and self.interp_method == 'linear' and D == 3 and vol.dtype == torch.float32
+                and self._variant == 0 and self._tune == 0 and L % 4 == 0 and 4 <= L <= 256
+                and not (torch.is_grad_enabled() and (vol.requires_grad or trf_requires_grad))
+                # inference tensors carry no version counter: an in-place change could not be detected, so they warp eagerly
+                and not (inference or torch.is_inference_mode_enabled()))
+
     def call(self, inputs):
         assert len(inputs) == 2, 'inputs has to be len 2, found: %d' % len(inputs)
         vol, trf = inputs
@@ -241,6 +251,23 @@ class SpatialTransformer(_Layer):
         if trf.dim() == 3 and trf.shape[-1] == D + 1 and trf.shape[-2] in (D, D + 1):
             out_spatial = list(self.shape) if self.shape is not None else list(vol.shape[1:-1])
             nb = 1 if self.single_transform else trf.shape[0]
+            # one kernel, no dense field (fused.affine_warp, csrc/affine_warp.hip; the same bits), unless the warp is to be deferred for
+            # the fused Dice kernel below, which consumes the field.  A linear 3-D warp of 32, 64 or 128 channels whose matrix needs no
+            # gradient keeps the field as well: there the wave-cache and tile kernels of csrc/interpn.hip outrun the plain gather by
+            # more than the field costs (4 x 160^3: 0.967 against 1.302 ms at 32 channels, 2.473 against 2.771 at 64, 5.149 against 5.941
+            # at 128; at 256 the single kernel wins again, 5.115 against 6.021 for 2 x 160^3; tools/affine_warp_bench.py).  With a
+            # gradient the single kernel and its reduction win tenfold at 32 channels.
+            C = vol.shape[-1]
+            needs_grad = torch.is_grad_enabled() and trf.requires_grad
+            wide = D == 3 and self.interp_method == 'linear' and C in (32, 64, 128) and not needs_grad
+            if (self.indexing == 'ij' and D in (2, 3) and vol.dtype == torch.float32 and trf.is_floating_point() and not wide
+                    and self._variant == 0 and self._tune == 0 and vol.numel() > 0 and int(np.prod(out_spatial)) > 0
+                    and (self.single_transform or trf.shape[0] == B)
+                    and not self._defers(vol, D, needs_grad, vol.is_inference())):
+                from . import fused
+                return fused.affine_warp(vol, trf.to(torch.float32), shape=out_spatial, interp_method=self.interp_method,
+                                         fill_value=self.fill_value, shift_center=self.shift_center,
+                                         single_transform=self.single_transform)
             trf = utils.affine_to_dense_shift(trf[:nb].to(vol.device), out_spatial, shift_center=self.shift_center,
                                               indexing=self.indexing)                      # batched: one launch on the device
         else:
@@ -267,12 +294,8 @@ class SpatialTransformer(_Layer):
         # gradient the warp is deferred so that Dice can run the fused kernel and `warped` is never written
         # (neurite_amd/deferred.py); any other use of the result evaluates it with the stand-alone kernel, bit-identically
         L = vol.shape[-1]
-        if (deferred.is_enabled() and self.interp_method == 'linear' and D == 3 and vol.dtype == torch.float32
-                and self._variant == 0 and self._tune == 0 and L % 4 == 0 and 4 <= L <= 256
-                and shift.numel() > 0 and vol.numel() > 0
-                and not (torch.is_grad_enabled() and (vol.requires_grad or shift.requires_grad))
-                # inference tensors carry no version counter: an in-place change could not be detected, so they warp eagerly
-                and not (vol32.is_inference() or shift.is_inference() or torch.is_inference_mode_enabled())):
+        if (shift.numel() > 0 and vol.numel() > 0
+                and self._defers(vol, D, shift.requires_grad, vol32.is_inference() or shift.is_inference())):
             vol_c, shift_c = vol32.contiguous(), shift.contiguous()
             return deferred.DeferredWarp([B] + list(shift.shape[1:-1]) + [L], vol.dtype, vol.device, run,
                                          dict(vol=vol_c, shift=shift_c, single_transform=self.single_transform,
