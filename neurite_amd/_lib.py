@@ -247,6 +247,15 @@ def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def call(dev, name, *args, what=None):
+    """Launch entry point `name` (one that returns an NRT_* status and takes `void *stream` last) on `dev`: under the device guard,
+    on torch's current stream of `dev`, and checked.  `what` replaces the name in the error text.  The arguments go through as
+    they are; the entry point is looked up on the handle now, so one replaced there is honoured."""
+    with torch.cuda.device(dev):
+        rc = getattr(lib(), name)(*args, stream_ptr(dev))
+    check(rc, what or name)
+
+
 def ptr(t):
     # a DeferredWarp (neurite_amd/deferred.py) evaluates itself when its address is asked for
     return C.c_void_p(t.data_ptr()) if t is not None else None

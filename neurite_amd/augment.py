@@ -92,15 +92,11 @@ def _global_stat(x, name):
     """0-d device tensor: population SD or maximum over all elements (device reductions of csrc, no host sync)"""
     if name == 'max':
         return utils._device_minmax(x)[1]
-    lib = _lib.lib()
     dev = x.device
     s = torch.zeros(2, dtype=torch.float32, device=dev)
     flat = x.contiguous()
-    with torch.cuda.device(dev):
-        rc = lib.nrt_channel_sums_f32(_lib.ptr(flat), None, flat.numel(), 1, _lib.ptr(s[:1]), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_channel_sums_f32')
-        rc = lib.nrt_channel_sums_f32(_lib.ptr(flat), _lib.ptr(flat), flat.numel(), 1, _lib.ptr(s[1:]), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_channel_sums_f32')
+    _lib.call(dev, 'nrt_channel_sums_f32', _lib.ptr(flat), None, flat.numel(), 1, _lib.ptr(s[:1]))
+    _lib.call(dev, 'nrt_channel_sums_f32', _lib.ptr(flat), _lib.ptr(flat), flat.numel(), 1, _lib.ptr(s[1:]))
     n = float(flat.numel())
     mean = s[0] / n
     return torch.sqrt(torch.clamp(s[1] / n - mean * mean, min=0.0))

@@ -119,7 +119,6 @@ def all_reduce_mean_pair(buf, group=None, async_op=False):
 def _mean3(dice, weights):
     """[sum of dice * weights, number of entries, their quotient] as a 3-float device buffer, one launch"""
     from . import _lib
-    lib = _lib.lib()
     dev = _lib.require_device(dice)
     if dice.dim() != 2:
         raise ValueError('local_dice must be [B_local, L]')
@@ -135,9 +134,7 @@ def _mean3(dice, weights):
         else:
             raise ValueError('weights must be [L], [1, L] or [B, L]; got %s for dice %s' % (tuple(wt.shape), (B, L)))
     buf = torch.empty(3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_dice_mean_f32(_lib.ptr(d), _lib.ptr(wt), int(L), int(B), per_batch, _lib.ptr(buf), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_dice_mean_f32')
+    _lib.call(dev, 'nrt_dice_mean_f32', _lib.ptr(d), _lib.ptr(wt), int(L), int(B), per_batch, _lib.ptr(buf))
     return buf
 
 
@@ -166,16 +163,12 @@ def dice_from_sums(sums, laplace_smoothing=0.):
     computed by the HIP finalize kernel (ROCm tensors only, like every compute entry point).
     """
     from . import _lib
-    lib = _lib.lib()
     dev = _lib.require_device(sums)
     B, three, L = sums.shape
     assert three == 3, 'sums must be [B, 3, L]'
     s = sums.contiguous().to(torch.float32)
     out = torch.empty((B, L), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_dice_from_sums_f32(_lib.ptr(s), L, B, float(laplace_smoothing), _lib.ptr(out),
-                                        _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_dice_from_sums_f32')
+    _lib.call(dev, 'nrt_dice_from_sums_f32', _lib.ptr(s), L, B, float(laplace_smoothing), _lib.ptr(out))
     return out
 
 

@@ -101,21 +101,15 @@ def warp_dice(moving, trf, fixed, indexing='ij', single_transform=False, fill_va
     loc_bs = 0 if single_transform else shift[0].numel()
 
     def run():
-        with torch.cuda.device(dev):
-            if bf16:
-                rc = lib.nrt_warp_dice_soft_bf16(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ints(S), o_shape, L, B,
-                                                 loc_bs, _lib.LOC_SHIFT, int(has_fill), float(fill_value) if has_fill else 0.0,
-                                                 float(laplace_smoothing), _lib.ptr(sums), _lib.ptr(dice),
-                                                 _lib.ptr(minmax) if check_input_limits else None,
-                                                 int(_tune), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-            else:
-                rc = lib.nrt_warp_dice_soft_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(warped),
-                                                _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT,
-                                                int(has_fill), float(fill_value) if has_fill else 0.0,
-                                                float(laplace_smoothing), _lib.ptr(sums), _lib.ptr(dice),
-                                                _lib.ptr(minmax) if check_input_limits else None,
-                                                int(_tune), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_warp_dice_soft')
+        if bf16:
+            _lib.call(dev, 'nrt_warp_dice_soft_bf16', _lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ints(S), o_shape, L, B, loc_bs,
+                      _lib.LOC_SHIFT, int(has_fill), float(fill_value) if has_fill else 0.0, float(laplace_smoothing), _lib.ptr(sums),
+                      _lib.ptr(dice), _lib.ptr(minmax) if check_input_limits else None, int(_tune), _lib.ptr(ws), nws)
+        else:
+            _lib.call(dev, 'nrt_warp_dice_soft_f32', _lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(warped), _lib.ints(S),
+                      o_shape, L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill), float(fill_value) if has_fill else 0.0,
+                      float(laplace_smoothing), _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(minmax) if check_input_limits else None,
+                      int(_tune), _lib.ptr(ws), nws)
         if check_input_limits == 'deferred':
             from . import checked
             return checked.wrap(dice, minmax, 'fused warp + Dice')
@@ -128,11 +122,8 @@ def warp_dice(moving, trf, fixed, indexing='ij', single_transform=False, fill_va
     def run_backward(grad_dice):
         gshift = torch.empty((B,) + tuple(shift.shape[1:]), dtype=torch.float32, device=dev)
         g = grad_dice.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_warp_dice_bwd_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(sums), _lib.ptr(g),
-                                           _lib.ptr(gshift), _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT,
-                                           int(has_fill), float(laplace_smoothing), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_warp_dice_bwd_f32')
+        _lib.call(dev, 'nrt_warp_dice_bwd_f32', _lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(sums), _lib.ptr(g),
+                  _lib.ptr(gshift), _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill), float(laplace_smoothing))
         return gshift.sum(0, keepdim=True) if single_transform else gshift
 
     if torch.is_grad_enabled() and (moving.requires_grad or fixed.requires_grad):
@@ -223,21 +214,16 @@ def warp_dice_labels(moving, trf, fixed, nb_labels, indexing='ij', single_transf
     loc_bs = 0 if single_transform else shift[0].numel()
 
     def run():
-        with torch.cuda.device(dev):
-            rc = lib.nrt_warp_dice_labels_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(warped), _lib.ints(S), o_shape, L, B,
-                                              loc_bs, _lib.LOC_SHIFT, int(has_fill), 0.0, float(laplace_smoothing), _lib.ptr(sums),
-                                              _lib.ptr(dice), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_warp_dice_labels_f32')
+        _lib.call(dev, 'nrt_warp_dice_labels_f32', _lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(warped), _lib.ints(S), o_shape,
+                  L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill), 0.0, float(laplace_smoothing), _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(ws),
+                  nws)
         return dice
 
     def run_backward(grad_dice):
         gshift = torch.empty((B,) + tuple(shift.shape[1:]), dtype=torch.float32, device=dev)
         g = grad_dice.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_warp_dice_labels_bwd_f32(_lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(sums), _lib.ptr(g),
-                                                  _lib.ptr(gshift), _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill),
-                                                  float(laplace_smoothing), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_warp_dice_labels_bwd_f32')
+        _lib.call(dev, 'nrt_warp_dice_labels_bwd_f32', _lib.ptr(mov), _lib.ptr(shift), _lib.ptr(fix), _lib.ptr(sums), _lib.ptr(g),
+                  _lib.ptr(gshift), _lib.ints(S), o_shape, L, B, loc_bs, _lib.LOC_SHIFT, int(has_fill), float(laplace_smoothing))
         return gshift.sum(0, keepdim=True) if single_transform else gshift
 
     if torch.is_grad_enabled() and shift.requires_grad:
@@ -325,11 +311,8 @@ class _AffineWarpFn(torch.autograd.Function):
             o_shape = _lib.ints(O)
             nws = lib.nrt_affine_warp_workspace_bytes(D, o_shape, C, B)
             ws = _lib.workspace(dev, nws)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_affine_warp_bwd_f32(_lib.ptr(vol), _lib.ptr(matrix), _lib.ptr(g), _lib.ptr(gmat), D, _lib.ints(S), o_shape,
-                                                 C, B, Bm, int(cfg['shift_center']), cfg['method'], int(cfg['fill_value'] is not None),
-                                                 _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_affine_warp_bwd_f32')
+            _lib.call(dev, 'nrt_affine_warp_bwd_f32', _lib.ptr(vol), _lib.ptr(matrix), _lib.ptr(g), _lib.ptr(gmat), D, _lib.ints(S),
+                      o_shape, C, B, Bm, int(cfg['shift_center']), cfg['method'], int(cfg['fill_value'] is not None), _lib.ptr(ws), nws)
         if ctx.needs_input_grad[0]:
             shift = utils.affine_to_dense_shift(matrix.detach(), O, shift_center=cfg['shift_center'])
             bcfg = dict(out_spatial=O, loc_mode=_lib.LOC_SHIFT, method=cfg['method'], fill_value=cfg['fill_value'], batched=True,
@@ -339,17 +322,13 @@ class _AffineWarpFn(torch.autograd.Function):
 
 
 def _launch_affine_warp(vol, matrix, cfg):
-    lib = _lib.lib()
     dev = vol.device
     S, O = list(vol.shape[1:-1]), cfg['out_spatial']
     B, C = vol.shape[0], vol.shape[-1]
     out = torch.empty([B] + O + [C], dtype=torch.float32, device=dev)
     has_fill = cfg['fill_value'] is not None
-    with torch.cuda.device(dev):
-        rc = lib.nrt_affine_warp_f32(_lib.ptr(vol), _lib.ptr(matrix), _lib.ptr(out), len(S), _lib.ints(S), _lib.ints(O), C, B,
-                                     matrix.shape[0], int(cfg['shift_center']), cfg['method'], int(has_fill),
-                                     float(cfg['fill_value']) if has_fill else 0.0, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_affine_warp_f32')
+    _lib.call(dev, 'nrt_affine_warp_f32', _lib.ptr(vol), _lib.ptr(matrix), _lib.ptr(out), len(S), _lib.ints(S), _lib.ints(O), C, B,
+              matrix.shape[0], int(cfg['shift_center']), cfg['method'], int(has_fill), float(cfg['fill_value']) if has_fill else 0.0)
     return out
 
 

@@ -580,7 +580,6 @@ class RandomCrop(_Layer):
     def call(self, x):
         if self.prob == 0:
             return x
-        lib = _lib.lib()
         dev = _lib.require_device(x)
         if x.dtype != torch.float32:
             raise NotImplementedError('RandomCrop: float32 tensors, got %s' % x.dtype)
@@ -592,10 +591,8 @@ class RandomCrop(_Layer):
         y = torch.empty_like(x)
         outer = int(np.prod(x.shape[:ax])) if ax else 1
         inner = int(np.prod(x.shape[ax + 1:]))
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_axis_mask_f32(_lib.ptr(x), _lib.ptr(mask.reshape(-1).contiguous()), _lib.ptr(y), outer, x.shape[ax],
-                                             inner, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_synth_axis_mask_f32')
+        _lib.call(dev, 'nrt_synth_axis_mask_f32', _lib.ptr(x), _lib.ptr(mask.reshape(-1).contiguous()), _lib.ptr(y), outer, x.shape[ax],
+                  inner)
         return y
 
 
@@ -632,7 +629,6 @@ class GaussianNoise(_Layer):
     def call(self, x):
         if self.noise_max == 0 and not self.noise_only:
             return x
-        lib = _lib.lib()
         dev = _lib.require_device(x)
         if x.dtype != torch.float32:
             raise NotImplementedError('GaussianNoise: float32 tensors, got %s' % x.dtype)
@@ -657,10 +653,8 @@ class GaussianNoise(_Layer):
         self.last_draws = dict(sd=sd, noise=noise)
         base = torch.zeros_like(x) if self.noise_only else x
         y = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_noise_add_f32(_lib.ptr(base), _lib.ptr(noise), _lib.ptr(sd), _lib.ptr(y), B, x[0].numel() // C, C,
-                                             nc if nb > 1 else 0, 1 if nc > 1 else 0, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_synth_noise_add_f32')
+        _lib.call(dev, 'nrt_synth_noise_add_f32', _lib.ptr(base), _lib.ptr(noise), _lib.ptr(sd), _lib.ptr(y), B, x[0].numel() // C, C,
+                  nc if nb > 1 else 0, 1 if nc > 1 else 0)
         return y
 
 
@@ -822,15 +816,12 @@ class _Pad3dFn(torch.autograd.Function):
 
 
 def _pad3d(t, ins, before, padded, crop):
-    lib = _lib.lib()
     dev = _lib.require_device(t)
     B, C = t.shape[0], t.shape[-1]
     shape = [B] + list(ins if crop else padded) + [C]
     out = torch.empty(shape, dtype=t.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_pad3d(_lib.ptr(t), _lib.ptr(out), B, _lib.ints(ins), _lib.ints(before), _lib.ints(padded),
-                           C * t.element_size(), int(crop), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_pad3d')
+    _lib.call(dev, 'nrt_pad3d', _lib.ptr(t), _lib.ptr(out), B, _lib.ints(ins), _lib.ints(before), _lib.ints(padded), C * t.element_size(),
+              int(crop))
     return out
 
 
@@ -1014,7 +1005,6 @@ class LocallyConnected3D(_Layer):
         return dict(list(base_config.items()) + list(config.items()))
 
     def call(self, inputs):
-        lib = _lib.lib()
         dev = _lib.require_device(inputs, self.kernel)
         x = inputs
         if x.dim() != 5:
@@ -1050,11 +1040,8 @@ class LocallyConnected3D(_Layer):
         xd = x.detach()
 
         def run():
-            with torch.cuda.device(dev):
-                rc = lib.nrt_lc3d_f(_lib.ptr(xd), _lib.ptr(k), _lib.ptr(bias), _lib.ptr(y), dt, B, _lib.ints(S), cin,
-                                    _lib.ints(self.kernel_size), _lib.ints(self.strides), self.filters, kact,
-                                    int(self._variant), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_lc3d_f')
+            _lib.call(dev, 'nrt_lc3d_f', _lib.ptr(xd), _lib.ptr(k), _lib.ptr(bias), _lib.ptr(y), dt, B, _lib.ints(S), cin,
+                      _lib.ints(self.kernel_size), _lib.ints(self.strides), self.filters, kact, int(self._variant))
             if act > 2:
                 from .models import _elementwise
                 y.copy_(_elementwise(y.float(), act=act))        # in place: the backward reads the activated output
@@ -1065,11 +1052,8 @@ class LocallyConnected3D(_Layer):
             dk = torch.empty_like(k) if need_k else None
             db = torch.empty((int(np.prod(O)), self.filters), dtype=xd.dtype, device=dev) if need_b else None
             dx = torch.zeros(xd.shape, dtype=torch.float32, device=dev) if need_x else None
-            with torch.cuda.device(dev):
-                rc = lib.nrt_lc3d_bwd_f(_lib.ptr(xd), _lib.ptr(k), _lib.ptr(y), _lib.ptr(g), _lib.ptr(dk), _lib.ptr(db),
-                                        _lib.ptr(dx), dt, B, _lib.ints(S), cin, _lib.ints(self.kernel_size),
-                                        _lib.ints(self.strides), self.filters, act, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_lc3d_bwd_f')
+            _lib.call(dev, 'nrt_lc3d_bwd_f', _lib.ptr(xd), _lib.ptr(k), _lib.ptr(y), _lib.ptr(g), _lib.ptr(dk), _lib.ptr(db), _lib.ptr(dx),
+                      dt, B, _lib.ints(S), cin, _lib.ints(self.kernel_size), _lib.ints(self.strides), self.filters, act)
             return (None if dx is None else dx.to(xd.dtype)), dk, (None if db is None else db.reshape(bias.shape))
 
         needs = torch.is_grad_enabled() and (x.requires_grad or w1.requires_grad
@@ -1108,29 +1092,24 @@ def _hyperconv_run(x, kernel, bias, ksize3, dilation, same, kact, flipped=False)
     ci, co = (cout, cin) if flipped else (cin, cout)
     O = S if same else [S[d] - (ksize3[d] - 1) * dilation for d in range(3)]
     out = torch.empty([B] + O + [co], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        weights = packed = None
-        if lib.nrt_hyperconv3d_uses_packed(_lib.ints(S), _lib.ints(ksize3), ci, co, int(dilation), int(same)) == 1:
-            n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(ksize3), ci, co)
-            packed = torch.empty(B * int(n), dtype=torch.float32, device=dev)
-            rc = lib.nrt_hyperconv3d_pack_weights_f32(_lib.ptr(kernel), B, _lib.ints(ksize3), cin, cout, int(flipped),
-                                                      _lib.ptr(packed), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_hyperconv3d_pack_weights_f32')
-        else:
-            # the direct and single-input-channel kernels read the Keras layout (one batched re-layout for the input gradient)
-            weights = kernel.flip(1, 2, 3).transpose(4, 5).contiguous() if flipped else kernel
-        if flipped:
-            # the transpose of a 'same' convolution pads (k - 1) * dilation - (k - 1) * dilation // 2 before (even kernels: one more
-            # than 'same' does)
-            from .models import _dgrad_pad_before
-            rc = lib.nrt_hyperconv3d_pad_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
-                                             _lib.ints(S), _lib.ints(ksize3), co, int(dilation),
-                                             _lib.ints(_dgrad_pad_before(ksize3, dilation)), int(kact), 0, _lib.stream_ptr(dev))
-        else:
-            rc = lib.nrt_hyperconv3d_f32(_lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
-                                         _lib.ints(S), _lib.ints(ksize3), co, int(dilation), int(same), int(kact), 0,
-                                         _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_hyperconv3d_f32')
+    weights = packed = None
+    if lib.nrt_hyperconv3d_uses_packed(_lib.ints(S), _lib.ints(ksize3), ci, co, int(dilation), int(same)) == 1:
+        n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(ksize3), ci, co)
+        packed = torch.empty(B * int(n), dtype=torch.float32, device=dev)
+        _lib.call(dev, 'nrt_hyperconv3d_pack_weights_f32', _lib.ptr(kernel), B, _lib.ints(ksize3), cin, cout, int(flipped),
+                  _lib.ptr(packed))
+    else:
+        # the direct and single-input-channel kernels read the Keras layout (one batched re-layout for the input gradient)
+        weights = kernel.flip(1, 2, 3).transpose(4, 5).contiguous() if flipped else kernel
+    if flipped:
+        # the transpose of a 'same' convolution pads (k - 1) * dilation - (k - 1) * dilation // 2 before (even kernels: one more
+        # than 'same' does)
+        from .models import _dgrad_pad_before
+        _lib.call(dev, 'nrt_hyperconv3d_pad_f32', _lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
+                  _lib.ints(S), _lib.ints(ksize3), co, int(dilation), _lib.ints(_dgrad_pad_before(ksize3, dilation)), int(kact), 0)
+    else:
+        _lib.call(dev, 'nrt_hyperconv3d_f32', _lib.ptr(x), ci, _lib.ptr(weights), _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(out), B,
+                  _lib.ints(S), _lib.ints(ksize3), co, int(dilation), int(same), int(kact), 0)
     return out
 
 
@@ -1153,7 +1132,6 @@ class _HyperConvFn(torch.autograd.Function):
         from .models import _act_bwd
         x, kernel, out = ctx.saved_tensors
         ksize3, dilation, same, act = ctx.cfg
-        lib = _lib.lib()
         dev = g.device
         dpre = _act_bwd(g, out, act)
         B, S = x.shape[0], list(x.shape[1:4])
@@ -1168,10 +1146,8 @@ class _HyperConvFn(torch.autograd.Function):
         if need_k or need_b:
             dk = torch.zeros_like(kernel)
             db = torch.zeros(B, cout, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_hyperconv3d_wgrad_f32(_lib.ptr(x), _lib.ptr(dpre), _lib.ptr(dk), _lib.ptr(db), B, _lib.ints(S), cin,
-                                                   cout, _lib.ints(ksize3), dilation, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_hyperconv3d_wgrad_f32')
+            _lib.call(dev, 'nrt_hyperconv3d_wgrad_f32', _lib.ptr(x), _lib.ptr(dpre), _lib.ptr(dk), _lib.ptr(db), B, _lib.ints(S), cin, cout,
+                      _lib.ints(ksize3), dilation)
         if need_x:
             dx = _hyperconv_run(dpre, kernel, None, ksize3, dilation, True, 0, flipped=True)
         return dx, dk if need_k else None, db if need_b else None, None, None, None, None
@@ -1591,25 +1567,18 @@ def _local_init(what, initializer, shape, device, normal=(0.0, 0.05)):
 
 def _local_affine_launch(x, probe, mult, bias, bias_scale, B, n, dev):
     """nrt_local_affine_f32 on contiguous float32 tensors; probe: the tensor whose entries' first elements give the factors e[b]"""
-    lib = _lib.lib()
     y = torch.empty((B, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_local_affine_f32(_lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0), _lib.ptr(mult),
-                                      _lib.ptr(bias), float(bias_scale), _lib.ptr(y), B, n, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_local_affine_f32')
+    _lib.call(dev, 'nrt_local_affine_f32', _lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0), _lib.ptr(mult),
+              _lib.ptr(bias), float(bias_scale), _lib.ptr(y), B, n)
     return y
 
 
 def _local_affine_bwd_launch(g, x, probe, mult, bias_scale, need_x, need_mult, need_bias, B, n, dev):
-    lib = _lib.lib()
     gx = torch.empty((B, n), dtype=torch.float32, device=dev) if need_x else None
     gm = torch.empty(n, dtype=torch.float32, device=dev) if need_mult else None
     gb = torch.empty(n, dtype=torch.float32, device=dev) if need_bias else None
-    with torch.cuda.device(dev):
-        rc = lib.nrt_local_affine_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0),
-                                          _lib.ptr(mult), float(bias_scale), _lib.ptr(gx), _lib.ptr(gm), _lib.ptr(gb), B, n,
-                                          _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_local_affine_bwd_f32')
+    _lib.call(dev, 'nrt_local_affine_bwd_f32', _lib.ptr(g), _lib.ptr(x), _lib.ptr(probe), 0 if probe is None else probe.stride(0),
+              _lib.ptr(mult), float(bias_scale), _lib.ptr(gx), _lib.ptr(gm), _lib.ptr(gb), B, n)
     return gx, gm, gb
 
 
@@ -1729,15 +1698,11 @@ class _CrossLinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias):
-        lib = _lib.lib()
         dev = x.device
         cin, cout = w.shape[-2], w.shape[-1]
         B, V = x.shape[0], x[0].numel() // cin
         y = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_local_cross_linear_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, V, cin, cout,
-                                                _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_local_cross_linear_f32')
+        _lib.call(dev, 'nrt_local_cross_linear_f32', _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B, V, cin, cout)
         ctx.save_for_backward(x, w)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
         return y
@@ -1745,7 +1710,6 @@ class _CrossLinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         cin, cout = w.shape[-2], w.shape[-1]
@@ -1754,10 +1718,8 @@ class _CrossLinearFn(torch.autograd.Function):
         gx = torch.empty_like(x) if need_x else None
         gw = torch.empty_like(w) if need_w else None
         gb = torch.empty(ctx.bias_shape, dtype=torch.float32, device=dev) if need_b else None
-        with torch.cuda.device(dev):
-            rc = lib.nrt_local_cross_linear_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(w), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), B, V,
-                                                    cin, cout, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_local_cross_linear_bwd_f32')
+        _lib.call(dev, 'nrt_local_cross_linear_bwd_f32', _lib.ptr(g), _lib.ptr(x), _lib.ptr(w), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), B,
+                  V, cin, cout)
         return gx, gw, gb
 
 
@@ -1923,13 +1885,10 @@ class _StreamMeanFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         coef, = ctx.saved_tensors
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         gx = torch.empty_like(g)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_stream_mean_bwd_f32(_lib.ptr(g), _lib.ptr(coef), _lib.ptr(gx), g.shape[0], g[0].numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_stream_mean_bwd_f32')
+        _lib.call(dev, 'nrt_stream_mean_bwd_f32', _lib.ptr(g), _lib.ptr(coef), _lib.ptr(gx), g.shape[0], g[0].numel())
         return gx, None
 
 
@@ -1978,14 +1937,11 @@ class MeanStream(_StreamLayer):
         self.built = True
 
     def _run(self, x, training, dev):
-        lib = _lib.lib()
         B, n = x.shape[0], self.mean.numel()
         y = torch.empty(x.shape, dtype=torch.float32, device=dev)
         coef = torch.empty(1, dtype=torch.float32, device=dev) if training else None
-        with torch.cuda.device(dev):
-            rc = lib.nrt_stream_mean_f32(_lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.count), self.cap, _lib.ptr(y), _lib.ptr(coef),
-                                         B, n, int(training), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_stream_mean_f32')
+        _lib.call(dev, 'nrt_stream_mean_f32', _lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.count), self.cap, _lib.ptr(y), _lib.ptr(coef),
+                  B, n, int(training))
         return y, coef
 
     def call(self, x, training=None):
@@ -2026,14 +1982,11 @@ class CovStream(_StreamLayer):
             raise NotImplementedError('CovStream: the gradient with respect to the input is not implemented; detach the input')
         dev = self._prepare(x)
         _lib.require_device(x, self.cov)
-        lib = _lib.lib()
         x = x.detach().contiguous()
         B, v = x.shape[0], self.cov.shape[0]
         y = torch.empty((B, v, v), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_stream_cov_f32(_lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.cov), _lib.ptr(self.count), self.cap, _lib.ptr(y),
-                                        B, v, int(bool(training)), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_stream_cov_f32')
+        _lib.call(dev, 'nrt_stream_cov_f32', _lib.ptr(x), _lib.ptr(self.mean), _lib.ptr(self.cov), _lib.ptr(self.count), self.cap,
+                  _lib.ptr(y), B, v, int(bool(training)))
         return y
 
 

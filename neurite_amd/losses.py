@@ -141,9 +141,7 @@ class _NCCFn(torch.autograd.Function):
         else:
             out = torch.empty(tuple(I.shape[:-1]) + (1,), dtype=torch.float32, device=dev)
             args = (None, _lib.ptr(out), None, None, 0)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_ncc_f32(_lib.ptr(I), _lib.ptr(J), batch, cshape, channels, cwin, eps, *args, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_ncc_f32')
+        _lib.call(dev, 'nrt_ncc_f32', _lib.ptr(I), _lib.ptr(J), batch, cshape, channels, cwin, eps, *args)
         ctx.save_for_backward(I, J)
         ctx.cfg = (batch, shape, channels, tuple(win), eps, as_loss)
         return out
@@ -163,10 +161,8 @@ class _NCCFn(torch.autograd.Function):
         cshape, cwin = _lib.ints(shape), _lib.ints(win)
         nws = int(lib.nrt_ncc_workspace_bytes(batch, cshape, channels, cwin))
         ws = _lib.workspace(dev, max(nws, 16))
-        with torch.cuda.device(dev):
-            rc = lib.nrt_ncc_bwd_f32(_lib.ptr(I), _lib.ptr(J), None if as_loss else _lib.ptr(g), _lib.ptr(g) if as_loss else None, batch,
-                                     cshape, channels, cwin, eps, _lib.ptr(gI), _lib.ptr(gJ), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_ncc_bwd_f32')
+        _lib.call(dev, 'nrt_ncc_bwd_f32', _lib.ptr(I), _lib.ptr(J), None if as_loss else _lib.ptr(g), _lib.ptr(g) if as_loss else None,
+                  batch, cshape, channels, cwin, eps, _lib.ptr(gI), _lib.ptr(gJ), _lib.ptr(ws), nws)
         return gI, gJ, None, None, None
 
 
@@ -239,16 +235,13 @@ class _GradLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, penalty, mult):
-        lib = _lib.lib()
         dev = y.device
         batch, shape, nd, channels = _spatial3(y)
         loss = torch.empty((batch,), dtype=torch.float32, device=dev)
         nws = batch * 6144
         ws = _lib.workspace(dev, nws)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_grad_loss_f32(_lib.ptr(y), batch, _lib.ints(shape), nd, channels, penalty, mult, _lib.ptr(loss), _lib.ptr(ws), nws,
-                                       _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_grad_loss_f32')
+        _lib.call(dev, 'nrt_grad_loss_f32', _lib.ptr(y), batch, _lib.ints(shape), nd, channels, penalty, mult, _lib.ptr(loss), _lib.ptr(ws),
+                  nws)
         ctx.save_for_backward(y)
         ctx.cfg = (batch, shape, nd, channels, penalty, mult)
         return loss
@@ -257,14 +250,11 @@ class _GradLossFn(torch.autograd.Function):
     def backward(ctx, g):
         y, = ctx.saved_tensors
         batch, shape, nd, channels, penalty, mult = ctx.cfg
-        lib = _lib.lib()
         dev = y.device
         g = g.to(torch.float32).contiguous()
         gy = torch.empty_like(y)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_grad_loss_bwd_f32(_lib.ptr(y), _lib.ptr(g), batch, _lib.ints(shape), nd, channels, penalty, mult, _lib.ptr(gy),
-                                           _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_grad_loss_bwd_f32')
+        _lib.call(dev, 'nrt_grad_loss_bwd_f32', _lib.ptr(y), _lib.ptr(g), batch, _lib.ints(shape), nd, channels, penalty, mult,
+                  _lib.ptr(gy))
         return gy, None, None
 
 

@@ -74,19 +74,13 @@ def dice_partial_sums(y_true, y_pred, normalize=False, laplace_smoothing=0.):
         if B * L == 0:
             return sums, dice, minmax.fill_(0)
         sums.zero_()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_dice_from_sums_f32(_lib.ptr(sums), L, B, float(laplace_smoothing), _lib.ptr(dice),
-                                            _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_dice_from_sums_f32')
+        _lib.call(dev, 'nrt_dice_from_sums_f32', _lib.ptr(sums), L, B, float(laplace_smoothing), _lib.ptr(dice))
         minmax.copy_(torch.tensor([float('inf'), float('-inf'), float('inf'), float('-inf')]))
         return sums, dice, minmax
     nws = lib.nrt_dice_workspace_bytes(V, L, B)
     ws = _lib.workspace(dev, nws)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_dice_soft(_lib.ptr(t), _lib.ptr(p), dt, V, L, B, int(bool(normalize)),
-                               float(laplace_smoothing), _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(minmax),
-                               _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_dice_soft')
+    _lib.call(dev, 'nrt_dice_soft', _lib.ptr(t), _lib.ptr(p), dt, V, L, B, int(bool(normalize)), float(laplace_smoothing), _lib.ptr(sums),
+              _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(ws), nws)
     return sums, dice, minmax
 
 
@@ -108,7 +102,6 @@ class _SoftDiceFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_dice):
         t, p, sums = ctx.saved_tensors
-        lib = _lib.lib()
         dev = t.device
         B, L = t.shape[0], t.shape[-1]
         V = t.numel() // max(B * L, 1)
@@ -116,11 +109,8 @@ class _SoftDiceFn(torch.autograd.Function):
         gt = torch.empty_like(t) if ctx.needs_input_grad[0] else None
         gp = torch.empty_like(p) if ctx.needs_input_grad[1] else None
         if t.numel() and (gt is not None or gp is not None):
-            fn = lib.nrt_dice_soft_bwd_norm_f32 if ctx.normalize else lib.nrt_dice_soft_bwd_f32
-            with torch.cuda.device(dev):
-                rc = fn(_lib.ptr(t), _lib.ptr(p), _lib.ptr(sums), _lib.ptr(g), V, L, B, float(ctx.eps), _lib.ptr(gp),
-                        _lib.ptr(gt), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_dice_soft_bwd(_norm)_f32')
+            _lib.call(dev, 'nrt_dice_soft_bwd_norm_f32' if ctx.normalize else 'nrt_dice_soft_bwd_f32', _lib.ptr(t), _lib.ptr(p),
+                      _lib.ptr(sums), _lib.ptr(g), V, L, B, float(ctx.eps), _lib.ptr(gp), _lib.ptr(gt))
         if gt is not None:
             gt = gt.to(ctx.in_dtypes[0])
         if gp is not None:
@@ -140,16 +130,12 @@ def _wcce_launch(t, p, w, from_logits, label_smoothing, per_voxel, divide_by=Non
     nws = lib.nrt_wcce_workspace_bytes(N, yf)
     ws = _lib.workspace(dev, nws)
     dt = _lib.DT_F32 if p.dtype == torch.float32 else _lib.DT_BF16
-    with torch.cuda.device(dev):
-        if divide_by is None:
-            rc = lib.nrt_wcce(_lib.ptr(t), _lib.ptr(p), dt, _lib.ptr(w), N, yf, int(from_logits),
-                              float(label_smoothing), _lib.ptr(loss_sum), _lib.ptr(pv), _lib.ptr(ws), nws,
-                              _lib.stream_ptr(dev))
-        else:
-            rc = lib.nrt_wcce_mean(_lib.ptr(t), _lib.ptr(p), dt, _lib.ptr(w), N, yf, int(from_logits),
-                                   float(label_smoothing), float(divide_by), _lib.ptr(loss_sum), _lib.ptr(pv), _lib.ptr(ws), nws,
-                                   _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_wcce' if divide_by is None else 'nrt_wcce_mean')
+    if divide_by is None:
+        _lib.call(dev, 'nrt_wcce', _lib.ptr(t), _lib.ptr(p), dt, _lib.ptr(w), N, yf, int(from_logits), float(label_smoothing),
+                  _lib.ptr(loss_sum), _lib.ptr(pv), _lib.ptr(ws), nws)
+    else:
+        _lib.call(dev, 'nrt_wcce_mean', _lib.ptr(t), _lib.ptr(p), dt, _lib.ptr(w), N, yf, int(from_logits), float(label_smoothing),
+                  float(divide_by), _lib.ptr(loss_sum), _lib.ptr(pv), _lib.ptr(ws), nws)
     return pv if per_voxel else loss_sum
 
 
@@ -176,18 +162,14 @@ class _WcceFn(torch.autograd.Function):
             grad = grad / float(divide_by)
         if p.dtype != torch.float32:
             raise NotImplementedError('neurite_amd: CCE backward takes float32 inputs')
-        lib = _lib.lib()
         dev = p.device
         yf = p.shape[-1]
         N = p.numel() // max(yf, 1)
         g = grad.to(torch.float32).contiguous()
         gp = torch.empty_like(p)
         if N:
-            with torch.cuda.device(dev):
-                rc = lib.nrt_wcce_bwd_f32(_lib.ptr(t), _lib.ptr(p), _lib.ptr(w), None if per_voxel else _lib.ptr(g),
-                                          _lib.ptr(g) if per_voxel else None, N, yf, int(from_logits),
-                                          float(label_smoothing), 1.0, _lib.ptr(gp), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_wcce_bwd_f32')
+            _lib.call(dev, 'nrt_wcce_bwd_f32', _lib.ptr(t), _lib.ptr(p), _lib.ptr(w), None if per_voxel else _lib.ptr(g),
+                      _lib.ptr(g) if per_voxel else None, N, yf, int(from_logits), float(label_smoothing), 1.0, _lib.ptr(gp))
         return None, gp, None, None, None, None, None
 
 
@@ -212,10 +194,8 @@ class _SegLossFn(torch.autograd.Function):
         cce_sum = torch.empty((1,), dtype=torch.float32, device=dev)
         nws = lib.nrt_seg_loss_workspace_bytes(V, L, B)
         ws = _lib.workspace(dev, nws)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_seg_loss_f32(_lib.ptr(t), _lib.ptr(p), _lib.ptr(w), V, L, B, float(smoothing), float(eps), _lib.ptr(sums),
-                                      _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(cce_sum), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_seg_loss_f32')
+        _lib.call(dev, 'nrt_seg_loss_f32', _lib.ptr(t), _lib.ptr(p), _lib.ptr(w), V, L, B, float(smoothing), float(eps), _lib.ptr(sums),
+                  _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(cce_sum), _lib.ptr(ws), nws)
         if check_limits:
             _check_limits(minmax)
         ctx.save_for_backward(t, p, w, sums)
@@ -229,17 +209,14 @@ class _SegLossFn(torch.autograd.Function):
         src = ctx.src
         if ctx.needs_input_grad[0]:
             raise NotImplementedError('neurite_amd: the joint Dice + CCE loss has no gradient wrt y_true')
-        lib = _lib.lib()
         dev = p.device
         B, L = p.shape[0], p.shape[-1]
         V = p.numel() // (B * L)
         g_cce = g_cce.to(torch.float32).contiguous()
         g_dice = g_dice.to(torch.float32).contiguous()
         grad = torch.empty_like(p)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_seg_loss_bwd_f32(_lib.ptr(t), _lib.ptr(p), _lib.ptr(w), _lib.ptr(sums), _lib.ptr(g_dice), _lib.ptr(g_cce), V, L, B,
-                                          float(smoothing), float(eps), int(src is not None), _lib.ptr(grad), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_seg_loss_bwd_f32')
+        _lib.call(dev, 'nrt_seg_loss_bwd_f32', _lib.ptr(t), _lib.ptr(p), _lib.ptr(w), _lib.ptr(sums), _lib.ptr(g_dice), _lib.ptr(g_cce), V,
+                  L, B, float(smoothing), float(eps), int(src is not None), _lib.ptr(grad))
         if src is None:
             return (None, grad, None, None, None)
         return (None, None, None, None, None) + tuple(src.grads_from_dz(grad, ctx.needs_input_grad[5:]))
@@ -311,11 +288,8 @@ class _SegLossLabelsFn(torch.autograd.Function):
         cce_sum = torch.empty((1,), dtype=torch.float32, device=dev) if wc else None
         nws = lib.nrt_seg_loss_labels_workspace_bytes(V, L, B)
         ws = _lib.workspace(dev, nws)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_seg_loss_labels_f32(_lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), V, L, B, int(want), float(smoothing), float(eps),
-                                             _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(cce_sum), _lib.ptr(ws), nws,
-                                             _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_seg_loss_labels_f32')
+        _lib.call(dev, 'nrt_seg_loss_labels_f32', _lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), V, L, B, int(want), float(smoothing), float(eps),
+                  _lib.ptr(sums), _lib.ptr(dice), _lib.ptr(minmax), _lib.ptr(cce_sum), _lib.ptr(ws), nws)
         if minmax is not None:
             _check_limits(minmax)                      # (0, 1, min p, max p): an id cannot leave [0, 1]
         ctx.save_for_backward(ids, p, w, sums)
@@ -327,18 +301,14 @@ class _SegLossLabelsFn(torch.autograd.Function):
         ids, p, w, sums = ctx.saved_tensors
         eps, smoothing, _ = ctx.cfg
         src = ctx.src
-        lib = _lib.lib()
         dev = p.device
         B, L = p.shape[0], p.shape[-1]
         V = p.numel() // (B * L)
         g_cce = g_cce.to(torch.float32).contiguous() if ctx.want & _lib.SEG_WANT_CCE else None
         g_dice = g_dice.to(torch.float32).contiguous() if ctx.want & _lib.SEG_WANT_DICE else None
         grad = torch.empty_like(p)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_seg_loss_labels_bwd_f32(_lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), _lib.ptr(sums), _lib.ptr(g_dice), _lib.ptr(g_cce),
-                                                 V, L, B, float(smoothing), float(eps), int(src is not None), _lib.ptr(grad),
-                                                 _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_seg_loss_labels_bwd_f32')
+        _lib.call(dev, 'nrt_seg_loss_labels_bwd_f32', _lib.ptr(ids), _lib.ptr(p), _lib.ptr(w), _lib.ptr(sums), _lib.ptr(g_dice),
+                  _lib.ptr(g_cce), V, L, B, float(smoothing), float(eps), int(src is not None), _lib.ptr(grad))
         if src is None:
             return (None, grad, None, None, None, None)
         return (None, None, None, None, None, None) + tuple(src.grads_from_dz(grad, ctx.needs_input_grad[6:]))
@@ -578,10 +548,8 @@ class Dice:
             nws = lib.nrt_dice_workspace_bytes(V, L, B)
             ws = _lib.workspace(dev, nws)
             mm = torch.empty((4,), dtype=torch.float32, device=dev) if fused_limits else None
-            with torch.cuda.device(dev):
-                rc = lib.nrt_dice_hard_prob(_lib.ptr(t), _lib.ptr(p), dt, V, L, B, eps, _lib.ptr(counts), _lib.ptr(d),
-                                            _lib.ptr(mm) if fused_limits else None, _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_dice_hard_prob')
+            _lib.call(dev, 'nrt_dice_hard_prob', _lib.ptr(t), _lib.ptr(p), dt, V, L, B, eps, _lib.ptr(counts), _lib.ptr(d),
+                      _lib.ptr(mm) if fused_limits else None, _lib.ptr(ws), nws)
             if fused_limits:
                 _check_limits(mm)
             return d
@@ -604,10 +572,8 @@ class Dice:
         # the atomic form, whose workspace is nothing (the row buffer grows with 2048 * 3 * L per batch entry)
         nws = lib.nrt_dice_workspace_bytes(V, L, B) if L <= 256 else 0
         ws = _lib.workspace(dev, nws) if nws else None
-        with torch.cuda.device(dev):
-            rc = lib.nrt_dice_hard_label_i32(_lib.ptr(t), _lib.ptr(p), V, L, B, eps, _lib.ptr(counts),
-                                             _lib.ptr(d), _lib.ptr(ws) if nws else None, nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_dice_hard_label_i32')
+        _lib.call(dev, 'nrt_dice_hard_label_i32', _lib.ptr(t), _lib.ptr(p), V, L, B, eps, _lib.ptr(counts), _lib.ptr(d),
+                  _lib.ptr(ws) if nws else None, nws)
         return d
 
     def mean_dice(self, y_true, y_pred):
@@ -719,7 +685,6 @@ class CategoricalCrossentropy:
             lf = self.label_weights.shape[-1]
             if yf != lf:                                                                  # metrics.py:644-645
                 raise ValueError(f'Label weights must be of len {yf}, but got {lf}.')
-        lib = _lib.lib()
         dev = _lib.require_device(y_true, y_pred)
         need_pv = sample_weight is not None or self.reduction == 'none'
         joint = None if need_pv else JointSegLoss.lookup(self, y_true, y_pred)
@@ -796,10 +761,7 @@ class _MseProbFn(torch.autograd.Function):
         scratch = torch.empty((B, L), dtype=torch.float32, device=dev)
         nws = lib.nrt_dice_workspace_bytes(V, L, B)
         ws = _lib.workspace(dev, nws)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_sqdiff_sums_f32(_lib.ptr(tc), _lib.ptr(pc), V, L, B, _lib.ptr(sums), _lib.ptr(scratch), _lib.ptr(ws), nws,
-                                         _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_sqdiff_sums_f32')
+        _lib.call(dev, 'nrt_sqdiff_sums_f32', _lib.ptr(tc), _lib.ptr(pc), V, L, B, _lib.ptr(sums), _lib.ptr(scratch), _lib.ptr(ws), nws)
         per_label = sums[:, 1].double().sum(0)                                                             # [L] sum d^2
         ctx.save_for_backward(t, p, w)
         return (per_label * w.double()).sum().to(torch.float32)
@@ -807,7 +769,6 @@ class _MseProbFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         t, p, w = ctx.saved_tensors
-        lib = _lib.lib()
         dev = p.device
         L = p.shape[-1]
         ca = (2.0 * w * g).to(torch.float32).contiguous()
@@ -817,16 +778,12 @@ class _MseProbFn(torch.autograd.Function):
         pc, tc = p.contiguous(), t.contiguous()
         if ctx.needs_input_grad[1]:
             dp = torch.empty_like(pc)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_channel_axpby_f32(_lib.ptr(pc), _lib.ptr(tc), _lib.ptr(ca), _lib.ptr(cb), _lib.ptr(zero), _lib.ptr(dp),
-                                               pc.numel(), L, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_channel_axpby_f32')
+            _lib.call(dev, 'nrt_channel_axpby_f32', _lib.ptr(pc), _lib.ptr(tc), _lib.ptr(ca), _lib.ptr(cb), _lib.ptr(zero), _lib.ptr(dp),
+                      pc.numel(), L)
         if ctx.needs_input_grad[0]:
             dt = torch.empty_like(tc)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_channel_axpby_f32(_lib.ptr(tc), _lib.ptr(pc), _lib.ptr(ca), _lib.ptr(cb), _lib.ptr(zero), _lib.ptr(dt),
-                                               tc.numel(), L, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_channel_axpby_f32')
+            _lib.call(dev, 'nrt_channel_axpby_f32', _lib.ptr(tc), _lib.ptr(pc), _lib.ptr(ca), _lib.ptr(cb), _lib.ptr(zero), _lib.ptr(dt),
+                      tc.numel(), L)
         return dt, dp, None
 
 
@@ -886,13 +843,10 @@ def _mi_from_joint(joint, sx, sy, eps=1e-7):
     the tiny tensors, so that autodiff supplies d mi / d joint for the backward kernel; otherwise one kernel (csrc/mi.hip)."""
     needs_graph = torch.is_grad_enabled() and (joint.requires_grad or sx.requires_grad or sy.requires_grad)
     if not needs_graph and joint.is_cuda and joint.shape[-1] <= 64:
-        lib = _lib.lib()
         joint, sx, sy = joint.contiguous(), sx.contiguous(), sy.contiguous()
         mi = torch.empty((joint.shape[0],), dtype=torch.float32, device=joint.device)
-        with torch.cuda.device(joint.device):
-            rc = lib.nrt_mi_from_joint_f32(_lib.ptr(joint), _lib.ptr(sx), _lib.ptr(sy), int(joint.shape[0]), int(joint.shape[-1]),
-                                           float(eps), _lib.ptr(mi), _lib.stream_ptr(joint.device))
-        _lib.check(rc, 'nrt_mi_from_joint_f32')
+        _lib.call(joint.device, 'nrt_mi_from_joint_f32', _lib.ptr(joint), _lib.ptr(sx), _lib.ptr(sy), int(joint.shape[0]),
+                  int(joint.shape[-1]), float(eps), _lib.ptr(mi))
         return mi
     pxy = joint / (joint.sum((1, 2), keepdim=True) + eps)
     px = sx / (sx.sum(1, keepdim=True) + eps)
@@ -906,7 +860,6 @@ class _MiJointFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, cx, cy, alpha, lo, hi):
-        lib = _lib.lib()
         dev = x.device
         B, V, C = x.shape
         nb = cx.numel()
@@ -914,10 +867,8 @@ class _MiJointFn(torch.autograd.Function):
         joint = acc[:B * C * nb * nb].view(B * C, nb, nb)
         sx = acc[B * C * nb * nb:B * C * (nb * nb + nb)].view(B * C, nb)
         sy = acc[B * C * (nb * nb + nb):].view(B * C, nb)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_mi_joint_f32(_lib.ptr(x), _lib.ptr(y), _lib.ptr(cx), _lib.ptr(cy), float(alpha), float(lo), float(hi),
-                                      B, V, C, nb, _lib.ptr(joint), _lib.ptr(sx), _lib.ptr(sy), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_mi_joint_f32')
+        _lib.call(dev, 'nrt_mi_joint_f32', _lib.ptr(x), _lib.ptr(y), _lib.ptr(cx), _lib.ptr(cy), float(alpha), float(lo), float(hi), B, V,
+                  C, nb, _lib.ptr(joint), _lib.ptr(sx), _lib.ptr(sy))
         ctx.save_for_backward(x, y, cx, cy)
         ctx.cfg = (float(alpha), float(lo), float(hi))
         return joint, sx, sy
@@ -926,7 +877,6 @@ class _MiJointFn(torch.autograd.Function):
     def backward(ctx, gj, gsx, gsy):
         x, y, cx, cy = ctx.saved_tensors
         alpha, lo, hi = ctx.cfg
-        lib = _lib.lib()
         dev = x.device
         B, V, C = x.shape
         nb = cx.numel()
@@ -937,11 +887,8 @@ class _MiJointFn(torch.autograd.Function):
         gj = torch.zeros((B * C, nb, nb), dtype=torch.float32, device=dev) if gj is None else gj.contiguous()
         gsx = torch.zeros((B * C, nb), dtype=torch.float32, device=dev) if gsx is None else gsx.contiguous()
         gsy = torch.zeros((B * C, nb), dtype=torch.float32, device=dev) if gsy is None else gsy.contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_mi_joint_bwd_f32(_lib.ptr(x), _lib.ptr(y), _lib.ptr(cx), _lib.ptr(cy), alpha, lo, hi, B, V, C, nb,
-                                          _lib.ptr(gj), _lib.ptr(gsx), _lib.ptr(gsy), _lib.ptr(gx), _lib.ptr(gy),
-                                          _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_mi_joint_bwd_f32')
+        _lib.call(dev, 'nrt_mi_joint_bwd_f32', _lib.ptr(x), _lib.ptr(y), _lib.ptr(cx), _lib.ptr(cy), alpha, lo, hi, B, V, C, nb,
+                  _lib.ptr(gj), _lib.ptr(gsx), _lib.ptr(gsy), _lib.ptr(gx), _lib.ptr(gy))
         return gx, gy, None, None, None, None, None
 
 
@@ -952,27 +899,22 @@ class _MiMapsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xf, yf):
-        lib = _lib.lib()
         dev = xf.device
         bs, V, Bn = xf.shape
         joint = torch.zeros((bs, Bn, Bn), dtype=torch.float32, device=dev)
         sx = torch.zeros((bs, Bn), dtype=torch.float32, device=dev)
         sy = torch.zeros((bs, Bn), dtype=torch.float32, device=dev)
         shape = [V // 32, 4, 8] if V % 32 == 0 else [V, 1, 1]
-        with torch.cuda.device(dev):
-            for b in range(bs):
-                rc = lib.nrt_conv3d_wgrad_f32(_lib.ptr(xf[b]), _lib.ptr(yf[b]), _lib.ptr(joint[b]), _lib.ptr(sy[b]), 1,
-                                              _lib.ints(shape), Bn, Bn, _lib.ints([1, 1, 1]), 1, _lib.stream_ptr(dev))
-                _lib.check(rc, 'nrt_conv3d_wgrad_f32')
-            rc = lib.nrt_colsum_f32(_lib.ptr(xf), bs, V, Bn, _lib.ptr(sx), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_colsum_f32')
+        for b in range(bs):
+            _lib.call(dev, 'nrt_conv3d_wgrad_f32', _lib.ptr(xf[b]), _lib.ptr(yf[b]), _lib.ptr(joint[b]), _lib.ptr(sy[b]), 1,
+                      _lib.ints(shape), Bn, Bn, _lib.ints([1, 1, 1]), 1)
+        _lib.call(dev, 'nrt_colsum_f32', _lib.ptr(xf), bs, V, Bn, _lib.ptr(sx))
         ctx.save_for_backward(xf, yf)
         return joint, sx, sy
 
     @staticmethod
     def backward(ctx, gj, gsx, gsy):
         xf, yf = ctx.saved_tensors
-        lib = _lib.lib()
         dev = xf.device
         bs, V, Bn = xf.shape
         if Bn > 64:
@@ -983,16 +925,13 @@ class _MiMapsFn(torch.autograd.Function):
         gx = torch.empty_like(xf) if ctx.needs_input_grad[0] else None
         gy = torch.empty_like(yf) if ctx.needs_input_grad[1] else None
         gjt = gj.transpose(1, 2).contiguous()
-        with torch.cuda.device(dev):
-            for b in range(bs):
-                if gx is not None:          # dx[v, i] = sum_j y[v, j] gJ[i, j] + gsx[i]: weights [cin = j][cout = i] = gJ^T
-                    rc = lib.nrt_conv1x1_softmax_f32(_lib.ptr(yf[b]), _lib.ptr(gjt[b]), _lib.ptr(gsx[b]), _lib.ptr(gx[b]), V, Bn, Bn,
-                                                     0, 0, _lib.stream_ptr(dev))
-                    _lib.check(rc, 'nrt_conv1x1_softmax_f32')
-                if gy is not None:          # dy[v, j] = sum_i x[v, i] gJ[i, j] + gsy[j]
-                    rc = lib.nrt_conv1x1_softmax_f32(_lib.ptr(xf[b]), _lib.ptr(gj[b]), _lib.ptr(gsy[b]), _lib.ptr(gy[b]), V, Bn, Bn,
-                                                     0, 0, _lib.stream_ptr(dev))
-                    _lib.check(rc, 'nrt_conv1x1_softmax_f32')
+        for b in range(bs):
+            if gx is not None:          # dx[v, i] = sum_j y[v, j] gJ[i, j] + gsx[i]: weights [cin = j][cout = i] = gJ^T
+                _lib.call(dev, 'nrt_conv1x1_softmax_f32', _lib.ptr(yf[b]), _lib.ptr(gjt[b]), _lib.ptr(gsx[b]), _lib.ptr(gx[b]), V, Bn, Bn,
+                          0, 0)
+            if gy is not None:          # dy[v, j] = sum_i x[v, i] gJ[i, j] + gsy[j]
+                _lib.call(dev, 'nrt_conv1x1_softmax_f32', _lib.ptr(xf[b]), _lib.ptr(gj[b]), _lib.ptr(gsy[b]), _lib.ptr(gy[b]), V, Bn, Bn,
+                          0, 0)
         return gx, gy
 
 

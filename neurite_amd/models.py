@@ -93,11 +93,11 @@ _BY_DTYPE = {torch.float32: ('_f32', _p32), torch.bfloat16: ('_bf16', _pbf)}
 
 
 def _glue(stem, t):
-    """(entry point, its name, pointer check) of the glue kernel `stem` for the dtype of tensor `t`; outputs take t's dtype"""
+    """(entry point's name, pointer check) of the glue kernel `stem` for the dtype of tensor `t`; outputs take t's dtype"""
     if t.dtype not in _BY_DTYPE:
         _p32(t)                                   # raises: no kernel family takes this dtype
     suffix, p = _BY_DTYPE[t.dtype]
-    return getattr(_lib.lib(), stem + suffix), stem + suffix, p
+    return stem + suffix, p
 
 
 def _triple(v, ndims, what):
@@ -275,10 +275,8 @@ class _Conv(nn.Module):
             dev = self.kernel.device
             n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(self.ksize3), self.cin, self.cout)
             packed = torch.empty(int(n), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_pack_weights_f32(_p32(self.kernel.detach().contiguous()), _lib.ints(self.ksize3),
-                                                     self.cin, self.cout, _p32(packed), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
+            _lib.call(dev, 'nrt_conv3d_pack_weights_f32', _p32(self.kernel.detach().contiguous()), _lib.ints(self.ksize3), self.cin,
+                      self.cout, _p32(packed))
             return packed
         return self._pack('packed', self._kernel_key(), build)
 
@@ -290,10 +288,8 @@ class _Conv(nn.Module):
             dev = self.kernel.device
             n = lib.nrt_conv3d_up2_packed_weight_floats(int(c0), self.cin - int(c0), self.cout)
             packed = torch.empty(int(n), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_up2_pack_weights_f32(_p32(self.kernel.detach().contiguous()), int(c0), self.cin - int(c0),
-                                                         self.cout, _p32(packed), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_conv3d_up2_pack_weights_f32')
+            _lib.call(dev, 'nrt_conv3d_up2_pack_weights_f32', _p32(self.kernel.detach().contiguous()), int(c0), self.cin - int(c0),
+                      self.cout, _p32(packed))
             return packed
         return self._pack('up2', self._kernel_key(int(c0)), build)
 
@@ -328,31 +324,25 @@ class _Conv(nn.Module):
 
     def run_with_pool(self, x):
         """(act(conv(x)), MaxPooling3D(2) of it) from one kernel (nrt_conv3d_c1_pool_f32 / nrt_conv3d_pool_f32).  Inference only."""
-        lib = _lib.lib()
         dev = _lib.require_device(x, self.kernel)
         x = x.contiguous()
         B, S = x.shape[0], list(x.shape[1:4])
         out = torch.empty([B] + S + [self.cout], dtype=torch.float32, device=dev)
         pooled = torch.empty([B] + [v // 2 for v in S] + [self.cout], dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            if self.cin == 1:
-                rc = lib.nrt_conv3d_c1_pool_f32(_p32(x), _p32(self.kernel.detach().contiguous()), _p32(self.bias.detach()),
-                                                _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
-            else:
-                rc = lib.nrt_conv3d_pool_f32(_p32(x), self.cin, _p32(self._packed_weights()), _p32(self.bias.detach()),
-                                             _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_c1_pool_f32' if self.cin == 1 else 'nrt_conv3d_pool_f32')
+        if self.cin == 1:
+            _lib.call(dev, 'nrt_conv3d_c1_pool_f32', _p32(x), _p32(self.kernel.detach().contiguous()), _p32(self.bias.detach()),
+                      _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act)
+        else:
+            _lib.call(dev, 'nrt_conv3d_pool_f32', _p32(x), self.cin, _p32(self._packed_weights()), _p32(self.bias.detach()),
+                      _p32(out), _p32(pooled), B, _lib.ints(S), self.cout, self.act)
         return out, pooled
 
     def _packed_head(self, head_kernel, labels, dev):
         """the head's kernel in matrix-core fragment order, repacked when the parameter changes (version counter)"""
         def build():
-            lib = _lib.lib()
             src = head_kernel.detach().reshape(-1, labels).contiguous()
             packed = torch.empty(16 * labels, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nrt_conv3d_up2_head_pack_f32(_p32(src), labels, _p32(packed), _lib.stream_ptr(dev)),
-                           'nrt_conv3d_up2_head_pack_f32')
+            _lib.call(dev, 'nrt_conv3d_up2_head_pack_f32', _p32(src), labels, _p32(packed))
             return packed
         # keyed by the head's kernel, not this layer's: served in any mode (run_with_head is inference only)
         return self._pack('head', (head_kernel.data_ptr(), head_kernel._version, str(dev)), build, while_training=True)
@@ -360,7 +350,6 @@ class _Conv(nn.Module):
     def run_with_head(self, x, lo, head_kernel, head_bias):
         """softmax(act(this decoder convolution) @ head_kernel + head_bias) in one kernel (nrt_conv3d_up2_head_f32); the caller has
         checked ConvNet._head_foldable.  Inference only."""
-        lib = _lib.lib()
         dev = _lib.require_device(x, lo, self.kernel)
         x, lo = x.contiguous(), lo.contiguous()
         c0, c1 = x.shape[-1], lo.shape[-1]
@@ -368,11 +357,8 @@ class _Conv(nn.Module):
         labels = head_kernel.shape[-1]
         out = torch.empty([B] + S + [labels], dtype=torch.float32, device=dev)
         hw = self._packed_head(head_kernel, labels, dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_up2_head_f32(_p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)),
-                                             _p32(self.bias.detach()), _p32(hw), _p32(head_bias.detach()), labels,
-                                             _p32(out), B, _lib.ints(S), self.cout, self.act, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_up2_head_f32')
+        _lib.call(dev, 'nrt_conv3d_up2_head_f32', _p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)), _p32(self.bias.detach()),
+                  _p32(hw), _p32(head_bias.detach()), labels, _p32(out), B, _lib.ints(S), self.cout, self.act)
         return out
 
     def _packed_weights_bf16(self):
@@ -383,10 +369,8 @@ class _Conv(nn.Module):
             dev = self.kernel.device
             n = lib.nrt_conv3d_packed_weight_bytes_bf16(_lib.ints(self.ksize3), self.cin, self.cout)
             packed = torch.empty(int(n) // 2, dtype=torch.bfloat16, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_pack_weights_bf16(_pbf(self.kernel.detach().contiguous()), _lib.DT_BF16, _lib.ints(self.ksize3),
-                                                      self.cin, self.cout, _lib.ptr(packed), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_conv3d_pack_weights_bf16')
+            _lib.call(dev, 'nrt_conv3d_pack_weights_bf16', _pbf(self.kernel.detach().contiguous()), _lib.DT_BF16, _lib.ints(self.ksize3),
+                      self.cin, self.cout, _lib.ptr(packed))
             return packed
         return self._pack('bf16', self._kernel_key(self.kernel.dtype), build)
 
@@ -410,17 +394,13 @@ class _Conv(nn.Module):
     def run_bf16(self, x, lo=None, up=None):
         """act(conv(concat(x, upsample(lo)))) on bf16 tensors (nrt_conv3d_bf16): exact products, float32 accumulation, bias and
         ELU / ReLU in float32, one rounding; any other activation as a pass of its own, a softmax activation as its own kernel"""
-        lib = _lib.lib()
         dev = _lib.require_device(x, lo, self.kernel)
         x, lo, c0, c1, B, S, O = self._geometry(x, lo, up)
         out = torch.empty([B] + O + [self.cout], dtype=torch.bfloat16, device=dev)
         bias = self.bias.detach().to(torch.float32).contiguous()          # exact: every bf16 value is a float32
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_bf16(_pbf(x), c0, _pbf(lo), c1, _lib.ints(up) if lo is not None else None,
-                                     _lib.ptr(self._packed_weights_bf16()), _lib.ptr(bias), _lib.ptr(out), B, _lib.ints(S),
-                                     _lib.ints(self.ksize3), self.cout, self.dilation, int(self.padding == 'same'),
-                                     self.act if self.act <= _ACT_LAST_FUSED else 0, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_bf16')
+        _lib.call(dev, 'nrt_conv3d_bf16', _pbf(x), c0, _pbf(lo), c1, _lib.ints(up) if lo is not None else None,
+                  _lib.ptr(self._packed_weights_bf16()), _lib.ptr(bias), _lib.ptr(out), B, _lib.ints(S), _lib.ints(self.ksize3), self.cout,
+                  self.dilation, int(self.padding == 'same'), self.act if self.act <= _ACT_LAST_FUSED else 0)
         if self.act > _ACT_LAST_FUSED:
             out = _elementwise(out, act=self.act)
         if self.post_softmax:
@@ -428,7 +408,6 @@ class _Conv(nn.Module):
         return out
 
     def _run(self, x, lo=None, up=None, variant=0):
-        lib = _lib.lib()
         dev = _lib.require_device(x, lo, self.kernel)
         if x.dtype != torch.float32:
             raise NotImplementedError('the HIP conv path is float32')
@@ -437,31 +416,24 @@ class _Conv(nn.Module):
         w = self.kernel.detach().contiguous()
         # decoder form (UpSampling3D(2) + concatenate + 3x3x3 SAME): the up-sampled half runs as 8 folded taps on the
         # low-resolution grid (variant 0 = auto, 4 = required; 2 keeps the plain implicit GEMM over all 27 taps)
+        # these are all the reasons nrt_conv3d_up2_f32 has to decline (NRT_ERR_UNSUPPORTED): anything outside them takes the plain GEMM
         folded = (variant in (0, 4) and lo is not None and tuple(up) == (2, 2, 2) and self.ksize3 == (3, 3, 3)
                   and self.dilation == 1 and self.padding == 'same'
-                  and lib.nrt_conv3d_up2_supported(c0, c1, self.cout, _lib.ints(S)) == 1
+                  and _lib.lib().nrt_conv3d_up2_supported(c0, c1, self.cout, _lib.ints(S)) == 1
                   # the folded kernel forms 32-bit output offsets over the whole batch (conv_up2.h launch_up2); the shape query
                   # does not see the batch, and nrt_conv3d_f32 has no such limit
                   and B * S[0] * S[1] * S[2] * self.cout < (1 << 30))
         if variant == 4 and not folded:
             raise NotImplementedError('%s: shapes outside the folded decoder kernel' % self.layer_name)
         if folded:
-            with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_up2_f32(_p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)),
-                                            _p32(self.bias.detach()), _p32(out), B, _lib.ints(S), self.cout,
-                                            self.act if self.act <= _ACT_LAST_FUSED else 0, _lib.stream_ptr(dev))
-            if not (rc == _lib.NRT_ERR_UNSUPPORTED and variant == 0):       # auto: anything the folded form declines takes the plain GEMM
-                _lib.check(rc, 'nrt_conv3d_up2_f32')
-                if self.act > _ACT_LAST_FUSED:
-                    out = _elementwise(out, act=self.act)
-                return out
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_f32(_p32(x), c0, _p32(lo), c1, _lib.ints(up) if lo is not None else None,
-                                    _p32(w), _p32(self._packed_weights()), _p32(self.bias.detach()),
-                                    _p32(out), B, _lib.ints(S), _lib.ints(self.ksize3), self.cout, self.dilation,
-                                    int(self.padding == 'same'), self.act if self.act <= _ACT_LAST_FUSED else 0, int(variant),
-                                    _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_f32')
+            _lib.call(dev, 'nrt_conv3d_up2_f32', _p32(x), c0, _p32(lo), c1, _p32(self._packed_weights_up2(c0)), _p32(self.bias.detach()),
+                      _p32(out), B, _lib.ints(S), self.cout, self.act if self.act <= _ACT_LAST_FUSED else 0)
+            if self.act > _ACT_LAST_FUSED:
+                out = _elementwise(out, act=self.act)
+            return out
+        _lib.call(dev, 'nrt_conv3d_f32', _p32(x), c0, _p32(lo), c1, _lib.ints(up) if lo is not None else None, _p32(w),
+                  _p32(self._packed_weights()), _p32(self.bias.detach()), _p32(out), B, _lib.ints(S), _lib.ints(self.ksize3), self.cout,
+                  self.dilation, int(self.padding == 'same'), self.act if self.act <= _ACT_LAST_FUSED else 0, int(variant))
         if self.act > _ACT_LAST_FUSED:            # activations beyond elu / relu: an element-wise pass over the layer output
             out = _elementwise(out, act=self.act)
         return out
@@ -506,18 +478,14 @@ def _dense_workspace(dev, batch, cin, cout, variant):
 
 
 def _dense_run(x, kernel, bias, act, variant):
-    lib = _lib.lib()
     dev = _lib.require_device(x, kernel, bias)
     x = x.contiguous()
     B, cin, cout = x.shape[0], kernel.shape[0], kernel.shape[1]
     if x.dim() != 2 or x.shape[1] != cin:
         raise ValueError('Dense: input of shape %s for a kernel %s' % (tuple(x.shape), tuple(kernel.shape)))
     y = torch.empty((B, cout), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, n = _dense_workspace(dev, B, cin, cout, variant)
-        rc = lib.nrt_dense_f32(_p32(x), _p32(kernel), _p32(bias), _p32(y), B, cin, cout, int(act), int(variant), _lib.ptr(ws), n,
-                               _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_dense_f32')
+    ws, n = _dense_workspace(dev, B, cin, cout, variant)
+    _lib.call(dev, 'nrt_dense_f32', _p32(x), _p32(kernel), _p32(bias), _p32(y), B, cin, cout, int(act), int(variant), _lib.ptr(ws), n)
     return y
 
 
@@ -536,7 +504,6 @@ class _DenseFn(torch.autograd.Function):
     def backward(ctx, g):
         x, kernel, y = ctx.saved_tensors
         act, variant = ctx.cfg
-        lib = _lib.lib()
         dev = g.device
         d = _act_bwd(g, y, act)
         x = x.contiguous()
@@ -545,11 +512,9 @@ class _DenseFn(torch.autograd.Function):
         gx = torch.empty_like(x) if need_x else None
         gw = torch.empty_like(kernel) if need_w else None
         gb = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
-        with torch.cuda.device(dev):
-            ws, n = _dense_workspace(dev, B, cin, cout, variant)
-            rc = lib.nrt_dense_bwd_f32(_p32(d), _p32(x), _p32(kernel), _p32(gx), _p32(gw), _p32(gb), B, cin, cout, int(variant),
-                                       _lib.ptr(ws), n, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_dense_bwd_f32')
+        ws, n = _dense_workspace(dev, B, cin, cout, variant)
+        _lib.call(dev, 'nrt_dense_bwd_f32', _p32(d), _p32(x), _p32(kernel), _p32(gx), _p32(gw), _p32(gb), B, cin, cout, int(variant),
+                  _lib.ptr(ws), n)
         return gx, gw, gb, None, None
 
 
@@ -582,13 +547,11 @@ def _elementwise(a, b=None, scale=None, shift=None, act=0, mul=False):
     if mul:
         act = int(act) | _ACT_MUL_B
     dev = _lib.require_device(a, b)
-    fn, what, p = _glue('nrt_add_act_affine', a)
+    name, p = _glue('nrt_add_act_affine', a)
     a = a.contiguous()
     b = None if b is None else b.contiguous()
     y = torch.empty_like(a)
-    with torch.cuda.device(dev):
-        rc = fn(p(a), p(b), _p32(scale), _p32(shift), p(y), a.numel(), a.shape[-1], int(act), _lib.stream_ptr(dev))
-    _lib.check(rc, what)
+    _lib.call(dev, name, p(a), p(b), _p32(scale), _p32(shift), p(y), a.numel(), a.shape[-1], int(act))
     return y
 
 
@@ -606,7 +569,6 @@ class _GlobalMaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, per_channel):
-        lib = _lib.lib()
         dev = _lib.require_device(x)
         x = x.contiguous()
         B = x.shape[0]
@@ -614,10 +576,8 @@ class _GlobalMaxFn(torch.autograd.Function):
         V = x.numel() // (B * C)
         y = torch.empty((B, C), dtype=torch.float32, device=dev)
         count = torch.empty((B, C), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            ws, n = _global_max_workspace(dev, B, V, C)
-            rc = lib.nrt_global_max_f32(_p32(x), B, V, C, _p32(y), _lib.ptr(count), _lib.ptr(ws), n, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_global_max_f32')
+        ws, n = _global_max_workspace(dev, B, V, C)
+        _lib.call(dev, 'nrt_global_max_f32', _p32(x), B, V, C, _p32(y), _lib.ptr(count), _lib.ptr(ws), n)
         ctx.save_for_backward(x, y, count)
         ctx.dims = (B, V, C)
         ctx.mark_non_differentiable(count)
@@ -627,15 +587,11 @@ class _GlobalMaxFn(torch.autograd.Function):
     def backward(ctx, g, _gcount):
         x, y, count = ctx.saved_tensors
         B, V, C = ctx.dims
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         gx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            ws, n = _global_max_workspace(dev, B, V, C)
-            rc = lib.nrt_global_max_bwd_f32(_p32(x), _p32(y), _lib.ptr(count), _p32(g), B, V, C, _p32(gx), _lib.ptr(ws), n,
-                                            _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_global_max_bwd_f32')
+        ws, n = _global_max_workspace(dev, B, V, C)
+        _lib.call(dev, 'nrt_global_max_bwd_f32', _p32(x), _p32(y), _lib.ptr(count), _p32(g), B, V, C, _p32(gx), _lib.ptr(ws), n)
         return gx, None
 
 
@@ -677,33 +633,27 @@ def _scale_values(x, factor):
 
 def _maxnorm(w, max_value, eps=1e-7):
     """Keras MaxNorm(max_value, axis=0) in place on a contiguous float32 weight tensor"""
-    lib = _lib.lib()
     dev = _lib.require_device(w)
     if not w.is_contiguous():
         raise ValueError('a constrained weight must be contiguous')
-    with torch.cuda.device(dev):
-        rc = lib.nrt_maxnorm_f32(_p32(w), int(w.shape[0]), w.numel() // int(w.shape[0]), float(max_value), float(eps),
-                                 _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_maxnorm_f32')
+    _lib.call(dev, 'nrt_maxnorm_f32', _p32(w), int(w.shape[0]), w.numel() // int(w.shape[0]), float(max_value), float(eps))
 
 
 def _maxpool(x, pool3, padding):
     dev = _lib.require_device(x)
-    fn, what, p = _glue('nrt_maxpool3d', x)
+    name, p = _glue('nrt_maxpool3d', x)
     x = x.contiguous()
     B, S, C = x.shape[0], list(x.shape[1:4]), x.shape[-1]
     same = padding == 'same'
     O = [(S[d] + pool3[d] - 1) // pool3[d] if same else S[d] // pool3[d] for d in range(3)]
     y = torch.empty([B] + O + [C], dtype=x.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = fn(p(x), p(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same), _lib.stream_ptr(dev))
-    _lib.check(rc, what)
+    _lib.call(dev, name, p(x), p(y), B, _lib.ints(S), C, _lib.ints(pool3), int(same))
     return y
 
 
 def _upsample_concat(skip, lo, up3):
     dev = _lib.require_device(skip, lo)
-    fn, what, p = _glue('nrt_upsample_concat', lo)
+    name, p = _glue('nrt_upsample_concat', lo)
     lo = lo.contiguous()
     B, S1, c1 = lo.shape[0], list(lo.shape[1:4]), lo.shape[-1]
     S = [S1[d] * up3[d] for d in range(3)]
@@ -713,16 +663,14 @@ def _upsample_concat(skip, lo, up3):
         if list(skip.shape[1:4]) != S:
             raise ValueError('concatenate: shapes %s and %s do not match' % (list(skip.shape[1:4]), S))
     y = torch.empty([B] + S + [c0 + c1], dtype=lo.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = fn(p(skip), c0, p(lo), c1, p(y), B, _lib.ints(S), _lib.ints(up3), _lib.stream_ptr(dev))
-    _lib.check(rc, what)
+    _lib.call(dev, name, p(skip), c0, p(lo), c1, p(y), B, _lib.ints(S), _lib.ints(up3))
     return y
 
 
 def _conv1x1_softmax(x, kernel, bias, softmax, act=0):
     """a 1x1x1 convolution (the likelihood layer, cout <= 64) with the channel softmax optionally fused: float32 logits"""
     dev = _lib.require_device(x, kernel)
-    fn, what, p = _glue('nrt_conv1x1_softmax', x)
+    name, p = _glue('nrt_conv1x1_softmax', x)
     x = x.contiguous()
     cin, cout = kernel.shape[-2], kernel.shape[-1]
     y = torch.empty(list(x.shape[:-1]) + [cout], dtype=x.dtype, device=dev)
@@ -731,20 +679,16 @@ def _conv1x1_softmax(x, kernel, bias, softmax, act=0):
     fused = int(act) if int(act) <= _ACT_LAST_FUSED else 0       # elu / relu ride in the epilogue, the others as a pass of their own
     if softmax and fused != int(act):
         raise NotImplementedError('a 1x1x1 convolution with a non-fused activation followed by the channel softmax')
-    with torch.cuda.device(dev):
-        rc = fn(p(x), p(w), _p32(b), p(y), x.numel() // cin, cin, cout, int(softmax), fused, _lib.stream_ptr(dev))
-    _lib.check(rc, what)
+    _lib.call(dev, name, p(x), p(w), _p32(b), p(y), x.numel() // cin, cin, cout, int(softmax), fused)
     return y if fused == int(act) else _elementwise(y, act=int(act))
 
 
 def _softmax(x):
     dev = _lib.require_device(x)
-    fn, what, p = _glue('nrt_softmax_lastdim', x)
+    name, p = _glue('nrt_softmax_lastdim', x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = fn(p(x), p(y), x.numel() // x.shape[-1], x.shape[-1], _lib.stream_ptr(dev))
-    _lib.check(rc, what)
+    _lib.call(dev, name, p(x), p(y), x.numel() // x.shape[-1], x.shape[-1])
     return y
 
 
@@ -755,27 +699,20 @@ def _softmax(x):
 def _act_bwd(g, y, act):
     if act == 0:
         return g.contiguous()
-    lib = _lib.lib()
     dev = g.device
     g = g.contiguous()
     d = torch.empty_like(g)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_act_bwd_f32(_p32(g), _p32(y), int(act), _p32(d), g.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_act_bwd_f32')
+    _lib.call(dev, 'nrt_act_bwd_f32', _p32(g), _p32(y), int(act), _p32(d), g.numel())
     return d
 
 
 def _upsample_sum(g, c_off, c, lo_shape, up3):
     """grad of nearest up-sampling: channels [c_off, c_off + c) of g [B, S, Cg] summed over up^3 blocks -> [B, S/up, c]."""
-    lib = _lib.lib()
     dev = g.device
     g = g.contiguous()
     B = g.shape[0]
     d = torch.empty([B] + list(lo_shape) + [c], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_upsample_sum_f32(_p32(g), g.shape[-1], int(c_off), _p32(d), int(c), B, _lib.ints(lo_shape),
-                                      _lib.ints(up3), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_upsample_sum_f32')
+    _lib.call(dev, 'nrt_upsample_sum_f32', _p32(g), g.shape[-1], int(c_off), _p32(d), int(c), B, _lib.ints(lo_shape), _lib.ints(up3))
     return d
 
 
@@ -798,22 +735,15 @@ def _conv_dgrad(dpre, wpart, ksize3, dilation, variant=0):
         # 1x1x1 (the likelihood layer): a per-voxel matrix product on the streaming kernel, not on the halo-tile convolution
         dpre = dpre.contiguous()
         out = torch.empty(list(dpre.shape[:-1]) + [cpart], dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv1x1_softmax_f32(_p32(dpre), _p32(wt), None, _p32(out), dpre.numel() // cout, cout, cpart, 0, 0,
-                                             _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv1x1_softmax_f32 (dgrad)')
+        _lib.call(dev, 'nrt_conv1x1_softmax_f32', _p32(dpre), _p32(wt), None, _p32(out), dpre.numel() // cout, cout, cpart, 0, 0)
         return out
     n = lib.nrt_conv3d_packed_weight_floats(_lib.ints(ksize3), cout, cpart)
     packed = torch.empty(int(n), dtype=torch.float32, device=dev)
     B, S = dpre.shape[0], list(dpre.shape[1:4])
     out = torch.empty([B] + S + [cpart], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_pack_weights_f32(_p32(wt), _lib.ints(ksize3), cout, cpart, _p32(packed), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-        rc = lib.nrt_conv3d_pad_f32(_p32(dpre), cout, None, 0, None, _p32(wt), _p32(packed), None, _p32(out), B,
-                                    _lib.ints(S), _lib.ints(ksize3), cpart, int(dilation),
-                                    _lib.ints(_dgrad_pad_before(ksize3, dilation)), 0, int(variant), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv3d_pad_f32 (dgrad)')
+    _lib.call(dev, 'nrt_conv3d_pack_weights_f32', _p32(wt), _lib.ints(ksize3), cout, cpart, _p32(packed))
+    _lib.call(dev, 'nrt_conv3d_pad_f32', _p32(dpre), cout, None, 0, None, _p32(wt), _p32(packed), None, _p32(out), B, _lib.ints(S),
+              _lib.ints(ksize3), cpart, int(dilation), _lib.ints(_dgrad_pad_before(ksize3, dilation)), 0, int(variant))
     return out
 
 
@@ -861,14 +791,11 @@ def _fold_backward_ok(mod, x, lo, up):
 
 
 def _space_to_depth2(dpre):
-    lib = _lib.lib()
     dev = dpre.device
     dpre = dpre.contiguous()
     B, S, C = dpre.shape[0], list(dpre.shape[1:4]), dpre.shape[-1]
     y = torch.empty([B] + [s // 2 for s in S] + [8 * C], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_space_to_depth2_f32(_p32(dpre), _p32(y), B, _lib.ints(S), C, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_space_to_depth2_f32')
+    _lib.call(dev, 'nrt_space_to_depth2_f32', _p32(dpre), _p32(y), B, _lib.ints(S), C)
     return y
 
 
@@ -884,24 +811,17 @@ def _conv_dgrad_lo_folded(s2d, k_lo):
     packed = torch.empty(int(n), dtype=torch.float32, device=dev)
     B, S1 = s2d.shape[0], list(s2d.shape[1:4])
     out = torch.empty([B] + S1 + [c1], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_pack_weights_f32(_p32(wf), _lib.ints(k3), 8 * cout, c1, _p32(packed), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_pack_weights_f32')
-        rc = lib.nrt_conv3d_s2d_taps_f32(_p32(s2d), cout, _p32(packed), _p32(out), B, _lib.ints(S1), c1, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv3d_s2d_taps_f32')
+    _lib.call(dev, 'nrt_conv3d_pack_weights_f32', _p32(wf), _lib.ints(k3), 8 * cout, c1, _p32(packed))
+    _lib.call(dev, 'nrt_conv3d_s2d_taps_f32', _p32(s2d), cout, _p32(packed), _p32(out), B, _lib.ints(S1), c1)
     return out
 
 
 def _conv_wgrad_lo_folded(lo, s2d, cout):
-    lib = _lib.lib()
     dev = lo.device
     lo = lo.contiguous()
     c1 = lo.shape[-1]
     dwf = torch.zeros(8, 8, c1, cout, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_conv3d_wgrad_s2d_f32(_p32(lo), _p32(s2d), _p32(dwf), lo.shape[0], _lib.ints(list(lo.shape[1:4])), c1,
-                                          cout, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_conv3d_wgrad_s2d_f32')
+    _lib.call(dev, 'nrt_conv3d_wgrad_s2d_f32', _p32(lo), _p32(s2d), _p32(dwf), lo.shape[0], _lib.ints(list(lo.shape[1:4])), c1, cout)
     return _unfold_wgrad(dwf)
 
 
@@ -924,7 +844,6 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, g):
         x, lo, kernel, out = ctx.saved_tensors
         mod, up = ctx.mod, ctx.up
-        lib = _lib.lib()
         dev = g.device
         dpre = _act_bwd(g, out, mod.act)
         if mod.padding != 'same':
@@ -936,10 +855,8 @@ class _ConvFn(torch.autograd.Function):
             pb = [((mod.ksize3[d] - 1) * mod.dilation) // 2 for d in range(3)]
             padded = torch.empty([dpre.shape[0]] + S + [dpre.shape[-1]], dtype=dpre.dtype, device=dev)
             dpre = dpre.contiguous()
-            with torch.cuda.device(dev):
-                rc = lib.nrt_pad3d(_p32(dpre), _p32(padded), dpre.shape[0], _lib.ints(list(dpre.shape[1:4])), _lib.ints(pb),
-                                   _lib.ints(S), dpre.shape[-1] * 4, 0, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_pad3d')
+            _lib.call(dev, 'nrt_pad3d', _p32(dpre), _p32(padded), dpre.shape[0], _lib.ints(list(dpre.shape[1:4])), _lib.ints(pb),
+                      _lib.ints(S), dpre.shape[-1] * 4, 0)
             dpre = padded
         need_x, need_lo, need_w, need_b = ctx.needs_input_grad[:4]
         dx = dlo = dw = db = None
@@ -958,11 +875,8 @@ class _ConvFn(torch.autograd.Function):
                 dws = torch.zeros(3, 3, 3, c0, mod.cout, dtype=torch.float32, device=dev)
                 db = torch.zeros(mod.cout, dtype=torch.float32, device=dev)
                 xs = x.contiguous()
-                with torch.cuda.device(dev):
-                    rc = lib.nrt_conv3d_wgrad_f32(_p32(xs), _p32(dpre), _p32(dws), _p32(db), xs.shape[0],
-                                                  _lib.ints(list(xs.shape[1:4])), c0, mod.cout, _lib.ints(mod.ksize3), 1,
-                                                  _lib.stream_ptr(dev))
-                _lib.check(rc, 'nrt_conv3d_wgrad_f32')
+                _lib.call(dev, 'nrt_conv3d_wgrad_f32', _p32(xs), _p32(dpre), _p32(dws), _p32(db), xs.shape[0],
+                          _lib.ints(list(xs.shape[1:4])), c0, mod.cout, _lib.ints(mod.ksize3), 1)
                 dw[..., :c0, :] = dws
                 dw[..., c0:, :] = _conv_wgrad_lo_folded(lo, s2d, mod.cout)
             return dx, dlo, dw if need_w else None, db if need_b else None, None, None, None, None
@@ -974,11 +888,9 @@ class _ConvFn(torch.autograd.Function):
             if lo_c is not None and c0 % 4:
                 xs, lo_c = _upsample_concat(xs, lo_c, up), None          # a channel quad would straddle the two sources
             B, S = xs.shape[0], list(xs.shape[1:4])
-            with torch.cuda.device(dev):
-                rc = lib.nrt_conv3d_wgrad2_f32(_p32(xs), xs.shape[-1], _p32(lo_c), 0 if lo_c is None else lo_c.shape[-1],
-                                               _lib.ints(up) if lo_c is not None else None, _p32(dpre), _p32(dw), _p32(db),
-                                               B, _lib.ints(S), mod.cout, _lib.ints(mod.ksize3), mod.dilation, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_conv3d_wgrad2_f32')
+            _lib.call(dev, 'nrt_conv3d_wgrad2_f32', _p32(xs), xs.shape[-1], _p32(lo_c), 0 if lo_c is None else lo_c.shape[-1],
+                      _lib.ints(up) if lo_c is not None else None, _p32(dpre), _p32(dw), _p32(db), B, _lib.ints(S), mod.cout,
+                      _lib.ints(mod.ksize3), mod.dilation)
         k5 = kernel.detach()
         if lo is not None and need_x and need_lo and mod.cin <= 64:
             # one dgrad for both sources of the fused loader (dpre is staged once, three N-tiles per A fragment)
@@ -1007,15 +919,12 @@ class _MaxPoolFn(torch.autograd.Function):
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
         pool3, padding = ctx.cfg
-        lib = _lib.lib()
         dev = g.device
         x = x.contiguous()
         g = g.contiguous()
         dx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_maxpool3d_bwd_f32(_p32(x), _p32(g), _p32(dx), x.shape[0], _lib.ints(list(x.shape[1:4])),
-                                           x.shape[-1], _lib.ints(pool3), int(padding == 'same'), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_maxpool3d_bwd_f32')
+        _lib.call(dev, 'nrt_maxpool3d_bwd_f32', _p32(x), _p32(g), _p32(dx), x.shape[0], _lib.ints(list(x.shape[1:4])), x.shape[-1],
+                  _lib.ints(pool3), int(padding == 'same'))
         return dx, None, None
 
 
@@ -1039,18 +948,14 @@ class _MergeFn(torch.autograd.Function):
 
 def _head_grads(x, kernel, mod, dz, needs):
     """(dx, dw, db) of the likelihood conv from dz = d loss / d logits; needs = which of the three are wanted"""
-    lib = _lib.lib()
     dev = dz.device
     dx = dw = db = None
     if needs[1] or needs[2]:
         xin = x.contiguous()
         dw = torch.zeros_like(kernel, dtype=torch.float32)
         db = torch.zeros(mod.cout, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv3d_wgrad_f32(_p32(xin), _p32(dz), _p32(dw), _p32(db), xin.shape[0],
-                                          _lib.ints(list(xin.shape[1:4])), mod.cin, mod.cout, _lib.ints(mod.ksize3), 1,
-                                          _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv3d_wgrad_f32')
+        _lib.call(dev, 'nrt_conv3d_wgrad_f32', _p32(xin), _p32(dz), _p32(dw), _p32(db), xin.shape[0], _lib.ints(list(xin.shape[1:4])),
+                  mod.cin, mod.cout, _lib.ints(mod.ksize3), 1)
     if needs[0]:
         dx = _conv_dgrad(dz, kernel.detach(), mod.ksize3, 1)
     return dx, dw, db
@@ -1107,14 +1012,10 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, kernel, y = ctx.saved_tensors
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         dz = torch.empty_like(y)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_softmax_bwd_f32(_p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1],
-                                         _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_softmax_bwd_f32')
+        _lib.call(dev, 'nrt_softmax_bwd_f32', _p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1])
         return _head_grads(x, kernel, ctx.mod, dz, ctx.needs_input_grad) + (None,)
 
 
@@ -1135,14 +1036,10 @@ class _ChannelScaleFn(torch.autograd.Function):
     def _apply(x, scale):
         x = x.contiguous()
         y = torch.empty_like(x)
-        lib = _lib.lib()
         dev = x.device
         zero = torch.zeros(x.shape[-1], dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            for b in range(x.shape[0]):
-                rc = lib.nrt_add_act_affine_f32(_p32(x[b]), None, _p32(scale[b]), _p32(zero), _p32(y[b]), x[b].numel(),
-                                                x.shape[-1], 0, _lib.stream_ptr(dev))
-                _lib.check(rc, 'nrt_add_act_affine_f32')
+        for b in range(x.shape[0]):
+            _lib.call(dev, 'nrt_add_act_affine_f32', _p32(x[b]), None, _p32(scale[b]), _p32(zero), _p32(y[b]), x[b].numel(), x.shape[-1], 0)
         return y
 
     @staticmethod
@@ -1195,13 +1092,10 @@ class _MulFn(torch.autograd.Function):
 
 
 def _channel_sums(a, b=None):
-    lib = _lib.lib()
     dev = a.device
     C = a.shape[-1]
     out = torch.zeros(C, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_channel_sums_f32(_p32(a), _p32(b), a.numel() // C, C, _p32(out), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_channel_sums_f32')
+    _lib.call(dev, 'nrt_channel_sums_f32', _p32(a), _p32(b), a.numel() // C, C, _p32(out))
     return out
 
 
@@ -1228,7 +1122,6 @@ class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, gamma, mean, inv = ctx.saved_tensors
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         C = x.shape[-1]
@@ -1245,10 +1138,7 @@ class _BatchNormFn(torch.autograd.Function):
             B = (-scale * inv * m2).contiguous()
             C0 = (-scale * m1 + scale * inv * m2 * mean).contiguous()
             dx = torch.empty_like(x)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_channel_axpby_f32(_p32(g), _p32(x), _p32(A), _p32(B), _p32(C0), _p32(dx),
-                                               x.numel(), C, _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_channel_axpby_f32')
+            _lib.call(dev, 'nrt_channel_axpby_f32', _p32(g), _p32(x), _p32(A), _p32(B), _p32(C0), _p32(dx), x.numel(), C)
         return dx, dgamma, dbeta, None
 
 
@@ -1263,14 +1153,10 @@ class _SoftmaxFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (y,) = ctx.saved_tensors
-        lib = _lib.lib()
         dev = g.device
         g = g.contiguous()
         dz = torch.empty_like(y)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_softmax_bwd_f32(_p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1],
-                                         _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_softmax_bwd_f32')
+        _lib.call(dev, 'nrt_softmax_bwd_f32', _p32(y), _p32(g), _p32(dz), y.numel() // y.shape[-1], y.shape[-1])
         return dz
 
 

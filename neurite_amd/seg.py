@@ -65,11 +65,9 @@ def _argmax(pred, labels=None, of=None, prob=None):
         if C == 0:
             raise ValueError('attempt to get argmax of an empty sequence')
         return
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nrt_seg_argmax(_lib.ptr(pred), _PRED_DTYPES[pred.dtype], n, C, _lib.ptr(labels),
-                                       int(labels is not None and labels.dtype == torch.int64), _lib.ptr(of),
-                                       int(of is not None and of.dtype == torch.int64), _lib.ptr(prob), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_seg_argmax')
+    _lib.call(dev, 'nrt_seg_argmax', _lib.ptr(pred), _PRED_DTYPES[pred.dtype], n, C, _lib.ptr(labels),
+              int(labels is not None and labels.dtype == torch.int64), _lib.ptr(of), int(of is not None and of.dtype == torch.int64),
+              _lib.ptr(prob))
 
 
 def pred_to_label(*y):
@@ -150,10 +148,8 @@ def recode(seg, mapping, max_label=None):
     if seg.numel() == 0:
         return out
     table = torch.from_numpy(lookup).to(dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nrt_seg_recode(_lib.ptr(seg), int(seg.dtype == torch.int64), seg.numel(), _lib.ptr(table), table.numel(),
-                                       _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_seg_recode')
+    _lib.call(dev, 'nrt_seg_recode', _lib.ptr(seg), int(seg.dtype == torch.int64), seg.numel(), _lib.ptr(table), table.numel(),
+              _lib.ptr(out))
     return out
 
 
@@ -197,10 +193,8 @@ def extract_patches(vol, patch_size, patch_stride, grid_size=None, start=0, coun
     if out.numel() == 0:
         return out
     dev = vol.device
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nrt_patch_extract(_lib.ptr(vol), _PRED_DTYPES[vol.dtype], ndims, _lib.ints(shape), C, _lib.ints(patch),
-                                          _lib.ints(stride), _lib.ints(grid), start, count, _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_patch_extract')
+    _lib.call(dev, 'nrt_patch_extract', _lib.ptr(vol), _PRED_DTYPES[vol.dtype], ndims, _lib.ints(shape), C, _lib.ints(patch),
+              _lib.ints(stride), _lib.ints(grid), start, count, _lib.ptr(out))
     return out
 
 
@@ -254,10 +248,8 @@ def quilt(patches, patch_size, grid_size, patch_stride, nan_func=np.nanmean):
     dev = patches.device
     out = torch.empty(shape + ((C,) if with_channels else ()), dtype=torch.float32, device=dev)
     code = _lib.DT_F32 if patches.dtype == torch.float32 else _lib.DT_I32
-    with torch.cuda.device(dev):
-        rc = _lib.lib().nrt_patch_quilt(_lib.ptr(patches), code, ndims, _lib.ints(patch), _lib.ints(stride), _lib.ints(grid), C, reduce,
-                                        _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_patch_quilt')
+    _lib.call(dev, 'nrt_patch_quilt', _lib.ptr(patches), code, ndims, _lib.ints(patch), _lib.ints(stride), _lib.ints(grid), C, reduce,
+              _lib.ptr(out))
     return out
 
 

@@ -47,23 +47,19 @@ class SynthModel(nn.Module):
 
     def forward(self, labels):
         c = self.cfg
-        lib = _lib.lib()
         dev = _lib.require_device(labels)
         num_dim = c['num_dim']
         if labels.dim() != num_dim + 2 or labels.shape[-1] != 1 or tuple(labels.shape[1:-1]) != tuple(c['in_shape']):
             raise ValueError('labels_to_image expects label maps of shape [B, %s, 1], got %s'
                              % (', '.join(str(s) for s in c['in_shape']), tuple(labels.shape)))
         B = labels.shape[0]
-        st = _lib.stream_ptr(dev)
         draws = {}
         # ---- labels -> dense indices [0, N) (:778-784) -----------------------------------------------------------
         lab = labels if labels.dtype == torch.int32 else labels.to(torch.int32)            # tf.cast(labels, int32) (:773-774)
         lab = lab.contiguous()
         in_lut = torch.from_numpy(c['in_lut']).to(dev)
         idx = torch.empty(lab.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_relabel_i32(_lib.ptr(lab), _lib.ptr(in_lut), in_lut.numel(), _lib.ptr(idx), lab.numel(), st)
-        _lib.check(rc, 'nrt_synth_relabel_i32')
+        _lib.call(dev, 'nrt_synth_relabel_i32', _lib.ptr(lab), _lib.ptr(in_lut), in_lut.numel(), _lib.ptr(idx), lab.numel())
         vel_field = def_field = None
         # ---- random diffeomorphic warp of the label map (:786-806) ------------------------------------------------
         if c['warp_std'] > 0:
@@ -95,10 +91,8 @@ class SynthModel(nn.Module):
         draws.update(mean=mean, std=std, noise=noise, bg_zero=bgz, labels_warped=idx)
         image = torch.empty((B,) + S + (C,), dtype=torch.float32, device=dev)
         idx = idx.contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_intensity_f32(_lib.ptr(idx), _lib.ptr(noise), _lib.ptr(mean.contiguous()), _lib.ptr(std.contiguous()),
-                                             _lib.ptr(bgz), _lib.ptr(image), B, V, C, L, st)
-        _lib.check(rc, 'nrt_synth_intensity_f32')
+        _lib.call(dev, 'nrt_synth_intensity_f32', _lib.ptr(idx), _lib.ptr(noise), _lib.ptr(mean.contiguous()), _lib.ptr(std.contiguous()),
+                  _lib.ptr(bgz), _lib.ptr(image), B, V, C, L)
         # ---- blur (:851-857) ----------------------------------------------------------------------------------------
         if c['blur_std'] > 0:
             kernels = utils.gaussian_kernel([c['blur_std']] * num_dim, separate=True, random=c['blur_modulate'],
@@ -119,9 +113,7 @@ class SynthModel(nn.Module):
                 raise ValueError('Incompatible shapes: image %s and bias field %s' % (S, tuple(bias.shape[1:-1])))
             draws['bias_field'] = bias
         out = torch.empty_like(image)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_bias_clip_f32(_lib.ptr(image), _lib.ptr(bias), _lib.ptr(out), B * V, C, 0.0, 255.0, st)
-        _lib.check(rc, 'nrt_synth_bias_clip_f32')
+        _lib.call(dev, 'nrt_synth_bias_clip_f32', _lib.ptr(image), _lib.ptr(bias), _lib.ptr(out), B * V, C, 0.0, 255.0)
         image = out
         # ---- normalisation, gamma, offset (:875-888) ---------------------------------------------------------------
         if c['normalize']:
@@ -134,22 +126,17 @@ class SynthModel(nn.Module):
         draws.update(gamma=gamma, dc_offset=dc)
         if gamma is not None or dc is not None:
             out = torch.empty_like(image)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_gamma_dc_f32(_lib.ptr(image), _lib.ptr(gamma), _lib.ptr(dc), _lib.ptr(out), B, V, C, st)
-            _lib.check(rc, 'nrt_synth_gamma_dc_f32')
+            _lib.call(dev, 'nrt_synth_gamma_dc_f32', _lib.ptr(image), _lib.ptr(gamma), _lib.ptr(dc), _lib.ptr(out), B, V, C)
             image = out
         # ---- output labels (:890-918) ------------------------------------------------------------------------------
         out_lut = torch.from_numpy(c['out_lut']).to(dev)
         if c['one_hot']:
             depth = c['depth']
             lab_out = torch.empty((B,) + S + (depth,), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_labels_out(_lib.ptr(idx), _lib.ptr(out_lut), out_lut.numel(), depth, _lib.ptr(lab_out), None, B * V, st)
+            _lib.call(dev, 'nrt_synth_labels_out', _lib.ptr(idx), _lib.ptr(out_lut), out_lut.numel(), depth, _lib.ptr(lab_out), None, B * V)
         else:
             lab_out = torch.empty((B,) + S + (1,), dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_labels_out(_lib.ptr(idx), _lib.ptr(out_lut), out_lut.numel(), 1, None, _lib.ptr(lab_out), B * V, st)
-        _lib.check(rc, 'nrt_synth_labels_out')
+            _lib.call(dev, 'nrt_synth_labels_out', _lib.ptr(idx), _lib.ptr(out_lut), out_lut.numel(), 1, None, _lib.ptr(lab_out), B * V)
         self.last_draws = draws
         outputs = [image, lab_out]
         if c['return_vel']:
@@ -290,14 +277,12 @@ class SynthModelNew(nn.Module):
         c = self.cfg
         if not self._built:
             self._build()
-        lib = _lib.lib()
         dev = _lib.require_device(labels)
         nd = c['num_dim']
         if labels.dim() != nd + 2 or labels.shape[-1] != 1 or tuple(labels.shape[1:-1]) != tuple(int(s) for s in c['in_shape']):
             raise ValueError('labels_to_image_new expects label maps of shape [B, %s, 1], got %s'
                              % (', '.join(str(int(s)) for s in c['in_shape']), tuple(labels.shape)))
         B = labels.shape[0]
-        st = _lib.stream_ptr(dev)
         draws = {}
         lab = labels.to(torch.float32).contiguous()                       # compute_type (:1059-1061)
         in_shape, out_shape = np.asarray(c['in_shape']), np.asarray(c['out_shape'])
@@ -342,19 +327,15 @@ class SynthModelNew(nn.Module):
         gen_lut = torch.from_numpy(c['gen_lut']).to(dev)
         idx = torch.empty(lab.shape, dtype=torch.float32, device=dev)
         lab_i = lab.to(torch.int32).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_relabel_i32(_lib.ptr(lab_i), _lib.ptr(gen_lut), gen_lut.numel(), _lib.ptr(idx), lab_i.numel(), st)
-        _lib.check(rc, 'nrt_synth_relabel_i32')
+        _lib.call(dev, 'nrt_synth_relabel_i32', _lib.ptr(lab_i), _lib.ptr(gen_lut), gen_lut.numel(), _lib.ptr(idx), lab_i.numel())
         m0 = torch.as_tensor(np.asarray(c['mean_min'], np.float32), device=dev)
         m1 = torch.as_tensor(np.asarray(c['mean_max'], np.float32), device=dev)
         mean = (m0 + (m1 - m0) * torch.rand((B, C, L), generator=self._gen(dev, 'mean'), device=dev)).contiguous()
         zeros_v = torch.zeros((B,) + S, dtype=torch.float32, device=dev)
         zeros_s = torch.zeros_like(mean)
         image = torch.empty((B,) + S + (C,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nrt_synth_intensity_f32(_lib.ptr(idx.contiguous()), _lib.ptr(zeros_v), _lib.ptr(mean), _lib.ptr(zeros_s), None,
-                                             _lib.ptr(image), B, V, C, L, st)
-        _lib.check(rc, 'nrt_synth_intensity_f32')
+        _lib.call(dev, 'nrt_synth_intensity_f32', _lib.ptr(idx.contiguous()), _lib.ptr(zeros_v), _lib.ptr(mean), _lib.ptr(zeros_s), None,
+                  _lib.ptr(image), B, V, C, L)
         mean_image = image
         draws['mean'] = mean
         # ---- bias field (:1179-1193) --------------------------------------------------------------------------------------
@@ -363,10 +344,9 @@ class SynthModelNew(nn.Module):
             bias_field = self.perlin_bias(image).contiguous()
             draws['bias_field'] = bias_field
             out = torch.empty_like(image)
-            with torch.cuda.device(dev):                                  # image * exp(bias), one bias value per element
-                rc = lib.nrt_synth_bias_clip_f32(_lib.ptr(image), _lib.ptr(bias_field), _lib.ptr(out), image.numel(), 1,
-                                                 float('-inf'), float('inf'), st)
-            _lib.check(rc, 'nrt_synth_bias_clip_f32')
+            # image * exp(bias), one bias value per element
+            _lib.call(dev, 'nrt_synth_bias_clip_f32', _lib.ptr(image), _lib.ptr(bias_field), _lib.ptr(out), image.numel(), 1, float('-inf'),
+                      float('inf'))
             image = out
             bias_field = torch.exp(bias_field)                              # bias_func = tf.exp: what return_bias hands out
         # ---- noise (:1196) -------------------------------------------------------------------------------------------------
@@ -378,10 +358,8 @@ class SynthModelNew(nn.Module):
             flag = (torch.rand((B,), generator=self._gen(dev, 'background'), device=dev) < c['zero_background']).to(torch.float32)
             draws['bg_zero'] = flag
             out = torch.empty_like(image)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_bg_clear_f32(_lib.ptr(image.contiguous()), _lib.ptr(lab.contiguous()), _lib.ptr(flag.contiguous()),
-                                                _lib.ptr(out), B, V, C, st)
-            _lib.check(rc, 'nrt_synth_bg_clear_f32')
+            _lib.call(dev, 'nrt_synth_bg_clear_f32', _lib.ptr(image.contiguous()), _lib.ptr(lab.contiguous()), _lib.ptr(flag.contiguous()),
+                      _lib.ptr(out), B, V, C)
             image = out
         # ---- blur, thick slices (:1210-1226) --------------------------------------------------------------------------------
         sig_hi = self.blur._normalize_sigma(c['blur_max'], nd)
@@ -401,10 +379,9 @@ class SynthModelNew(nn.Module):
             g = (1 - c['gamma']) + 2 * c['gamma'] * torch.rand((B, C), generator=self._gen(dev, 'gamma'), device=dev)
             draws['gamma'] = g
             out = torch.empty_like(image)
-            with torch.cuda.device(dev):                                  # the kernel raises to exp(.): pass log(gamma)
-                rc = lib.nrt_synth_gamma_dc_f32(_lib.ptr(image.contiguous()), _lib.ptr(torch.log(g).contiguous()), None, _lib.ptr(out),
-                                                B, V, C, st)
-            _lib.check(rc, 'nrt_synth_gamma_dc_f32')
+            # the kernel raises to exp(.): pass log(gamma)
+            _lib.call(dev, 'nrt_synth_gamma_dc_f32', _lib.ptr(image.contiguous()), _lib.ptr(torch.log(g).contiguous()), None, _lib.ptr(out),
+                      B, V, C)
             image = out
         # ---- output labels (:1243-1263) ----------------------------------------------------------------------------------------
         out_lut = torch.from_numpy(c['out_lut']).to(dev)
@@ -412,13 +389,10 @@ class SynthModelNew(nn.Module):
         if c['one_hot']:
             depth = c['depth']
             lab_out = torch.empty((B,) + S + (depth,), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_labels_out(_lib.ptr(lab_c), _lib.ptr(out_lut), out_lut.numel(), depth, _lib.ptr(lab_out), None, B * V, st)
+            _lib.call(dev, 'nrt_synth_labels_out', _lib.ptr(lab_c), _lib.ptr(out_lut), out_lut.numel(), depth, _lib.ptr(lab_out), None, B * V)
         else:
             lab_out = torch.empty((B,) + S + (1,), dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.nrt_synth_labels_out(_lib.ptr(lab_c), _lib.ptr(out_lut), out_lut.numel(), 1, None, _lib.ptr(lab_out), B * V, st)
-        _lib.check(rc, 'nrt_synth_labels_out')
+            _lib.call(dev, 'nrt_synth_labels_out', _lib.ptr(lab_c), _lib.ptr(out_lut), out_lut.numel(), 1, None, _lib.ptr(lab_out), B * V)
         self.last_draws = draws
         outputs = []
         if c['return_im']:

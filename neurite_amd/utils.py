@@ -76,7 +76,6 @@ class _InterpnFn(torch.autograd.Function):
 
 
 def _launch_interpn_bwd(vol, loc, grad_out, cfg, need_vol, need_loc):
-    lib = _lib.lib()
     dev = _lib.require_device(vol, loc, grad_out)
     batched, single = cfg['batched'], cfg.get('single_transform', False)
     B = vol.shape[0] if batched else 1
@@ -94,11 +93,8 @@ def _launch_interpn_bwd(vol, loc, grad_out, cfg, need_vol, need_loc):
             nvol = int(np.prod(S)) * Cc
             nloc = int(np.prod(out_spatial)) * D
             loc_bs = 0 if (single or loc is None) else nloc
-            with torch.cuda.device(dev):
-                rc = lib.nrt_interpn_nearest_bwd_f32(_lib.ptr(loc), _lib.ptr(g), _lib.ptr(gvol), D, _lib.ints(S),
-                                                     _lib.ints(abi_spatial), Cc, B, nvol, loc_bs, cfg['loc_mode'],
-                                                     int(cfg['fill_value'] is not None), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_interpn_nearest_bwd_f32')
+            _lib.call(dev, 'nrt_interpn_nearest_bwd_f32', _lib.ptr(loc), _lib.ptr(g), _lib.ptr(gvol), D, _lib.ints(S),
+                      _lib.ints(abi_spatial), Cc, B, nvol, loc_bs, cfg['loc_mode'], int(cfg['fill_value'] is not None))
         return gvol, gloc
     gvol = torch.zeros_like(vol) if need_vol else None
     gloc = None
@@ -111,11 +107,8 @@ def _launch_interpn_bwd(vol, loc, grad_out, cfg, need_vol, need_loc):
         nvol = int(np.prod(S)) * Cc
         nloc = int(np.prod(out_spatial)) * D
         loc_bs = 0 if (single or loc is None) else nloc
-        with torch.cuda.device(dev):
-            rc = lib.nrt_interpn_bwd_f32(_lib.ptr(vol), _lib.ptr(loc), _lib.ptr(g), _lib.ptr(gvol), _lib.ptr(gloc), D,
-                                         _lib.ints(S), _lib.ints(abi_spatial), Cc, B, nvol, loc_bs, cfg['loc_mode'],
-                                         int(cfg['fill_value'] is not None), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_interpn_bwd_f32')
+        _lib.call(dev, 'nrt_interpn_bwd_f32', _lib.ptr(vol), _lib.ptr(loc), _lib.ptr(g), _lib.ptr(gvol), _lib.ptr(gloc), D, _lib.ints(S),
+                  _lib.ints(abi_spatial), Cc, B, nvol, loc_bs, cfg['loc_mode'], int(cfg['fill_value'] is not None))
     if gloc is not None and single and batched:
         gloc = gloc.sum(0, keepdim=True)       # one transform shared by the whole batch
     return gvol, gloc
@@ -141,7 +134,6 @@ def _launch_interpn(vol, loc, out_spatial, loc_mode, method, fill_value, batched
     vol [B?, *S, C] contiguous; loc [B?, *S', D] float32 contiguous or None (LINSPACE).
     Returns out [B?, *S', C] with vol's dtype.
     """
-    lib = _lib.lib()
     dev = _lib.require_device(vol, loc)
     vol = vol.contiguous()
     if batched:
@@ -173,31 +165,25 @@ def _launch_interpn(vol, loc, out_spatial, loc_mode, method, fill_value, batched
     vol_bs = nvol
     loc_bs = 0 if (single_transform or loc is None) else nloc
     has_fill = fill_value is not None
-    st = _lib.stream_ptr(dev)
-    with torch.cuda.device(dev):
-        if vol.dtype in _ANY_DTYPES and (D > 3 or vol.dtype not in (torch.float32, torch.int32)):
-            # float16 / bfloat16 / float64 volumes, and ranks 4-8: the dtype- and rank-generic kernel (csrc/interpn_any.hip);
-            # arithmetic in the volume dtype, one rounding per op, as TensorFlow evaluates utils.py:137-213
-            if vol.dtype == torch.int32:
-                assert method == _lib.INTERP_NEAREST
-            loc64 = loc is not None and loc.dtype == torch.float64
-            assert not loc64 or (vol.dtype == torch.float64 and loc_mode == _lib.LOC_ABSOLUTE)
-            rc = lib.nrt_interpn_any(_lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), _ANY_DTYPES[vol.dtype], D, _lib.ints(S),
-                                     _lib.ints(out_spatial), Cc, B, vol_bs, loc_bs, loc_mode, int(loc64), method,
-                                     int(has_fill), float(fill_value) if has_fill else 0.0, st)
-        elif vol.dtype == torch.float32:
-            rc = lib.nrt_interpn_f32_ex(_lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), D, _lib.ints(S),
-                                        _lib.ints(out_spatial), Cc, B, vol_bs, loc_bs, loc_mode, method,
-                                        int(has_fill), float(fill_value) if has_fill else 0.0,
-                                        int(variant), int(tune), st)
-        elif vol.dtype == torch.int32:
+    if vol.dtype in _ANY_DTYPES and (D > 3 or vol.dtype not in (torch.float32, torch.int32)):
+        # float16 / bfloat16 / float64 volumes, and ranks 4-8: the dtype- and rank-generic kernel (csrc/interpn_any.hip);
+        # arithmetic in the volume dtype, one rounding per op, as TensorFlow evaluates utils.py:137-213
+        if vol.dtype == torch.int32:
             assert method == _lib.INTERP_NEAREST
-            rc = lib.nrt_interpn_nearest_i32(_lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), D, _lib.ints(S),
-                                             _lib.ints(out_spatial), Cc, B, vol_bs, loc_bs, loc_mode,
-                                             int(has_fill), int(fill_value) if has_fill else 0, st)
-        else:
-            raise NotImplementedError('unsupported volume dtype %s' % vol.dtype)
-    _lib.check(rc, 'nrt_interpn')
+        loc64 = loc is not None and loc.dtype == torch.float64
+        assert not loc64 or (vol.dtype == torch.float64 and loc_mode == _lib.LOC_ABSOLUTE)
+        _lib.call(dev, 'nrt_interpn_any', _lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), _ANY_DTYPES[vol.dtype], D, _lib.ints(S),
+                  _lib.ints(out_spatial), Cc, B, vol_bs, loc_bs, loc_mode, int(loc64), method, int(has_fill),
+                  float(fill_value) if has_fill else 0.0)
+    elif vol.dtype == torch.float32:
+        _lib.call(dev, 'nrt_interpn_f32_ex', _lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), D, _lib.ints(S), _lib.ints(out_spatial), Cc, B,
+                  vol_bs, loc_bs, loc_mode, method, int(has_fill), float(fill_value) if has_fill else 0.0, int(variant), int(tune))
+    elif vol.dtype == torch.int32:
+        assert method == _lib.INTERP_NEAREST
+        _lib.call(dev, 'nrt_interpn_nearest_i32', _lib.ptr(vol), _lib.ptr(loc), _lib.ptr(out), D, _lib.ints(S), _lib.ints(out_spatial),
+                  Cc, B, vol_bs, loc_bs, loc_mode, int(has_fill), int(fill_value) if has_fill else 0)
+    else:
+        raise NotImplementedError('unsupported volume dtype %s' % vol.dtype)
     return out
 
 
@@ -360,15 +346,12 @@ def affine_to_dense_shift(matrix, shape, shift_center=True, indexing='ij'):
             and not (torch.is_grad_enabled() and matrix.requires_grad)):
         # one kernel writes the D floats of a voxel (csrc/vxm.hip); a leading batch axis gives [B, *shape, D].  Under autograd
         # (an affine that a network predicted) the differentiable torch form below runs instead.
-        lib = _lib.lib()
         m = matrix.detach().contiguous()
         batch = m.shape[0] if m.dim() == 3 else 1
         out = torch.empty(((batch,) if m.dim() == 3 else ()) + tuple(int(n) for n in shape) + (D,), dtype=torch.float32, device=m.device)
         if out.numel():
-            with torch.cuda.device(m.device):
-                rc = lib.nrt_affine_to_dense_shift_f32(_lib.ptr(m), int(batch), D, _lib.ints([int(n) for n in shape]),
-                                                       int(bool(shift_center)), _lib.ptr(out), _lib.stream_ptr(m.device))
-            _lib.check(rc, 'nrt_affine_to_dense_shift_f32')
+            _lib.call(m.device, 'nrt_affine_to_dense_shift_f32', _lib.ptr(m), int(batch), D, _lib.ints([int(n) for n in shape]),
+                      int(bool(shift_center)), _lib.ptr(out))
         return out
     if matrix.dim() == 3:
         return torch.stack([affine_to_dense_shift(matrix[b], shape, shift_center=shift_center, indexing=indexing)
@@ -399,7 +382,6 @@ def _warp_add(src, shift, batched, interp_method='linear', fill_value=None):
     shift + transform(src, shift) in 'ij' coordinates: one kernel pass (csrc/interpn.hip, nrt_interpn_add_f32).
     src [B?, *S, C], shift [B?, *S', D] float32.  Falls back to the differentiable two-op form under autograd.
     """
-    lib = _lib.lib()
     dev = _lib.require_device(src, shift)
     if interp_method != 'linear':
         assert interp_method == 'nearest', 'method should be linear or nearest, got: %s' % interp_method
@@ -426,12 +408,9 @@ def _warp_add(src, shift, batched, interp_method='linear', fill_value=None):
     if out.numel() == 0:
         return out
     has_fill = fill_value is not None
-    with torch.cuda.device(dev):
-        rc = lib.nrt_interpn_add_f32(_lib.ptr(src), _lib.ptr(shift), _lib.ptr(shift), _lib.ptr(out), D, _lib.ints(S),
-                                     _lib.ints(out_spatial), Cc, B, int(np.prod(S)) * Cc,
-                                     int(np.prod(out_spatial)) * D, int(np.prod(out_spatial)) * Cc, _lib.LOC_SHIFT,
-                                     int(has_fill), float(fill_value) if has_fill else 0.0, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_interpn_add_f32')
+    _lib.call(dev, 'nrt_interpn_add_f32', _lib.ptr(src), _lib.ptr(shift), _lib.ptr(shift), _lib.ptr(out), D, _lib.ints(S),
+              _lib.ints(out_spatial), Cc, B, int(np.prod(S)) * Cc, int(np.prod(out_spatial)) * D, int(np.prod(out_spatial)) * Cc,
+              _lib.LOC_SHIFT, int(has_fill), float(fill_value) if has_fill else 0.0)
     return out
 
 
@@ -593,7 +572,6 @@ def gaussian_kernel(sigma, windowsize=None, indexing='ij', separate=False, rando
 
 def _conv1d_axis(x, k, ax, padding, stride, dilation):
     """one separable pass along tensor axis `ax` of the contiguous float32 tensor x (csrc/filter.hip)."""
-    lib = _lib.lib()
     dev = x.device
     n, w = x.shape[ax], k.numel()
     ke = (w - 1) * dilation + 1
@@ -611,10 +589,8 @@ def _conv1d_axis(x, k, ax, padding, stride, dilation):
     inner = int(np.prod(x.shape[ax + 1:]))
     y = torch.empty(tuple(x.shape[:ax]) + (o,) + tuple(x.shape[ax + 1:]), dtype=torch.float32, device=dev)
     if y.numel():
-        with torch.cuda.device(dev):
-            rc = lib.nrt_conv1d_axis_f32(_lib.ptr(x), _lib.ptr(k), _lib.ptr(y), outer, n, inner, o, w, int(stride),
-                                         int(dilation), int(before), _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_conv1d_axis_f32')
+        _lib.call(dev, 'nrt_conv1d_axis_f32', _lib.ptr(x), _lib.ptr(k), _lib.ptr(y), outer, n, inner, o, w, int(stride), int(dilation),
+                  int(before))
     return y
 
 
@@ -676,9 +652,7 @@ def minmax_norm(x, axis=None):
         return y
     nws = lib.nrt_minmax_workspace_bytes(outer, inner)
     ws = torch.empty((max(int(nws), 16),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_minmax_norm_f32(_lib.ptr(x), _lib.ptr(y), outer, red, inner, _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_minmax_norm_f32')
+    _lib.call(dev, 'nrt_minmax_norm_f32', _lib.ptr(x), _lib.ptr(y), outer, red, inner, _lib.ptr(ws), nws)
     return y
 
 
@@ -689,9 +663,7 @@ def _device_minmax(x):
     out = torch.empty((2,), dtype=torch.float32, device=dev)
     nws = int(lib.nrt_minmax_workspace_bytes(1, 1))
     ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_minmax_f32(_lib.ptr(x), x.numel(), _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_minmax_f32')
+    _lib.call(dev, 'nrt_minmax_f32', _lib.ptr(x), x.numel(), _lib.ptr(out), _lib.ptr(ws), nws)
     return out
 
 
@@ -709,9 +681,7 @@ def _bin_centers(x, bin_centers, nb_bins):
     c = torch.empty((int(nb_bins),), dtype=torch.float32, device=dev)
     nws = int(lib.nrt_minmax_workspace_bytes(1, 1))
     ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_bin_centers_f32(_lib.ptr(x), x.numel(), int(nb_bins), _lib.ptr(c), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_bin_centers_f32')
+    _lib.call(dev, 'nrt_bin_centers_f32', _lib.ptr(x), x.numel(), int(nb_bins), _lib.ptr(c), _lib.ptr(ws), nws)
     return c
 
 
@@ -721,7 +691,6 @@ def soft_quantize(x, bin_centers=None, nb_bins=16, alpha=1, min_clip=-np.inf, ma
     every bin centre c.  Returns a tensor with one more dimension [..., B].  Specify bin_centers OR nb_bins (centres are then
     spread between the extrema of x).
     """
-    lib = _lib.lib()
     dev = _lib.require_device(x)
     if x.dtype != torch.float32:
         raise NotImplementedError('soft_quantize: float32 tensors, got %s' % x.dtype)
@@ -734,15 +703,12 @@ def soft_quantize(x, bin_centers=None, nb_bins=16, alpha=1, min_clip=-np.inf, ma
 
 
 def _soft_quantize_fwd(x, centers, cfg):
-    lib = _lib.lib()
     dev = x.device
     nb = centers.numel()
     out = torch.empty(tuple(x.shape) + (nb,), dtype=torch.float32, device=dev)
     if x.numel():
-        with torch.cuda.device(dev):
-            rc = lib.nrt_soft_quantize_f32(_lib.ptr(x), _lib.ptr(centers), cfg[0], cfg[1], cfg[2], cfg[3], _lib.ptr(out),
-                                           x.numel(), nb, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_soft_quantize_f32')
+        _lib.call(dev, 'nrt_soft_quantize_f32', _lib.ptr(x), _lib.ptr(centers), cfg[0], cfg[1], cfg[2], cfg[3], _lib.ptr(out), x.numel(),
+                  nb)
     return out
 
 
@@ -762,15 +728,12 @@ class _SoftQuantizeFn(torch.autograd.Function):
     def backward(ctx, g):
         x, centers = ctx.saved_tensors
         cfg = ctx.cfg
-        lib = _lib.lib()
         dev = x.device
         g = g.to(torch.float32).contiguous()
         gx = torch.empty_like(x)
         if x.numel():
-            with torch.cuda.device(dev):
-                rc = lib.nrt_soft_quantize_bwd_f32(_lib.ptr(x), _lib.ptr(centers), cfg[0], cfg[1], cfg[2], cfg[3], _lib.ptr(g),
-                                                   _lib.ptr(gx), x.numel(), centers.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, 'nrt_soft_quantize_bwd_f32')
+            _lib.call(dev, 'nrt_soft_quantize_bwd_f32', _lib.ptr(x), _lib.ptr(centers), cfg[0], cfg[1], cfg[2], cfg[3], _lib.ptr(g),
+                      _lib.ptr(gx), x.numel(), centers.numel())
         return gx, None, None
 
 
@@ -817,10 +780,8 @@ class _BarycenterFn(torch.autograd.Function):
         shape = _lib.ints(red)
         nws = int(lib.nrt_barycenter_workspace_bytes(code, outer, shape, k, inner))
         ws = _lib.workspace(dev, max(nws, 16))
-        with torch.cuda.device(dev):
-            rc = lib.nrt_barycenter(_lib.ptr(x), code, outer, shape, k, inner, flags[0], flags[1], _lib.ptr(y), _lib.ptr(sums),
-                                    _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_barycenter')
+        _lib.call(dev, 'nrt_barycenter', _lib.ptr(x), code, outer, shape, k, inner, flags[0], flags[1], _lib.ptr(y), _lib.ptr(sums),
+                  _lib.ptr(ws), nws)
         ctx.save_for_backward(y, sums)
         ctx.cfg = (code, outer, tuple(red), inner, flags, x.dtype)
         return y
@@ -837,10 +798,8 @@ class _BarycenterFn(torch.autograd.Function):
         shape = _lib.ints(red)
         nws = int(lib.nrt_barycenter_workspace_bytes(code, outer, shape, k, inner))
         ws = _lib.workspace(dev, max(nws, 16))
-        with torch.cuda.device(dev):
-            rc = lib.nrt_barycenter_bwd(_lib.ptr(gy), _lib.ptr(y), _lib.ptr(sums), code, outer, shape, k, inner, flags[0], flags[1],
-                                        _lib.ptr(gx), _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, 'nrt_barycenter_bwd')
+        _lib.call(dev, 'nrt_barycenter_bwd', _lib.ptr(gy), _lib.ptr(y), _lib.ptr(sums), code, outer, shape, k, inner, flags[0], flags[1],
+                  _lib.ptr(gx), _lib.ptr(ws), nws)
         return gx, None, None
 
 
@@ -1109,17 +1068,13 @@ def draw_swap_matrix(ndims, last_row=True, dtype=torch.float32, seed=None):
 
 def _axis_gather(x, index, ax):
     """y = tf.gather(x, index, axis=ax) of a float32 device tensor (csrc/synth.hip)."""
-    lib = _lib.lib()
     dev = _lib.require_device(x)
     x = x.contiguous()
     idx = torch.as_tensor(np.asarray(index, dtype=np.int32)).to(dev)
     outer = int(np.prod(x.shape[:ax])) if ax else 1
     inner = int(np.prod(x.shape[ax + 1:]))
     y = torch.empty(tuple(x.shape[:ax]) + (idx.numel(),) + tuple(x.shape[ax + 1:]), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nrt_synth_axis_gather_f32(_lib.ptr(x), _lib.ptr(idx), _lib.ptr(y), outer, x.shape[ax], idx.numel(), inner,
-                                           _lib.stream_ptr(dev))
-    _lib.check(rc, 'nrt_synth_axis_gather_f32')
+    _lib.call(dev, 'nrt_synth_axis_gather_f32', _lib.ptr(x), _lib.ptr(idx), _lib.ptr(y), outer, x.shape[ax], idx.numel(), inner)
     return y
 
 

@@ -105,7 +105,4 @@ class Raw:
         return bool((N(self.whole) == self.MARK).all())
 
 
-def call(dev, name, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.stream_ptr(dev))
-    _lib.check(rc, name)
+call = _lib.call                                 # the product's own launch helper: device guard, stream, status check

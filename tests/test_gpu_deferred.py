@@ -304,3 +304,24 @@ def test_deferred_warp_behaves_like_its_tensor_everywhere_else(dev, batch):
     assert w.is_contiguous() and not w.requires_grad and w.pending
     assert 'pending' in repr(w) and w.pending                     # printing a pending warp says so instead of computing it
     assert 'tensor' in repr(w.materialize()) and 'tensor' in repr(w)
+
+
+def test_lib_call_checks_the_status_and_looks_the_entry_point_up_at_call_time(dev, monkeypatch):
+    """_lib.call is the one place a launch goes through: null pointers make nrt_softmax_lastdim_f32 refuse at its argument check (nothing
+    is launched), and the error names the entry point -- or the `what` text -- and the status"""
+    L = ne._lib
+    L.require_device(torch.empty(1, device=dev))
+    with pytest.raises(L.NeuriteAmdError) as e:
+        L.call(dev, 'nrt_softmax_lastdim_f32', None, None, 0, 0)
+    assert 'nrt_softmax_lastdim_f32 failed' in str(e.value) and '(status %d)' % L.NRT_ERR_INVALID_ARG in str(e.value)
+    assert L.lib().nrt_status_string(L.NRT_ERR_INVALID_ARG).decode() in str(e.value)
+    with pytest.raises(L.NeuriteAmdError) as e:
+        L.call(dev, 'nrt_softmax_lastdim_f32', None, None, 0, 0, what='x (y)')
+    assert str(e.value).startswith('x (y) failed') and 'nrt_softmax_lastdim_f32' not in str(e.value)
+    assert '(status %d)' % L.NRT_ERR_INVALID_ARG in str(e.value)
+    # an entry point replaced on the handle is the one that runs: the arguments as given, then the current stream of `dev`
+    seen = []
+    monkeypatch.setattr(L.lib(), 'nrt_softmax_lastdim_f32', lambda *a: seen.append(a) or L.NRT_OK)
+    L.call(dev, 'nrt_softmax_lastdim_f32', None, None, 3, 4)
+    assert len(seen) == 1 and seen[0][:4] == (None, None, 3, 4) and len(seen[0]) == 5
+    assert seen[0][4].value == (torch.cuda.current_stream(dev).cuda_stream or None)

@@ -84,6 +84,28 @@ def test_product_never_imports_the_oracle():
                 assert 'liboracle' not in text, f
 
 
+def test_every_launch_goes_through_lib_call():
+    """Outside _lib.py the package calls an entry point directly only when it is a query: one whose result is not the status int, or
+    whose last argument is not the `void *stream`.  Everything that launches goes through _lib.call (device guard, stream, check)."""
+    import ast
+    import glob
+    sigs = ne._lib._SIGNATURES
+    queries = {n for n, (res, args) in sigs.items() if res is not ctypes.c_int or not args or args[-1] is not ctypes.c_void_p}
+    assert {'nrt_dice_workspace_bytes', 'nrt_conv3d_up2_supported', 'nrt_status_string', 'nrt_init'} <= queries
+    assert not {'nrt_softmax_lastdim_f32', 'nrt_conv3d_f32', 'nrt_counters_reset'} & queries
+    root = os.path.dirname(ne.__file__)
+    direct = []
+    for path in sorted(glob.glob(os.path.join(root, '*.py'))):
+        if os.path.basename(path) == '_lib.py':
+            continue
+        for node in ast.walk(ast.parse(open(path).read())):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith('nrt_'):
+                assert node.func.attr in sigs, (path, node.lineno, node.func.attr)
+                if node.func.attr not in queries:
+                    direct.append('%s:%d %s' % (os.path.basename(path), node.lineno, node.func.attr))
+    assert not direct, 'launched without _lib.call: ' + ', '.join(direct)
+
+
 def test_interpn_argument_errors_match_reference():
     v = torch.zeros(4, 4, 4, 2)
     with pytest.raises(Exception, match='Number of loc Tensors 2 does not match volume dimension 3'):
