@@ -674,6 +674,27 @@ int nrt_conv1d_axis_f32(const float *x, const float *kernel, float *y, long long
 size_t nrt_minmax_workspace_bytes(long long outer, int inner);
 int nrt_minmax_norm_f32(const float *x, float *y, long long outer, long long reduce_len, int inner, void *workspace,
                         size_t workspace_bytes, void *stream);
+/* Backward of the two, float32, no atomics (two runs give the same bits), no host synchronisation.
+ *   nrt_conv1d_axis_bwd_f32   grad_x [outer, axis_len, inner] from grad_y [outer, out_len, inner]:
+ *                             grad_x[o, p, i] = sum_t kernel[t] * grad_y[o, (p + pad_before - t*dilation) / stride, i] over the t whose
+ *                             quotient is an integer in [0, out_len); from +0, terms in DESCENDING t, one rounding per multiply and
+ *                             per add, absent terms skipped.  stride 1 runs on the kernels of nrt_conv1d_axis_f32 (taps reversed).
+ *   nrt_conv1d_axis_bwd_kernel_f32   grad_kernel[t] = sum_{o, a, i} grad_y[o, a, i] * x[o, a*stride + t*dilation - pad_before, i];
+ *                             float32 products summed over at most 16 terms per lane, float64 above that; the workspace
+ *                             (8-byte aligned, >= nrt_conv1d_axis_bwd_kernel_workspace_bytes) holds the block partials
+ *   nrt_minmax_norm_bwd_f32   per group with m = min, M = max, r = M - m: grad_x = 0 if r == 0 (div_no_nan), else
+ *                             grad_x_i = g_i / r + [x_i == m] (Sgy - Sg) / (r n_min) - [x_i == M] Sgy / (r n_max), Sg = sum g,
+ *                             Sgy = sum g y; ties by float equality share evenly.  Same limits as nrt_minmax_norm_f32; the
+ *                             workspace is 8-byte aligned and >= nrt_minmax_norm_bwd_workspace_bytes */
+int nrt_conv1d_axis_bwd_f32(const float *grad_y, const float *kernel, float *grad_x, long long outer, int axis_len, long long inner,
+                            int out_len, int width, int stride, int dilation, int pad_before, void *stream);
+size_t nrt_conv1d_axis_bwd_kernel_workspace_bytes(long long outer, int out_len, long long inner, int width);
+int nrt_conv1d_axis_bwd_kernel_f32(const float *x, const float *grad_y, float *grad_kernel, long long outer, int axis_len,
+                                   long long inner, int out_len, int width, int stride, int dilation, int pad_before,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+size_t nrt_minmax_norm_bwd_workspace_bytes(long long outer, long long reduce_len, int inner);
+int nrt_minmax_norm_bwd_f32(const float *x, const float *grad_y, float *grad_x, long long outer, long long reduce_len, int inner,
+                            void *workspace, size_t workspace_bytes, void *stream);
 /* out2 = {min, max} of x[0..n) on the device (no host synchronisation); workspace >= nrt_minmax_workspace_bytes(1, 1) */
 int nrt_minmax_f32(const float *x, long long n, float *out2, void *workspace, size_t workspace_bytes, void *stream);
 /* centers[0..nb_bins) = tf.linspace(min(x), max(x), nb_bins), the bin centres of utils.soft_quantize / MutualInformation
@@ -736,6 +757,10 @@ int nrt_synth_axis_mask_f32(const float *x, const float *mask, float *y, long lo
                             void *stream);
 int nrt_synth_axis_gather_f32(const float *x, const int *index, float *y, long long outer, int axis_len, int out_len,
                               long long inner, void *stream);
+/* gradient of nrt_synth_axis_gather_f32 for a non-decreasing index list: run_start [axis_len + 1], the outputs that read slice a
+ * are [run_start[a], run_start[a + 1]); grad_x[o, a, i] = their sum, ascending from +0 (zeros for an empty run); no atomics */
+int nrt_synth_axis_gather_bwd_f32(const float *grad_y, const int *run_start, float *grad_x, long long outer, int axis_len,
+                                  int out_len, long long inner, void *stream);
 int nrt_synth_noise_add_f32(const float *x, const float *noise, const float *sd, float *y, int batch, long long nvox,
                             int channels, int sd_batch_stride, int sd_channel_stride, void *stream);
 int nrt_synth_bg_clear_f32(const float *image, const float *labels, const float *flag, float *y, int batch, long long nvox,

@@ -117,6 +117,12 @@ _SIGNATURES = {
     'nrt_conv1d_axis_f32': (_i, [_vp, _vp, _vp, _ll, _i, _ll, _i, _i, _i, _i, _i, _vp]),
     'nrt_minmax_workspace_bytes': (_sz, [_ll, _i]),
     'nrt_minmax_norm_f32': (_i, [_vp, _vp, _ll, _ll, _i, _vp, _sz, _vp]),
+    'nrt_conv1d_axis_bwd_f32': (_i, [_vp, _vp, _vp, _ll, _i, _ll, _i, _i, _i, _i, _i, _vp]),
+    'nrt_conv1d_axis_bwd_kernel_workspace_bytes': (_sz, [_ll, _i, _ll, _i]),
+    'nrt_conv1d_axis_bwd_kernel_f32': (_i, [_vp, _vp, _vp, _ll, _i, _ll, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'nrt_minmax_norm_bwd_workspace_bytes': (_sz, [_ll, _ll, _i]),
+    'nrt_minmax_norm_bwd_f32': (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _sz, _vp]),
+    'nrt_synth_axis_gather_bwd_f32': (_i, [_vp, _vp, _vp, _ll, _i, _i, _ll, _vp]),
     'nrt_minmax_f32': (_i, [_vp, _ll, _vp, _vp, _sz, _vp]),
     'nrt_bin_centers_f32': (_i, [_vp, _ll, _i, _vp, _vp, _sz, _vp]),
     'nrt_soft_quantize_f32': (_i, [_vp, _vp, _f, _f, _f, _i, _vp, _ll, _i, _vp]),

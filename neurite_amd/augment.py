@@ -106,7 +106,7 @@ def random_blur_rescale(x, std_min=8 / 2.355, std_max=32 / 2.355, isotropic=Fals
     """
     Smooth the spatial dimensions of a tensor (trailing feature dimension) with a random Gaussian kernel per axis and rescale
     it such that a global statistic (`reduce`: 'std' or 'max', or tf/torch functions of those names) is unchanged
-    (augment.py:66-113).
+    (augment.py:66-113).  Forward-only: a backward that reaches it raises NotImplementedError.
     """
     _lib.require_device(x)
     n_dim = x.dim() - 1 - int(batched)
@@ -117,11 +117,16 @@ def random_blur_rescale(x, std_min=8 / 2.355, std_max=32 / 2.355, isotropic=Fals
     if isotropic:
         kernel = kernel[:1] * n_dim
     name = _reduce_name(reduce)
-    before = _global_stat(x, name)
-    y = utils.separable_conv(x, kernel, batched=batched)
-    after = _global_stat(y, name)
-    ratio = torch.where(after != 0, before / torch.where(after != 0, after, torch.ones_like(after)), torch.zeros_like(after))
-    return y * ratio, kernel                                    # tf.math.divide_no_nan
+
+    def blur_rescale():
+        before = _global_stat(x, name)
+        y = utils.separable_conv(x, kernel, batched=batched)
+        after = _global_stat(y, name)
+        ratio = torch.where(after != 0, before / torch.where(after != 0, after, torch.ones_like(after)), torch.zeros_like(after))
+        return y * ratio                                        # tf.math.divide_no_nan
+    # forward-only: the two statistics are launched untracked, so a graph through the blur alone would be half a gradient; a
+    # backward that reaches this op raises instead
+    return utils._maybe_tracked(blur_rescale, x), kernel
 
 
 def draw_perlin_full(shape, noise_min=0.01, noise_max=1, fwhm_min=4, fwhm_max=32, isotropic=False, batched=False,

@@ -9,6 +9,7 @@
 // utils.minmax_norm (:953-968): (x - min) / (max - min) with div_no_nan over any contiguous run of axes, viewed as
 // [outer, R, inner]; the extrema are order-independent, so they are reduced with integer atomics on a monotone
 // encoding of the floats (deterministic), then applied in a second pass.
+// Backward of both (float32, no float atomics): further down, "backward".
 
 #include <type_traits>
 
@@ -23,7 +24,10 @@ struct C1Args {
     long long outer;
     int A, Aout, W, stride, dil, pad;
     long long inner;        // elements (scalar kernel) or float4 groups (vector kernel)
+    int k0, kstep;          // tap t is k[k0 + t * kstep]: {0, 1} forward, {W - 1, -1} the taps reversed (the stride-1 input gradient)
 };
+
+__device__ __forceinline__ float tap_of(const C1Args &a, int t) { return a.k[a.k0 + t * a.kstep]; }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void conv1d_axis(C1Args a) {
@@ -43,7 +47,7 @@ __global__ __launch_bounds__(256) void conv1d_axis(C1Args a) {
             const int ai = a0 + t * a.dil;
             if (ai >= 0 && ai < a.A) {
                 const T v = xo[(long long)ai * a.inner];
-                acc = acc + a.k[t] * v;
+                acc = acc + tap_of(a, t) * v;
             }
         }
         y[e] = acc;
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(256) void conv1d_axis(C1Args a) {
 // outputs from W + 3 inputs instead of 4 W (same tap order per output => bit-identical to conv1d_axis<false>)
 __global__ __launch_bounds__(256) void conv1d_axis_run4(C1Args a) {
     extern __shared__ float ks[];
-    for (int t = threadIdx.x; t < a.W; t += 256) ks[t] = a.k[t];
+    for (int t = threadIdx.x; t < a.W; t += 256) ks[t] = tap_of(a, t);
     __syncthreads();
     const long long nrun = (a.Aout + 3) / 4;
     const long long total = a.outer * nrun;
@@ -91,10 +95,10 @@ __global__ __launch_bounds__(256) void conv1d_axis_run4(C1Args a) {
 constexpr int CF_TB = 8, CF_WMAX = 256;
 
 // stage the taps in LDS (zero-padded to a multiple of TB); true when all of them are finite
-__device__ __forceinline__ bool stage_taps(const float *__restrict__ k, int W, float *ks) {
+__device__ __forceinline__ bool stage_taps(const C1Args &a, float *ks) {
     int bad = 0;
     for (int t = threadIdx.x; t < CF_WMAX + CF_TB; t += 256) {
-        const float v = t < W ? k[t] : 0.0f;
+        const float v = t < a.W ? tap_of(a, t) : 0.0f;
         ks[t] = v;
         bad |= !(fabsf(v) <= 3.402823466e38f);
     }
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(256) void conv1d_axis_rows(C1Args a, int chunks) {
     constexpr int TB = CF_TB;
     static_assert(R - 1 <= TB, "the register window is rotated by one tap block");
     __shared__ __attribute__((aligned(16))) float ks[CF_WMAX + CF_TB];
-    const bool finite = stage_taps(a.k, a.W, ks);
+    const bool finite = stage_taps(a, ks);
     const T *x = (const T *)a.x;
     T *y = (T *)a.y;
     const long long total = a.outer * chunks * a.inner;
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void conv1d_axis_rows(C1Args a, int chunks) {
                 T s = T{};
                 for (int t = 0; t < a.W; ++t) {
                     const int ai = first + r + t;
-                    if (ai >= 0 && ai < a.A) s = s + a.k[t] * xo[(long long)ai * a.inner];
+                    if (ai >= 0 && ai < a.A) s = s + tap_of(a, t) * xo[(long long)ai * a.inner];
                 }
 #pragma unroll
                 for (int q = 0; q < R; ++q)
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(256) void conv1d_inner_lds(C1Args a, CiGeom g) {
     extern __shared__ __attribute__((aligned(16))) float ci_lds[];      // [rows][span] inputs, then the taps
     const int rows = 256 >> g.lpr_log2, span = g.spanq * 4;
     float *ks = ci_lds + rows * span;
-    const bool finite = stage_taps(a.k, a.W, ks);
+    const bool finite = stage_taps(a, ks);
     const long long rb = blockIdx.x / g.segs;
     const int seg0 = (int)(blockIdx.x - rb * g.segs) * (R << g.lpr_log2);
     const long long row0 = rb * rows;
@@ -241,7 +245,7 @@ __global__ __launch_bounds__(256) void conv1d_inner_lds(C1Args a, CiGeom g) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int kt = t - r;
-                if (kt >= 0 && kt < a.W) acc[r] = acc[r] + a.k[kt] * v;
+                if (kt >= 0 && kt < a.W) acc[r] = acc[r] + tap_of(a, kt) * v;
             }
         }
     }
@@ -440,17 +444,13 @@ unsigned fblocks(long long n) {
     return (unsigned)b;
 }
 
-}  // namespace
-
-extern "C" int nrt_conv1d_axis_f32(const float *x, const float *kernel, float *y, long long outer, int axis_len, long long inner,
-                                   int out_len, int width, int stride, int dilation, int pad_before, void *stream) {
-    if (!x || !kernel || !y || outer < 0 || axis_len < 1 || inner < 1 || out_len < 0 || width < 1 || stride < 1 || dilation < 1)
-        return NRT_ERR_INVALID_ARG;
-    if (outer == 0 || out_len == 0) return NRT_OK;
-    C1Args a;
-    a.x = x; a.k = kernel; a.y = y; a.outer = outer; a.A = axis_len; a.Aout = out_len; a.W = width; a.stride = stride;
-    a.dil = dilation; a.pad = pad_before; a.inner = inner;
-    hipStream_t st = nrt_stream(stream);
+// the dispatch of one stride-1-or-not pass y = conv(x, taps): shared by the forward entry point and by the stride-1 input gradient,
+// which is the same pass over grad_y with the taps reversed
+int launch_conv1d(C1Args a, hipStream_t st) {
+    const float *x = a.x;
+    float *y = a.y;
+    const long long outer = a.outer, inner = a.inner;
+    const int out_len = a.Aout, width = a.W, stride = a.stride, dilation = a.dil;
     const bool vec = inner % 4 == 0 && ((((uintptr_t)x | (uintptr_t)y) & 15) == 0);
     const bool fast = nrt_env_int("NRT_CONV1D_GENERIC", 0) != 1 && stride == 1 && dilation == 1 && width <= 256 && out_len >= 8;
     constexpr int R = 8;
@@ -484,6 +484,372 @@ extern "C" int nrt_conv1d_axis_f32(const float *x, const float *kernel, float *y
     } else {
         hipLaunchKernelGGL((conv1d_axis<false>), dim3(fblocks(outer * out_len * inner)), dim3(256), 0, st, a);
     }
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+// ---- backward (float32) -------------------------------------------------------------------------------------------------------
+// Input gradient of one pass, the transpose of the contract at the top: dx[o, p, i] = sum_t k[t] * g[o, (p + pad - t * dil) / stride, i]
+// over the t whose quotient is an integer in [0, out_len); an element starts at +0 and receives its terms in DESCENDING t, one rounding
+// per multiply and per add, absent terms skipped.  For stride 1 that is the forward contract applied to g with the taps reversed,
+// pad' = (W - 1) * dil - pad and out_len = axis_len, so it runs on the forward arms (launch_conv1d with k0 = W - 1, kstep = -1).
+// For stride > 1 conv1d_axis_bwd gathers: a lane owns one input element (a float4 of them when VEC), consecutive lanes are consecutive
+// in memory; the taps that reach it satisfy t * dil == p + pad (mod stride) and lie tstep = stride / gcd(dil, stride) apart.
+struct C1BwdArgs {
+    const float *g;
+    const float *k;
+    float *dx;
+    long long outer, inner;
+    int A, Aout, W, stride, dil, pad, tstep;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void conv1d_axis_bwd(C1BwdArgs a) {
+    typedef typename std::conditional<VEC, nrt_f4, float>::type T;
+    const T *g = (const T *)a.g;
+    T *dx = (T *)a.dx;
+    const long long total = a.outer * a.A * a.inner;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long i = e % a.inner;
+        const long long r = e / a.inner;
+        const int p = (int)(r % a.A);
+        const long long o = r / a.A;
+        const T *go = g + o * a.Aout * a.inner + i;
+        const int base = p + a.pad;
+        int t = a.W - 1;                                         // the largest tap on this element's residue class, if there is one
+        bool found = false;
+        for (int j = 0; j < a.tstep && t >= 0; ++j, --t)
+            if ((base - t * a.dil) % a.stride == 0) { found = true; break; }
+        T acc = T{};
+        if (found) {
+            for (; t >= 0; t -= a.tstep) {                       // the output index grows as t falls
+                const int num = base - t * a.dil;
+                if (num < 0) continue;
+                const int q = num / a.stride;
+                if (q >= a.Aout) break;
+                acc = acc + a.k[t] * go[(long long)q * a.inner];
+            }
+        }
+        dx[e] = acc;
+    }
+}
+
+// Tap gradient of one pass: dk[t] = sum_{o, a, i} g[o, a, i] * x[o, a * stride + t * dil - pad, i], out-of-range terms skipped.
+// A block owns a contiguous chunk of outputs; per tap block of DK_TB taps a lane keeps DK_TB float32 sums over at most DK_PER_LANE
+// outputs (256 apart, so consecutive lanes are consecutive in memory), which it then adds into float64 sums; the block adds its
+// lanes' float64 sums in a fixed tree and writes DK_TB partials.  conv1d_dk_finish adds the partials in block order in float64.
+// No atomics.  The longest float32 chain is DK_PER_LANE products.
+constexpr int DK_TB = 8, DK_PER_LANE = 16, DK_MAXB = 1024;
+
+struct DkArgs {
+    const float *x;
+    const float *g;
+    double *part;           // [blocks][Wp]
+    long long outer, inner, total, per_block;
+    int A, Aout, W, Wp, stride, dil, pad;
+};
+
+struct DkGeom { long long nblocks, per_block; int Wp; };
+
+DkGeom dk_geometry(long long total, int width) {
+    const long long unit = 256ll * DK_PER_LANE;
+    long long nsub = (total + unit - 1) / unit;
+    if (nsub < 1) nsub = 1;
+    const long long per = (nsub + DK_MAXB - 1) / DK_MAXB;
+    DkGeom g;
+    g.per_block = per * unit;
+    g.nblocks = (nsub + per - 1) / per;
+    g.Wp = ((width + DK_TB - 1) / DK_TB) * DK_TB;
+    return g;
+}
+
+__global__ __launch_bounds__(256) void conv1d_dk_partial(DkArgs a) {
+    __shared__ double red[4][DK_TB];
+    const long long b0 = (long long)blockIdx.x * a.per_block;
+    const long long b1 = b0 + a.per_block < a.total ? b0 + a.per_block : a.total;
+    for (int kb = 0; kb < a.W; kb += DK_TB) {
+        double dacc[DK_TB];
+#pragma unroll
+        for (int q = 0; q < DK_TB; ++q) dacc[q] = 0.0;
+        for (long long c0 = b0; c0 < b1; c0 += 256ll * DK_PER_LANE) {
+            float acc[DK_TB];
+#pragma unroll
+            for (int q = 0; q < DK_TB; ++q) acc[q] = 0.0f;
+            for (int j = 0; j < DK_PER_LANE; ++j) {
+                const long long e = c0 + (long long)j * 256 + threadIdx.x;
+                if (e >= b1) break;
+                const long long i = e % a.inner;
+                const long long r = e / a.inner;
+                const int ao = (int)(r % a.Aout);
+                const long long o = r / a.Aout;
+                const float gv = a.g[e];
+                const float *xo = a.x + o * a.A * a.inner + i;
+                const int first = ao * a.stride - a.pad + kb * a.dil;
+#pragma unroll
+                for (int q = 0; q < DK_TB; ++q) {
+                    const int ai = first + q * a.dil;
+                    if (kb + q < a.W && ai >= 0 && ai < a.A) acc[q] = acc[q] + gv * xo[(long long)ai * a.inner];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < DK_TB; ++q) dacc[q] += (double)acc[q];
+        }
+#pragma unroll
+        for (int q = 0; q < DK_TB; ++q) {
+            double v = dacc[q];
+            for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < DK_TB)
+            a.part[(long long)blockIdx.x * a.Wp + kb + threadIdx.x] =
+                ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void conv1d_dk_finish(const double *__restrict__ part, int nblocks, int Wp, int W, float *__restrict__ dk) {
+    for (int t = threadIdx.x; t < W; t += 256) {
+        double s = 0.0;
+        for (int b = 0; b < nblocks; ++b) s += part[(long long)b * Wp + t];
+        dk[t] = (float)s;
+    }
+}
+
+// minmax_norm backward over a group [outer, R, inner] with m, M the extrema, r = M - m: dx = 0 when r == 0 (div_no_nan), else
+//   dx_i = g_i / r + [x_i == m] (Sgy - Sg) / (r n_min) - [x_i == M] Sgy / (r n_max),   Sg = sum g, Sgy = sum g y, y as the forward forms it.
+// The extrema come from the forward's reduce kernels; mm_bwd_reduce forms per-block Sg, Sgy (float32 per lane over at most MB_CHAIN
+// elements, float64 above that) and the two tie counts, mm_bwd_apply adds the block partials of its column in block order (float64) and
+// writes dx with one rounding.  A block covers ct = min(inner, 256) columns and 256 / ct rows at a time, so consecutive lanes are
+// consecutive in memory; blockIdx = (row chunk, outer, column tile).  No float atomics.
+constexpr int MB_CHAIN = 16, MB_MAXB = 256;
+
+struct MbPart { double sg, sgy; int nmin, nmax; };
+
+struct MbArgs {
+    const float *x;
+    const float *g;
+    float *dx;
+    const int *keys;        // inner == 1: nbp block pairs per outer entry (minmax_reduce1); else [outer, inner, 2]
+    MbPart *part;           // [outer][nb][inner]
+    long long R, rows_per_block;
+    int inner, ct, rpp, nb, nbp;
+};
+
+struct MbGeom { int ct, tiles, rpp, nb; long long rows_per_block; };
+
+MbGeom mb_geometry(long long R, int inner) {
+    MbGeom g;
+    g.ct = inner < 256 ? inner : 256;
+    g.tiles = (inner + g.ct - 1) / g.ct;
+    g.rpp = 256 / g.ct;
+    const long long unit = (long long)g.rpp * MB_CHAIN;
+    long long nunits = (R + unit - 1) / unit;
+    if (nunits < 1) nunits = 1;
+    const long long per = (nunits + MB_MAXB - 1) / MB_MAXB;
+    g.rows_per_block = per * unit;
+    g.nb = (int)((nunits + per - 1) / per);
+    return g;
+}
+
+size_t mb_keys_bytes(long long outer, int inner) {
+    const size_t n = (size_t)outer * (size_t)(inner == 1 ? MM_NB : inner) * 2 * sizeof(int);
+    return (n + 15) & ~(size_t)15;
+}
+
+// the extrema of (o, col); every lane of the block calls it
+__device__ __forceinline__ void mb_extrema(const MbArgs &a, int o, int col, bool active, int *sm, float &mn, float &mx) {
+    if (a.nbp > 0) {
+        int kmn = 0x7fffffff, kmx = (int)0x80000000;
+        if ((int)threadIdx.x < a.nbp) {
+            kmn = a.keys[((long long)o * a.nbp + threadIdx.x) * 2];
+            kmx = a.keys[((long long)o * a.nbp + threadIdx.x) * 2 + 1];
+        }
+        block_minmax(kmn, kmx, sm);
+        mn = key2f(kmn); mx = key2f(kmx);
+    } else if (active) {
+        mn = key2f(a.keys[((long long)o * a.inner + col) * 2]);
+        mx = key2f(a.keys[((long long)o * a.inner + col) * 2 + 1]);
+    } else {
+        mn = mx = 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void mm_bwd_reduce(MbArgs a) {
+    __shared__ int sm[8];
+    __shared__ double s1[256], s2[256];
+    __shared__ int c1[256], c2[256];
+    const int o = blockIdx.y, ci = threadIdx.x % a.ct, rr = threadIdx.x / a.ct;
+    const int col = blockIdx.z * a.ct + ci;
+    const bool active = rr < a.rpp && col < a.inner;
+    float mn, mx;
+    mb_extrema(a, o, col, active, sm, mn, mx);
+    const float den = mx - mn;
+    const long long r0 = (long long)blockIdx.x * a.rows_per_block;
+    const long long r1 = r0 + a.rows_per_block < a.R ? r0 + a.rows_per_block : a.R;
+    double dsg = 0.0, dsgy = 0.0;
+    int nmin = 0, nmax = 0;
+    if (active) {
+        long long row = r0 + rr;
+        while (row < r1) {
+            float sg = 0.0f, sgy = 0.0f;
+            for (int j = 0; j < MB_CHAIN && row < r1; ++j, row += a.rpp) {
+                const long long idx = ((long long)o * a.R + row) * a.inner + col;
+                const float xv = a.x[idx], gv = a.g[idx];
+                const float y = den != 0.0f ? (xv - mn) / den : 0.0f;
+                sg = sg + gv;
+                sgy = sgy + gv * y;
+                nmin += xv == mn;
+                nmax += xv == mx;
+            }
+            dsg += (double)sg;
+            dsgy += (double)sgy;
+        }
+    }
+    s1[threadIdx.x] = dsg; s2[threadIdx.x] = dsgy; c1[threadIdx.x] = nmin; c2[threadIdx.x] = nmax;
+    __syncthreads();
+    if (active && rr == 0) {
+        MbPart p = {0.0, 0.0, 0, 0};
+        for (int q = 0; q < a.rpp; ++q) {
+            const int l = q * a.ct + ci;
+            p.sg += s1[l]; p.sgy += s2[l]; p.nmin += c1[l]; p.nmax += c2[l];
+        }
+        a.part[((long long)o * a.nb + blockIdx.x) * a.inner + col] = p;
+    }
+}
+
+__global__ __launch_bounds__(256) void mm_bwd_apply(MbArgs a) {
+    __shared__ int sm[8];
+    const int o = blockIdx.y, ci = threadIdx.x % a.ct, rr = threadIdx.x / a.ct;
+    const int col = blockIdx.z * a.ct + ci;
+    const bool active = rr < a.rpp && col < a.inner;
+    float mn, mx;
+    mb_extrema(a, o, col, active, sm, mn, mx);
+    if (!active) return;
+    double Sg = 0.0, Sgy = 0.0;
+    long long nmin = 0, nmax = 0;
+    for (int b = 0; b < a.nb; ++b) {
+        const MbPart p = a.part[((long long)o * a.nb + b) * a.inner + col];
+        Sg += p.sg; Sgy += p.sgy; nmin += p.nmin; nmax += p.nmax;
+    }
+    const bool flat = (mx - mn) == 0.0f;
+    const double r = (double)mx - (double)mn;
+    const double inv = flat ? 0.0 : 1.0 / r;
+    const double cmin = flat ? 0.0 : (Sgy - Sg) / (r * (double)nmin);
+    const double cmax = flat ? 0.0 : Sgy / (r * (double)nmax);
+    const long long r0 = (long long)blockIdx.x * a.rows_per_block;
+    const long long r1 = r0 + a.rows_per_block < a.R ? r0 + a.rows_per_block : a.R;
+    for (long long row = r0 + rr; row < r1; row += a.rpp) {
+        const long long idx = ((long long)o * a.R + row) * a.inner + col;
+        const float xv = a.x[idx];
+        double d = (double)a.g[idx] * inv;
+        if (xv == mn) d += cmin;
+        if (xv == mx) d -= cmax;
+        a.dx[idx] = flat ? 0.0f : (float)d;
+    }
+}
+
+
+}  // namespace
+
+extern "C" int nrt_conv1d_axis_f32(const float *x, const float *kernel, float *y, long long outer, int axis_len, long long inner,
+                                   int out_len, int width, int stride, int dilation, int pad_before, void *stream) {
+    if (!x || !kernel || !y || outer < 0 || axis_len < 1 || inner < 1 || out_len < 0 || width < 1 || stride < 1 || dilation < 1)
+        return NRT_ERR_INVALID_ARG;
+    if (outer == 0 || out_len == 0) return NRT_OK;
+    C1Args a;
+    a.x = x; a.k = kernel; a.y = y; a.outer = outer; a.A = axis_len; a.Aout = out_len; a.W = width; a.stride = stride;
+    a.dil = dilation; a.pad = pad_before; a.inner = inner; a.k0 = 0; a.kstep = 1;
+    return launch_conv1d(a, nrt_stream(stream));
+}
+
+extern "C" int nrt_conv1d_axis_bwd_f32(const float *grad_y, const float *kernel, float *grad_x, long long outer, int axis_len,
+                                       long long inner, int out_len, int width, int stride, int dilation, int pad_before, void *stream) {
+    if (!grad_y || !kernel || !grad_x || outer < 0 || axis_len < 1 || inner < 1 || out_len < 0 || width < 1 || stride < 1 || dilation < 1)
+        return NRT_ERR_INVALID_ARG;
+    if (outer == 0) return NRT_OK;
+    hipStream_t st = nrt_stream(stream);
+    if (stride == 1 && out_len > 0) {
+        C1Args a;
+        a.x = grad_y; a.k = kernel; a.y = grad_x; a.outer = outer; a.A = out_len; a.Aout = axis_len; a.W = width; a.stride = 1;
+        a.dil = dilation; a.pad = (width - 1) * dilation - pad_before; a.inner = inner; a.k0 = width - 1; a.kstep = -1;
+        return launch_conv1d(a, st);
+    }
+    C1BwdArgs a;
+    a.g = grad_y; a.k = kernel; a.dx = grad_x; a.outer = outer; a.inner = inner; a.A = axis_len; a.Aout = out_len; a.W = width;
+    a.stride = stride; a.dil = dilation; a.pad = pad_before;
+    int gc = stride, b = dilation % stride;
+    while (b) { const int t = gc % b; gc = b; b = t; }
+    a.tstep = stride / gc;
+    if (inner % 4 == 0 && ((((uintptr_t)grad_y | (uintptr_t)grad_x) & 15) == 0)) {
+        a.inner = inner / 4;
+        hipLaunchKernelGGL((conv1d_axis_bwd<true>), dim3(fblocks(outer * axis_len * a.inner)), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((conv1d_axis_bwd<false>), dim3(fblocks(outer * axis_len * inner)), dim3(256), 0, st, a);
+    }
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+extern "C" size_t nrt_conv1d_axis_bwd_kernel_workspace_bytes(long long outer, int out_len, long long inner, int width) {
+    if (outer < 0 || out_len < 0 || inner < 1 || width < 1) return 0;
+    const DkGeom g = dk_geometry(outer * out_len * inner, width);
+    return (size_t)g.nblocks * (size_t)g.Wp * sizeof(double);
+}
+
+extern "C" int nrt_conv1d_axis_bwd_kernel_f32(const float *x, const float *grad_y, float *grad_kernel, long long outer, int axis_len,
+                                              long long inner, int out_len, int width, int stride, int dilation, int pad_before,
+                                              void *workspace, size_t workspace_bytes, void *stream) {
+    if (!x || !grad_y || !grad_kernel || outer < 0 || axis_len < 1 || inner < 1 || out_len < 0 || width < 1 || stride < 1 || dilation < 1)
+        return NRT_ERR_INVALID_ARG;
+    if (!workspace || workspace_bytes < nrt_conv1d_axis_bwd_kernel_workspace_bytes(outer, out_len, inner, width)) return NRT_ERR_WORKSPACE;
+    if (((uintptr_t)workspace & 7) != 0) return NRT_ERR_INVALID_ARG;
+    const DkGeom g = dk_geometry(outer * out_len * inner, width);
+    DkArgs a;
+    a.x = x; a.g = grad_y; a.part = (double *)workspace; a.outer = outer; a.inner = inner; a.total = outer * out_len * inner;
+    a.per_block = g.per_block; a.A = axis_len; a.Aout = out_len; a.W = width; a.Wp = g.Wp; a.stride = stride; a.dil = dilation;
+    a.pad = pad_before;
+    hipStream_t st = nrt_stream(stream);
+    hipLaunchKernelGGL(conv1d_dk_partial, dim3((unsigned)g.nblocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(conv1d_dk_finish, dim3(1), dim3(256), 0, st, (const double *)workspace, (int)g.nblocks, g.Wp, width, grad_kernel);
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+extern "C" size_t nrt_minmax_norm_bwd_workspace_bytes(long long outer, long long reduce_len, int inner) {
+    if (outer < 1 || reduce_len < 1 || inner < 1) return 0;
+    const MbGeom g = mb_geometry(reduce_len, inner);
+    return mb_keys_bytes(outer, inner) + (size_t)outer * (size_t)g.nb * (size_t)inner * sizeof(MbPart);
+}
+
+extern "C" int nrt_minmax_norm_bwd_f32(const float *x, const float *grad_y, float *grad_x, long long outer, long long reduce_len,
+                                       int inner, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!x || !grad_y || !grad_x || outer < 0 || reduce_len < 0 || inner < 1) return NRT_ERR_INVALID_ARG;
+    if (inner > 1024 || outer > 65535) return NRT_ERR_UNSUPPORTED;
+    if (outer == 0 || reduce_len == 0) return NRT_OK;
+    if (!workspace || workspace_bytes < nrt_minmax_norm_bwd_workspace_bytes(outer, reduce_len, inner)) return NRT_ERR_WORKSPACE;
+    if (((uintptr_t)workspace & 7) != 0) return NRT_ERR_INVALID_ARG;
+    hipStream_t st = nrt_stream(stream);
+    int *keys = (int *)workspace;
+    const MbGeom g = mb_geometry(reduce_len, inner);
+    MbArgs a;
+    a.x = x; a.g = grad_y; a.dx = grad_x; a.keys = keys; a.part = (MbPart *)((char *)workspace + mb_keys_bytes(outer, inner));
+    a.R = reduce_len; a.rows_per_block = g.rows_per_block; a.inner = inner; a.ct = g.ct; a.rpp = g.rpp; a.nb = g.nb; a.nbp = 0;
+    if (inner == 1) {                                            // the extrema as the forward finds them
+        long long nb = (reduce_len + 256 * 16 - 1) / (256 * 16);
+        if (nb > MM_NB) nb = MM_NB;
+        hipLaunchKernelGGL(minmax_reduce1, dim3((unsigned)nb, (unsigned)outer), dim3(256), 0, st, x, keys, reduce_len);
+        a.nbp = (int)nb;
+    } else {
+        hipLaunchKernelGGL(minmax_init, dim3(fblocks(outer * inner)), dim3(256), 0, st, keys, outer * inner);
+        long long bx = (reduce_len * inner + 256 * 16 - 1) / (256 * 16);
+        if (bx > 2048) bx = 2048;
+        hipLaunchKernelGGL(minmax_reduce, dim3((unsigned)bx, (unsigned)outer), dim3(256), (size_t)inner * 2 * sizeof(int), st, x, keys,
+                           reduce_len, inner);
+    }
+    const dim3 grid((unsigned)g.nb, (unsigned)outer, (unsigned)g.tiles);
+    hipLaunchKernelGGL(mm_bwd_reduce, grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mm_bwd_apply, grid, dim3(256), 0, st, a);
     NRT_CHECK_LAUNCH();
     return NRT_OK;
 }

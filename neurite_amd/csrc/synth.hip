@@ -8,6 +8,8 @@
 //   labels_out   indices -> output labels (lookup) and one-hot encoding, -1 = dropped label         (:890-918)
 // Random numbers are drawn by the caller (device RNG); these kernels are deterministic functions of their inputs.
 
+#include <type_traits>
+
 #include "nrt_common.h"
 
 namespace {
@@ -126,6 +128,28 @@ __global__ __launch_bounds__(256) void axis_gather(const float *__restrict__ x, 
     }
 }
 
+// gradient of axis_gather.  The index list is non-decreasing, so the outputs that read input slice a are one run
+// [run_start[a], run_start[a + 1]): dx[o, a, i] = sum of g[o, j, i] over the run, ascending j from +0; a slice nobody read gets zeros.
+// One lane per input element (a float4 of them when VEC), consecutive lanes consecutive in memory; no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void axis_gather_bwd(const float *__restrict__ g_, const int *__restrict__ run_start, float *__restrict__ dx_,
+                                                       long long total, int A, int J, long long inner) {
+    typedef typename std::conditional<VEC, nrt_f4, float>::type T;
+    const T *g = (const T *)g_;
+    T *dx = (T *)dx_;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long i = e % inner, r = e / inner;
+        const int a = (int)(r % A);
+        const long long o = r / A;
+        int j0 = run_start[a], j1 = run_start[a + 1];
+        if (j0 < 0) j0 = 0;
+        if (j1 > J) j1 = J;
+        T acc = T{};
+        for (int j = j0; j < j1; ++j) acc = acc + g[(o * J + j) * inner + i];
+        dx[e] = acc;
+    }
+}
+
 // y[b, v, c] = x[b, v, c] + sd[b * sdb + c * sdc] * noise[b, v, c]   (GaussianNoise, layers.py:2305-2403)
 __global__ __launch_bounds__(256) void noise_add(const float *__restrict__ x, const float *__restrict__ noise, const float *__restrict__ sd,
                                                  float *__restrict__ y, long long V, int C, int sdb, int sdc) {
@@ -218,6 +242,23 @@ extern "C" int nrt_synth_axis_gather_f32(const float *x, const int *index, float
     const long long total = outer * out_len * inner;
     if (total == 0) return NRT_OK;
     hipLaunchKernelGGL(axis_gather, dim3(sblocks(total)), dim3(256), 0, nrt_stream(stream), x, index, y, total, axis_len, out_len, inner);
+    NRT_CHECK_LAUNCH();
+    return NRT_OK;
+}
+
+extern "C" int nrt_synth_axis_gather_bwd_f32(const float *grad_y, const int *run_start, float *grad_x, long long outer, int axis_len,
+                                             int out_len, long long inner, void *stream) {
+    if (!grad_y || !run_start || !grad_x || outer < 0 || axis_len < 1 || out_len < 0 || inner < 1) return NRT_ERR_INVALID_ARG;
+    if (outer == 0) return NRT_OK;
+    if (inner % 4 == 0 && ((((uintptr_t)grad_y | (uintptr_t)grad_x) & 15) == 0)) {
+        const long long total = outer * axis_len * (inner / 4);
+        hipLaunchKernelGGL((axis_gather_bwd<true>), dim3(sblocks(total)), dim3(256), 0, nrt_stream(stream), grad_y, run_start, grad_x, total,
+                           axis_len, out_len, inner / 4);
+    } else {
+        const long long total = outer * axis_len * inner;
+        hipLaunchKernelGGL((axis_gather_bwd<false>), dim3(sblocks(total)), dim3(256), 0, nrt_stream(stream), grad_y, run_start, grad_x, total,
+                           axis_len, out_len, inner);
+    }
     NRT_CHECK_LAUNCH();
     return NRT_OK;
 }

@@ -447,7 +447,8 @@ class GaussianBlur(_Layer):
     """
     Blur a tensor [B, *S, C] by convolving it with a Gaussian kernel, isotropic or anisotropic, randomised or not
     (neurite/tf/layers.py:251-364): `utils.gaussian_kernel(separate=True)` + `utils.separable_conv` -- one HIP pass per
-    spatial axis, no transposes.
+    spatial axis, no transposes.  Differentiable with respect to the input (float32, once) through `utils.separable_conv`; the taps
+    are host-built constants, so there is no gradient with respect to sigma.
     """
 
     def __init__(self, sigma=None, level=None, random=False, min_sigma=0, isotropic=False, seed=None, **kwargs):
@@ -520,7 +521,8 @@ class GaussianBlur(_Layer):
 class Subsample(_Layer):
     """
     Symmetrically subsample a tensor [B, *S, C] by a random stride along one random spatial axis with nearest-neighbour
-    interpolation and (by default) up-sample it again, to create thick slices (layers.py:367-443).
+    interpolation and (by default) up-sample it again, to create thick slices (layers.py:367-443).  Differentiable with respect to
+    the input (float32, once) through `utils.subsample_axis`.
     """
 
     def __init__(self, stride_min=1, stride_max=8, axes=None, prob=1, upsample=True, seed=None, **kwargs):

@@ -530,7 +530,8 @@ def gaussian_kernel(sigma, windowsize=None, indexing='ij', separate=False, rando
     """
     N-dimensional Gaussian kernel (utils.py:581-662), or a list of N 1-D kernels with separate=True.  Host-side: the
     kernels are a few dozen numbers.  random=True draws each SD uniformly from [min_sigma, sigma) with torch's RNG
-    (the reference uses tf.random.uniform: same distribution, different stream).
+    (the reference uses tf.random.uniform: same distribution, different stream).  sigma is a host number: the gradient with
+    respect to sigma is out of scope (the taps it returns are constants of any graph they enter).
     """
     if not dtype.is_floating_point:
         raise AssertionError(f'{dtype} is not a real floating-point type')
@@ -570,21 +571,23 @@ def gaussian_kernel(sigma, windowsize=None, indexing='ij', separate=False, rando
     return kernel if len(kernel) > 1 else kernel[0]
 
 
-def _conv1d_axis(x, k, ax, padding, stride, dilation):
-    """one separable pass along tensor axis `ax` of the contiguous float32 tensor x (csrc/filter.hip)."""
-    dev = x.device
-    n, w = x.shape[ax], k.numel()
+def _conv1d_geometry(n, w, padding, stride, dilation):
+    """(outputs, padding in front) of one pass over an axis of n samples by the TF rules"""
     ke = (w - 1) * dilation + 1
     if padding.upper() == 'SAME':
         o = -(-n // stride)
-        before = max((o - 1) * stride + ke - n, 0) // 2
-    elif padding.upper() == 'VALID':
+        return o, max((o - 1) * stride + ke - n, 0) // 2
+    if padding.upper() == 'VALID':
         o = (n - ke) // stride + 1
-        before = 0
         if o < 1:
             raise ValueError('Negative dimension size caused by a VALID convolution of width %d along a length-%d axis' % (ke, n))
-    else:
-        raise ValueError('padding must be "SAME" or "VALID"')
+        return o, 0
+    raise ValueError('padding must be "SAME" or "VALID"')
+
+
+def _conv1d_launch(x, k, ax, o, before, stride, dilation):
+    dev = x.device
+    n, w = x.shape[ax], k.numel()
     outer = int(np.prod(x.shape[:ax])) if ax else 1
     inner = int(np.prod(x.shape[ax + 1:]))
     y = torch.empty(tuple(x.shape[:ax]) + (o,) + tuple(x.shape[ax + 1:]), dtype=torch.float32, device=dev)
@@ -594,10 +597,62 @@ def _conv1d_axis(x, k, ax, padding, stride, dilation):
     return y
 
 
+class _Conv1dAxisFn(torch.autograd.Function):
+    """
+    One separable pass with the hand-written backward of csrc/filter.hip: the input gradient (stride 1: a forward pass over the
+    incoming gradient with the taps reversed; stride > 1: a gather kernel) and, only when the taps require grad, the tap gradient.
+    x is saved only for the tap gradient, the taps only for the input gradient.
+    """
+
+    @staticmethod
+    def forward(ctx, x, k, ax, o, before, stride, dilation):
+        y = _conv1d_launch(x, k, ax, o, before, stride, dilation)
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, k if ctx.needs_input_grad[0] else None)
+        ctx.geom = (tuple(x.shape), ax, o, before, stride, dilation, k.numel())
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, k = ctx.saved_tensors
+        shape, ax, o, before, stride, dilation, w = ctx.geom
+        dev = grad_y.device
+        g = grad_y.contiguous()
+        if g.dtype != torch.float32:
+            raise NotImplementedError('separable_conv backward: float32 gradients, got %s' % g.dtype)
+        n = shape[ax]
+        outer = int(np.prod(shape[:ax])) if ax else 1
+        inner = int(np.prod(shape[ax + 1:]))
+        gx = gk = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty(shape, dtype=torch.float32, device=dev)
+            if gx.numel():
+                _lib.call(dev, 'nrt_conv1d_axis_bwd_f32', _lib.ptr(g), _lib.ptr(k), _lib.ptr(gx), outer, n, inner, o, w, stride, dilation,
+                          before)
+        if ctx.needs_input_grad[1]:
+            gk = torch.empty((w,), dtype=torch.float32, device=dev)
+            nws = int(_lib.lib().nrt_conv1d_axis_bwd_kernel_workspace_bytes(outer, o, inner, w))
+            ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+            _lib.call(dev, 'nrt_conv1d_axis_bwd_kernel_f32', _lib.ptr(x), _lib.ptr(g), _lib.ptr(gk), outer, n, inner, o, w, stride,
+                      dilation, before, _lib.ptr(ws), nws)
+        return gx, gk, None, None, None, None, None
+
+
+def _conv1d_axis(x, k, ax, padding, stride, dilation):
+    """one separable pass along tensor axis `ax` of the contiguous float32 tensor x (csrc/filter.hip); recorded for autograd only
+    when grad is enabled and x or the taps require it -- otherwise the launch and the output are those of the forward-only op"""
+    o, before = _conv1d_geometry(x.shape[ax], k.numel(), padding, stride, dilation)
+    if torch.is_grad_enabled() and (x.requires_grad or k.requires_grad):
+        return _Conv1dAxisFn.apply(x, k, ax, o, before, int(stride), int(dilation))
+    return _conv1d_launch(x, k, ax, o, before, stride, dilation)
+
+
 def separable_conv(x, kernels, axis=None, batched=False, padding='SAME', strides=None, dilations=None):
     """
     Apply 1-D kernels along spatial axes of a tensor with a trailing feature dimension, the same filters across
     features (utils.py:665-751).  One kernel pass per axis on the tensor as it lies in memory -- no transposes.
+    Differentiable (float32, once) with respect to x and to tap tensors that require grad; taps that already live on x's device are
+    used where they are.
     """
     dev = _lib.require_device(x)
     if x.dtype != torch.float32:
@@ -625,18 +680,54 @@ def separable_conv(x, kernels, axis=None, batched=False, padding='SAME', strides
     assert len(kernels) == len(axis), 'number of kernels and axes differ'
     x = x.contiguous()
     for ax, k, s, d in zip(axis, kernels, strides, dilations):
-        k = torch.as_tensor(k, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        if isinstance(k, torch.Tensor):                          # keeps the graph of a tap tensor; no copy if it is in place already
+            k = k.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        else:
+            k = torch.as_tensor(k, dtype=torch.float32).reshape(-1).to(dev).contiguous()
         x = _conv1d_axis(x, k, ax + 1, padding, int(s), int(d))
     return x if batched else x[0]
+
+
+def _minmax_launch(x, outer, red, inner):
+    dev = x.device
+    y = torch.empty_like(x)
+    nws = _lib.lib().nrt_minmax_workspace_bytes(outer, inner)
+    ws = torch.empty((max(int(nws), 16),), dtype=torch.uint8, device=dev)
+    _lib.call(dev, 'nrt_minmax_norm_f32', _lib.ptr(x), _lib.ptr(y), outer, red, inner, _lib.ptr(ws), nws)
+    return y
+
+
+class _MinmaxNormFn(torch.autograd.Function):
+    """minmax_norm with the backward of csrc/filter.hip (ties of the extrema share their gradient evenly; a constant group gets 0)."""
+
+    @staticmethod
+    def forward(ctx, x, outer, red, inner):
+        ctx.save_for_backward(x)
+        ctx.geom = (outer, red, inner)
+        return _minmax_launch(x, outer, red, inner)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, = ctx.saved_tensors
+        outer, red, inner = ctx.geom
+        dev = x.device
+        g = grad_y.contiguous()
+        if g.dtype != torch.float32:
+            raise NotImplementedError('minmax_norm backward: float32 gradients, got %s' % g.dtype)
+        gx = torch.empty_like(x)
+        nws = int(_lib.lib().nrt_minmax_norm_bwd_workspace_bytes(outer, red, inner))
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+        _lib.call(dev, 'nrt_minmax_norm_bwd_f32', _lib.ptr(x), _lib.ptr(g), _lib.ptr(gx), outer, red, inner, _lib.ptr(ws), nws)
+        return gx, None, None, None
 
 
 def minmax_norm(x, axis=None):
     """
     Min-max normalise with a safe division (utils.py:953-968).  axis: dimensions to reduce (None = all); they must
-    form one contiguous run (e.g. all, all but the batch, all spatial axes of a channels-last batch).
+    form one contiguous run (e.g. all, all but the batch, all spatial axes of a channels-last batch).  Differentiable (float32, once).
     """
-    lib = _lib.lib()
-    dev = _lib.require_device(x)
+    _lib.require_device(x)
     if x.dtype != torch.float32:
         raise NotImplementedError('minmax_norm: float32 tensors, got %s' % x.dtype)
     nd = x.dim()
@@ -647,13 +738,11 @@ def minmax_norm(x, axis=None):
     outer = int(np.prod(x.shape[:axes[0]])) if axes[0] else 1
     red = int(np.prod(x.shape[axes[0]:axes[-1] + 1]))
     inner = int(np.prod(x.shape[axes[-1] + 1:]))
-    y = torch.empty_like(x)
     if x.numel() == 0:
-        return y
-    nws = lib.nrt_minmax_workspace_bytes(outer, inner)
-    ws = torch.empty((max(int(nws), 16),), dtype=torch.uint8, device=dev)
-    _lib.call(dev, 'nrt_minmax_norm_f32', _lib.ptr(x), _lib.ptr(y), outer, red, inner, _lib.ptr(ws), nws)
-    return y
+        return torch.empty_like(x)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _MinmaxNormFn.apply(x, outer, red, inner)
+    return _minmax_launch(x, outer, red, inner)
 
 
 def _device_minmax(x):
@@ -1066,16 +1155,51 @@ def draw_swap_matrix(ndims, last_row=True, dtype=torch.float32, seed=None):
     return out
 
 
-def _axis_gather(x, index, ax):
-    """y = tf.gather(x, index, axis=ax) of a float32 device tensor (csrc/synth.hip)."""
-    dev = _lib.require_device(x)
-    x = x.contiguous()
+def _axis_gather_launch(x, index, ax):
+    dev = x.device
     idx = torch.as_tensor(np.asarray(index, dtype=np.int32)).to(dev)
     outer = int(np.prod(x.shape[:ax])) if ax else 1
     inner = int(np.prod(x.shape[ax + 1:]))
     y = torch.empty(tuple(x.shape[:ax]) + (idx.numel(),) + tuple(x.shape[ax + 1:]), dtype=torch.float32, device=dev)
     _lib.call(dev, 'nrt_synth_axis_gather_f32', _lib.ptr(x), _lib.ptr(idx), _lib.ptr(y), outer, x.shape[ax], idx.numel(), inner)
     return y
+
+
+class _AxisGatherFn(torch.autograd.Function):
+    """tf.gather along one axis by a non-decreasing host-built index list; the gradient is a segmented sum (csrc/synth.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, index, ax):
+        index = np.asarray(index, dtype=np.int32)
+        assert (np.diff(index) >= 0).all(), 'the index list must be non-decreasing'
+        ctx.geom = (tuple(x.shape), ax, index)
+        return _axis_gather_launch(x, index, ax)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        shape, ax, index = ctx.geom
+        dev = grad_y.device
+        g = grad_y.contiguous()
+        if g.dtype != torch.float32:
+            raise NotImplementedError('subsample_axis backward: float32 gradients, got %s' % g.dtype)
+        run_start = np.searchsorted(index, np.arange(shape[ax] + 1), side='left').astype(np.int32)
+        runs = torch.as_tensor(run_start).to(dev)
+        outer = int(np.prod(shape[:ax])) if ax else 1
+        inner = int(np.prod(shape[ax + 1:]))
+        gx = torch.empty(shape, dtype=torch.float32, device=dev)
+        if gx.numel():
+            _lib.call(dev, 'nrt_synth_axis_gather_bwd_f32', _lib.ptr(g), _lib.ptr(runs), _lib.ptr(gx), outer, shape[ax], index.size, inner)
+        return gx, None, None
+
+
+def _axis_gather(x, index, ax):
+    """y = tf.gather(x, index, axis=ax) of a float32 device tensor (csrc/synth.hip); recorded for autograd when x requires grad"""
+    _lib.require_device(x)
+    x = x.contiguous()
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _AxisGatherFn.apply(x, index, ax)
+    return _axis_gather_launch(x, index, ax)
 
 
 def subsample_axis_indices(width, thick):
@@ -1107,7 +1231,8 @@ def _subsample_draws(num_axes, stride_min, stride_max, prob, seed, draws=None):
 def subsample_axis(x, stride_min=1, stride_max=8, axes=None, prob=1, upsample=True, seed=None, _draws=None):
     """
     Symmetrically subsample a tensor by a random factor (stride) along one randomly drawn axis with nearest-neighbour
-    interpolation and optionally up-sample it again (utils.py:754-826).  float32 device tensors.
+    interpolation and optionally up-sample it again (utils.py:754-826).  float32 device tensors.  Differentiable (once) with
+    respect to x.
     """
     if x.dtype != torch.float32:
         raise NotImplementedError('subsample_axis: float32 tensors, got %s' % x.dtype)
