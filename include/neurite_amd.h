@@ -1014,6 +1014,39 @@ int nrt_affine_warp_bwd_f32(const float *vol, const float *matrix, const float *
                             const int *vol_shape, const int *out_shape, int channels, int batch, int matrix_batch, int shift_center,
                             int method, int has_fill, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The Jacobian determinant of a displacement field and its gradient (csrc/jacobian.hip): vxm.py.utils.jacobian_determinant.
+ * voxelmorph is not in the reference tree: the semantics are restated, not pinned; the oracle is np.gradient.
+ * float32, channels-last disp [batch, *shape, nd]: `shape` holds exactly nd extents, nd 2 or 3, 'ij' coordinates.
+ *   nrt_jacdet_f32      G[a][c] = the np.gradient difference of disp[.., c] along spatial axis a: (f[i + 1] - f[i - 1]) * 0.5 inside,
+ *                       f[1] - f[0] and f[n - 1] - f[n - 2] at the two ends; J[a][c] = G[a][c] + (a == c);
+ *                       3-D det = J0[0] (J1[1] J2[2] - J1[2] J2[1]) - J0[1] (J1[0] J2[2] - J1[2] J2[0]) + J0[2] (J1[0] J2[1] - J1[1] J2[0]),
+ *                       2-D det = J0[0] J1[1] - J1[0] J0[1]; one float32 rounding per operation, in this order.  One pass over disp
+ *                       writes any of (each may be NULL, not all three):
+ *                         det   [batch, V] float32, the map;
+ *                         stats [batch, 5] 8-byte slots (8-byte aligned): the count of det <= 0 as int64, then min, max, sum det and
+ *                               sum det^2 as float64 (min and max are the float32 values; the sums are formed in float64);
+ *                         loss  [batch] float32 = float32(sum max(0, -det) / V), the sum in float64.
+ *                       stats and loss need the workspace (a tiny second launch adds the per-block rows in block order); the map is
+ *                       not needed for them.
+ *   nrt_jacdet_bwd_f32  gdisp (the layout of disp) = sum_a sum_p coef_a(p, q) w[p] cof[p][a][c]: cof the cofactor matrix of J at p,
+ *                       coef the stencil weight with which q enters G[a] at p (+-1/2 from an interior p, +-1 from p = 0 and p = n - 1),
+ *                       w[p] = gdet[p] (the upstream gradient of det, [batch, V]) and / or -gloss[b] / V [det[p] < 0] (that of loss,
+ *                       [batch]; the sub-gradient at det == 0 is 0): at least one.  One gather pass that rebuilds J from disp: nothing of
+ *                       the forward is kept, no workspace.
+ *   nrt_jacdet_workspace_bytes   what the forward needs for stats or loss; 0 for a geometry the calls refuse.
+ * No atomics, no host synchronisation (both calls capture into a graph), no memset; every sum has a fixed partition and order: run-to-run
+ * bit-identical.  Base pointers and the workspace need 4-byte alignment only.  Checked before any launch: NRT_ERR_INVALID_ARG for a NULL
+ * disp, shape or gdisp, no output or no upstream gradient at all, batch < 1, an extent < 2, a stats pointer off 8 bytes;
+ * NRT_ERR_UNSUPPORTED for nd outside {2, 3}, 2^31 or more elements in a tensor and batch > 65535; NRT_ERR_WORKSPACE for a missing or
+ * short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_jacdet_workspace_bytes(int batch, const int *shape, int nd);
+int nrt_jacdet_f32(const float *disp, int batch, const int *shape, int nd, float *det, void *stats, float *loss, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int nrt_jacdet_bwd_f32(const float *disp, const float *gdet, const float *gloss, int batch, const int *shape, int nd, float *gdisp,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,9 @@ _SIGNATURES = {
     'nrt_affine_warp_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
     'nrt_affine_warp_f32': (_i, [_vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _i, _i, _f, _vp]),
     'nrt_affine_warp_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _i, _ip, _ip, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'nrt_jacdet_workspace_bytes': (_sz, [_i, _ip, _i]),
+    'nrt_jacdet_f32': (_i, [_vp, _i, _ip, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_jacdet_bwd_f32': (_i, [_vp, _vp, _vp, _i, _ip, _i, _vp, _vp]),
 }
 
 

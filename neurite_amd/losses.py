@@ -1,17 +1,18 @@
 """
 neurite_amd.losses -- neurite/tf/losses.py:46-205 for the hot path: the metrics classes with
 `loss` (negative Dice [B, L] / the CCE scalar) and `mean_loss` (negative mean Dice); and the two losses of an unsupervised
-VoxelMorph registration run, `NCC` and `Grad` (vxm.losses; restated), on csrc/vxmloss.hip.
+VoxelMorph registration run, `NCC` and `Grad` (vxm.losses; restated), on csrc/vxmloss.hip; and `NegJacobian`, the
+folding penalty on the Jacobian determinant of a field (an extension), on csrc/jacobian.hip.
 """
 
 import numpy as np
 import torch
 
-from . import _lib, metrics
+from . import _lib, metrics, utils
 from .deferred import materialize
 
 __all__ = ['Dice', 'SoftDice', 'HardDice', 'CategoricalCrossentropy', 'WeightedCategoricalCrossentropy',
-           'MeanSquaredErrorProb', 'multiple_losses_decorator', 'NCC', 'Grad']
+           'MeanSquaredErrorProb', 'multiple_losses_decorator', 'NCC', 'Grad', 'NegJacobian']
 
 
 class _DiceLossMixin:
@@ -280,3 +281,20 @@ class Grad:
         _lib.require_device(y)
         mult = 1.0 if self.loss_mult is None else float(self.loss_mult)        # (times 1 changes no bit)
         return _GradLossFn.apply(y.contiguous(), 1 if self.penalty == 'l1' else 2, mult)
+
+
+class NegJacobian:
+    """
+    Folding penalty on a displacement field: mean over each batch entry of max(0, -det), det the Jacobian determinant of
+    utils.jacobian_determinant (csrc/jacobian.hip), times loss_mult if given.  [B, *S, D] (or [*S, D], a batch of one) float32,
+    D = len(S) in {2, 3} -> [B].  An extension: VoxelMorph has the determinant (restated), not this penalty.
+    Differentiable in y_pred (the sub-gradient at det == 0 is 0); one pass each way that writes no map; captures into a graph.
+    """
+
+    def __init__(self, loss_mult=None):
+        self.loss_mult = loss_mult
+
+    def loss(self, _, y_pred):
+        disp, _ = utils._jacdet_checked(y_pred, 'NegJacobian')
+        out = utils._JacDetFn.apply(disp, True)
+        return out if self.loss_mult is None else out * float(self.loss_mult)

@@ -10,6 +10,7 @@ reference.  All voxel-sized work runs in csrc/dice.hip and csrc/cce.hip through 
 what remains here is argument handling and arithmetic on [B, L]-sized results.
 """
 
+import collections
 import threading
 import warnings
 
@@ -21,7 +22,8 @@ from . import utils
 from .errors import InvalidArgumentError
 
 __all__ = ['Dice', 'SoftDice', 'HardDice', 'CategoricalCrossentropy', 'WeightedCategoricalCrossentropy',
-           'dice_partial_sums', 'MutualInformation', 'MeanSquaredErrorProb', 'JointSegLoss']
+           'dice_partial_sums', 'MutualInformation', 'MeanSquaredErrorProb', 'JointSegLoss',
+           'JacobianDeterminant', 'JacobianStats']
 
 _INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64, torch.bool)
 
@@ -1033,3 +1035,35 @@ class MutualInformation:
             raise InvalidArgumentError('')
         joint, sx, sy = _MiMapsFn.apply(xf, yf)
         return _mi_from_joint(joint, sx, sy)
+
+
+JacobianStats = collections.namedtuple('JacobianStats', ['folded_voxels', 'folded_fraction', 'min', 'max', 'mean', 'std'])
+
+
+class JacobianDeterminant:
+    """
+    The Jacobian determinant of a displacement field as a validation metric (csrc/jacobian.hip): what a registration run takes from
+    vxm.py.utils.jacobian_determinant (restated) without the field or the map leaving the device.  Fields are
+    [B, *S, D] or [*S, D] (a batch of one), D = len(S) in {2, 3}, float32; see utils.jacobian_determinant.  Forward only.
+    """
+
+    def det(self, disp):
+        """the map [B, *S] (or [*S]): utils.jacobian_determinant without a gradient"""
+        with torch.no_grad():
+            return utils.jacobian_determinant(disp)
+
+    def stats(self, disp):
+        """JacobianStats of [B] tensors in one pass that writes no map: folded_voxels (int64, the count of det <= 0), folded_fraction,
+        min, max (the float32 extremes, widened), mean and std (population), the last four in float64 from float64 sums."""
+        disp, _ = utils._jacdet_checked(disp, 'JacobianDeterminant')
+        _, rows, _ = utils._jacdet_launch(disp.detach(), want_stats=True)
+        # (a tensor, not a Python number: torch divides by a scalar through its reciprocal, which is an ulp off the IEEE quotient)
+        V = torch.full((disp.shape[0],), float(disp[0].numel() // disp.shape[-1]), dtype=torch.float64, device=disp.device)
+        count = rows[:, 0].contiguous().view(torch.int64)
+        mean = rows[:, 3] / V
+        var = (rows[:, 4] / V - mean * mean).clamp_min(0.0)
+        return JacobianStats(count, count.to(torch.float64) / V, rows[:, 1], rows[:, 2], mean, var.sqrt())
+
+    def folded(self, disp):
+        """the share of voxels with det <= 0, [B] float64"""
+        return self.stats(disp).folded_fraction

@@ -5,7 +5,7 @@ Mirrors the names, arguments, defaults and error behaviour of neurite/tf/utils/u
 interpn (:73), resize/zoom (:223,:265), volshape_to_ndgrid (:333), volshape_to_meshgrid (:356),
 ndgrid (:382), meshgrid (:398), sub2ind2d (:1068), prod_n (:1085), batch_channel_flatten (:1175),
 flatten_axes (:1195), barycenter (:512); plus voxelmorph's transform()/affine_to_dense_shift, which the reference
-calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159).
+calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159), and voxelmorph's jacobian_determinant (restated: DESIGN 4.6i).
 
 Tensors are torch tensors on a ROCm device in the reference's channels-last layout.  All sampling
 work is done by the HIP kernels in csrc/interpn.hip through the C ABI; nothing here falls back
@@ -18,9 +18,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .deferred import materialize
 
 __all__ = ['interpn', 'resize', 'zoom', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
-           'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter',
+           'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter', 'jacobian_determinant',
            'rescale_dense_transform', 'rescale_affine', 'is_affine_shape', 'validate_affine_shape', 'make_square_affine', 'volshape_to_ndgrid',
            'volshape_to_meshgrid', 'ndgrid', 'meshgrid', 'sub2ind2d', 'prod_n', 'batch_channel_flatten',
            'flatten_batch_channel', 'flatten_axes']
@@ -936,6 +937,96 @@ def barycenter(x, axes=None, normalize=False, shift_center=False, dtype=torch.fl
     x3 = x.contiguous().view((outer,) + red + (inner,))
     y = _BarycenterFn.apply(x3, red, (int(bool(normalize)), int(bool(shift_center)))).view(out_shape)
     return y if dtype == torch.float32 else y.to(dtype)
+
+
+# --------------------------------------------------------------------------------------
+# the Jacobian determinant of a displacement field (csrc/jacobian.hip)
+# --------------------------------------------------------------------------------------
+
+def _jacdet_checked(disp, what):
+    """the host-side checks of a field, before its device is looked at: returns (disp [B, *S, D] contiguous, batched)"""
+    if not isinstance(disp, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(disp).__name__))
+    disp = materialize(disp)
+    if disp.dim() < 2:
+        raise ValueError('%s: expected [*spatial, D] or [batch, *spatial, D], got shape %s' % (what, tuple(disp.shape)))
+    D = int(disp.shape[-1])
+    batched = disp.dim() != D + 1                       # the rank decides: [*S, D] has D + 1 axes
+    nd = disp.dim() - (2 if batched else 1)
+    if nd not in (2, 3):
+        raise NotImplementedError('%s: 2 or 3 spatial axes, got shape %s' % (what, tuple(disp.shape)))
+    if D != nd:
+        raise ValueError('%s: %d spatial axes need %d channels, got shape %s' % (what, nd, nd, tuple(disp.shape)))
+    if disp.dtype != torch.float32:
+        raise NotImplementedError('%s: float32 only, got %s' % (what, disp.dtype))
+    if not batched:
+        disp = disp.unsqueeze(0)
+    if disp.shape[0] < 1 or any(int(v) < 2 for v in disp.shape[1:-1]):
+        raise ValueError('%s: every spatial extent must be at least 2 (and the batch at least 1), got shape %s' % (what, tuple(disp.shape)))
+    if disp.shape[0] > 65535 or disp.numel() >= 2 ** 31:
+        raise NotImplementedError('%s: up to 65535 batch entries and fewer than 2^31 elements, got shape %s' % (what, tuple(disp.shape)))
+    _lib.require_device(disp)
+    return disp.contiguous(), batched
+
+
+def _jacdet_launch(disp, want_det=False, want_stats=False, want_loss=False):
+    """one pass of nrt_jacdet_f32 over disp [B, *S, D] (checked, contiguous): (det [B, *S] | None, stats [B, 5] float64 | None,
+    loss [B] | None).  Slot 0 of a stats row holds an int64."""
+    dev = disp.device
+    batch, shape = int(disp.shape[0]), [int(v) for v in disp.shape[1:-1]]
+    cshape = _lib.ints(shape)
+    det = torch.empty(tuple(disp.shape[:-1]), dtype=torch.float32, device=dev) if want_det else None
+    stats = torch.empty((batch, 5), dtype=torch.float64, device=dev) if want_stats else None
+    loss = torch.empty((batch,), dtype=torch.float32, device=dev) if want_loss else None
+    ws, nws = None, 0
+    if want_stats or want_loss:
+        nws = int(_lib.lib().nrt_jacdet_workspace_bytes(batch, cshape, len(shape)))
+        ws = _lib.workspace(dev, max(nws, 16))
+    _lib.call(dev, 'nrt_jacdet_f32', _lib.ptr(disp), batch, cshape, len(shape), _lib.ptr(det), _lib.ptr(stats), _lib.ptr(loss),
+              _lib.ptr(ws), nws)
+    return det, stats, loss
+
+
+class _JacDetFn(torch.autograd.Function):
+    """disp [B, *S, D] float32 contiguous -> the map [B, *S] (as_loss False) or mean(max(0, -det)) [B] (as_loss True).  The backward
+    keeps disp only: one gather pass rebuilds the Jacobian."""
+
+    @staticmethod
+    def forward(ctx, disp, as_loss):
+        det, _, loss = _jacdet_launch(disp, want_det=not as_loss, want_loss=as_loss)
+        ctx.save_for_backward(disp)
+        ctx.as_loss = as_loss
+        return loss if as_loss else det
+
+    @staticmethod
+    def backward(ctx, g):
+        disp, = ctx.saved_tensors
+        dev = disp.device
+        g = g.to(torch.float32).contiguous()
+        gdisp = torch.empty_like(disp)
+        shape = [int(v) for v in disp.shape[1:-1]]
+        _lib.call(dev, 'nrt_jacdet_bwd_f32', _lib.ptr(disp), None if ctx.as_loss else _lib.ptr(g), _lib.ptr(g) if ctx.as_loss else None,
+                  int(disp.shape[0]), _lib.ints(shape), len(shape), _lib.ptr(gdisp))
+        return gdisp, None
+
+
+def jacobian_determinant(disp):
+    """
+    The Jacobian determinant of the transform x -> x + disp(x) at every voxel: vxm.py.utils.jacobian_determinant, restated (voxelmorph
+    is not in the reference tree) and computed on the device (csrc/jacobian.hip).
+
+    disp: [B, *S, D] or, as the VoxelMorph function takes it, [*S, D]; D = len(S) in {2, 3}, float32, 'ij' coordinates.  The rank
+          decides: a tensor of D + 1 axes (D = shape[-1]) is unbatched.  A non-contiguous field is made contiguous.
+
+    Returns the map [B, *S] (or [*S]) in float32: the derivatives are np.gradient's (central differences inside, one-sided first-order
+    differences at both ends of an axis), so every spatial extent must be at least 2 (ValueError, as np.gradient raises).  VoxelMorph's
+    own result is float64 (float32 + an integer grid promotes); this one differs from it by at most 12 * 2^-24 * sum over the
+    permutations pi of prod_a (|G[a][pi(a)]| + delta).  Differentiable in disp; nothing travels to the host, so forward and backward
+    capture into a graph.
+    """
+    disp, batched = _jacdet_checked(disp, 'jacobian_determinant')
+    det = _JacDetFn.apply(disp, False)
+    return det if batched else det[0]
 
 
 # --------------------------------------------------------------------------------------
