@@ -1047,6 +1047,51 @@ int nrt_jacdet_f32(const float *disp, int batch, const int *shape, int nd, float
 int nrt_jacdet_bwd_f32(const float *disp, const float *gdet, const float *gloss, int batch, const int *shape, int nd, float *gdisp,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact Euclidean distance transforms and surface-distance reductions (csrc/edt.hip).  They replace a copy of every
+ * volume to the host, scipy.ndimage.distance_transform_edt there (what VoxelMorph's dist_trf / signed_dist_trf call; voxelmorph is not
+ * in the reference tree: restated, not pinned; the oracle is the definition, brute force) and a copy back.
+ * out [batch, *shape, channels] float32, `shape` holds nd extents (2 or 3), each at most 1024.  The feature set comes from exactly one of
+ *   mask   [batch, *shape] uint8: nonzero voxels (nlabels 1, labels NULL, channels 1), or
+ *   ids    [batch, *shape] int32 with labels [nlabels] int32 on the device: channel l holds the transform of ids == labels[l]
+ *          (channels = nlabels); with NRT_EDT_ANY_OF the set is "ids in labels" and channels = 1.
+ * flags: NRT_EDT_SURFACE  (ids only) the features are the set's voxels with a face neighbour (2 nd of them) outside the set, the
+ *                         outside of the volume counting as outside the set: m & ~binary_erosion(m), border_value 0;
+ *        NRT_EDT_INVERT   the complement of the feature set;
+ *        NRT_EDT_SQUARED  squared distances (no root);
+ *        NRT_EDT_SIGNED   +d(p, set) outside the set, -d(p, complement) inside it (VoxelMorph's signed_dist_trf; with SQUARED the
+ *                         squares carry the sign): two transforms, the first kept in `workspace` (one float volume of out's size,
+ *                         nrt_edt_workspace_bytes); not with SURFACE.
+ * sampling: NULL (unit voxels) or nd voxel sizes ON THE HOST, finite and positive.
+ *   nrt_edt_f32   out = min over the feature voxels q of sqrt(sum_a (s_a (p_a - q_a))^2), 0 on the set, by one pass per axis on out in
+ *                 place: f[i] = min_j fl(g[j] + fl(fl(s |i - j|)^2)), float32, no fused multiply-add, then the correctly rounded root.
+ *                 At unit spacing every intermediate is an integer below 2^24: the squares are exact and the result is the correctly
+ *                 rounded root of the exact squared distance.  An empty feature set gives +inf everywhere (SIGNED of a full set: -inf);
+ *                 scipy returns arbitrary finite values there.
+ *   nrt_surface_stats_f32   t [batch, *shape] int32, d2 [batch, *shape, nlabels] (a SQUARED transform, from the other map's surfaces):
+ *                 over the surface voxels (as above) of label l in entry b, stats[b][l] = three 8-byte slots (8-byte aligned): their
+ *                 count (int64), max d2 and sum sqrt(d2) (float64; the root is the correctly rounded float32 one, the sum is formed in
+ *                 float64 from per-block partials added in block order; max is -inf where the count is 0).  hist, if given: [batch, nlabels, nbins] uint32, bin (int) d2 is
+ *                 incremented for every such voxel with 0 <= d2 < nbins (the caller zeroes it, and may run both directions into one).
+ * No float atomics (the histogram's integer adds commute), no host synchronisation (the calls capture into a graph), no allocation:
+ * run-to-run bit-identical.  Pointers need their type's alignment only.  Checked before any launch: NRT_ERR_INVALID_ARG for a NULL out,
+ * t, labels (with ids), d2, stats or shape, both or neither of mask and ids, mask with labels / nlabels != 1 / SURFACE / ANY_OF, SURFACE
+ * with SIGNED, an unknown flag, batch or an extent < 1, a sampling value that is not finite and positive, hist with nbins < 1;
+ * NRT_ERR_UNSUPPORTED for nd outside {2, 3}, an extent above 1024, nlabels outside 1 .. 256, batch > 65535, 2^31 or more elements in
+ * out (or in hist; nbins above 2^24); NRT_ERR_WORKSPACE for a missing or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define NRT_EDT_SURFACE 1
+#define NRT_EDT_INVERT 2
+#define NRT_EDT_SIGNED 4
+#define NRT_EDT_SQUARED 8
+#define NRT_EDT_ANY_OF 16
+size_t nrt_edt_workspace_bytes(int batch, const int *shape, int nd, int channels);
+int nrt_edt_f32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
+                const float *sampling, int flags, float *out, void *workspace, size_t workspace_bytes, void *stream);
+size_t nrt_surface_stats_workspace_bytes(int batch, const int *shape, int nd, int nlabels);
+int nrt_surface_stats_f32(const int *t, const int *labels, int nlabels, const float *d2, int batch, const int *shape, int nd,
+                          void *stats, unsigned *hist, long long nbins, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,11 +22,13 @@ LOC_ABSOLUTE, LOC_SHIFT, LOC_LINSPACE = 0, 1, 2
 INTERP_LINEAR, INTERP_NEAREST = 0, 1
 DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32 = 0, 1, 2, 3, 4
 SEG_WANT_DICE, SEG_WANT_CCE = 1, 2
+EDT_SURFACE, EDT_INVERT, EDT_SIGNED, EDT_SQUARED, EDT_ANY_OF = 1, 2, 4, 8, 16
 
 _lib = None
 
 _vp, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
+_fp = C.POINTER(C.c_float)
 
 _SIGNATURES = {
     'nrt_status_string': (C.c_char_p, [_i]),
@@ -182,6 +184,10 @@ _SIGNATURES = {
     'nrt_jacdet_workspace_bytes': (_sz, [_i, _ip, _i]),
     'nrt_jacdet_f32': (_i, [_vp, _i, _ip, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nrt_jacdet_bwd_f32': (_i, [_vp, _vp, _vp, _i, _ip, _i, _vp, _vp]),
+    'nrt_edt_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
+    'nrt_edt_f32': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _fp, _i, _vp, _vp, _sz, _vp]),
+    'nrt_surface_stats_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
+    'nrt_surface_stats_f32': (_i, [_vp, _vp, _i, _vp, _i, _ip, _i, _vp, _vp, _ll, _vp, _sz, _vp]),
 }
 
 

@@ -2,7 +2,8 @@
 neurite_amd.losses -- neurite/tf/losses.py:46-205 for the hot path: the metrics classes with
 `loss` (negative Dice [B, L] / the CCE scalar) and `mean_loss` (negative mean Dice); and the two losses of an unsupervised
 VoxelMorph registration run, `NCC` and `Grad` (vxm.losses; restated), on csrc/vxmloss.hip; and `NegJacobian`, the
-folding penalty on the Jacobian determinant of a field (an extension), on csrc/jacobian.hip.
+folding penalty on the Jacobian determinant of a field (an extension), on csrc/jacobian.hip; and `SignedDistanceMSE`,
+the regression of a signed distance map drawn from a label map (an extension), on csrc/edt.hip.
 """
 
 import numpy as np
@@ -12,7 +13,7 @@ from . import _lib, metrics, utils
 from .deferred import materialize
 
 __all__ = ['Dice', 'SoftDice', 'HardDice', 'CategoricalCrossentropy', 'WeightedCategoricalCrossentropy',
-           'MeanSquaredErrorProb', 'multiple_losses_decorator', 'NCC', 'Grad', 'NegJacobian']
+           'MeanSquaredErrorProb', 'multiple_losses_decorator', 'NCC', 'Grad', 'NegJacobian', 'SignedDistanceMSE']
 
 
 class _DiceLossMixin:
@@ -298,3 +299,64 @@ class NegJacobian:
         disp, _ = utils._jacdet_checked(y_pred, 'NegJacobian')
         out = utils._JacDetFn.apply(disp, True)
         return out if self.loss_mult is None else out * float(self.loss_mult)
+
+
+class SignedDistanceMSE:
+    """
+    Mean squared error between a predicted signed distance map and the signed distance transform of a foreground mask drawn from a
+    label map (utils.signed_dist_trf on csrc/edt.hip, positive outside the foreground): what a SynthStrip-style network with a linear
+    one-channel head regresses.  An extension, like NegJacobian: the definition is this project's, not SynthStrip's
+    published loss.
+
+        loss(ids, y_pred)        ids [B, *S] or [B, *S, 1] integer label ids, y_pred [B, *S, 1]
+        loss(None, y_pred)       y_pred [B, *S, 2], SynthStrip's stacked output: channel 0 the prediction, channel 1 the ids as float
+
+    target = signed distance (in units of voxel_size) to the set {ids in foreground}, clipped to +-max_dist when given; the result [B] is
+    the mean over voxels of (pred - target)^2.  The target is formed on the device from the id map (no mask tensor, nothing on the host)
+    and is a constant: the loss is differentiable in the prediction only.  With an empty or a full foreground the target is +-inf; give
+    max_dist to keep such samples finite.
+    """
+
+    def __init__(self, foreground, max_dist=None, voxel_size=None):
+        self.foreground = utils._edt_labels([foreground] if np.isscalar(foreground) else foreground, 'SignedDistanceMSE')
+        if not 1 <= len(self.foreground) <= utils._EDT_MAX_LABELS:
+            raise NotImplementedError('SignedDistanceMSE: 1 to %d foreground ids, got %d' % (utils._EDT_MAX_LABELS, len(self.foreground)))
+        if max_dist is not None and not float(max_dist) > 0:
+            raise ValueError('SignedDistanceMSE: max_dist must be positive, got %r' % (max_dist,))
+        self.max_dist = None if max_dist is None else float(max_dist)
+        self.voxel_size = voxel_size
+
+    def target(self, ids):
+        """the regression target [B, *S] of a label map [B, *S]"""
+        with torch.no_grad():
+            sdt = utils._label_dist_trf(ids, self.foreground, self.voxel_size, _lib.EDT_SIGNED, 'SignedDistanceMSE', any_of=True)[..., 0]
+            return sdt if self.max_dist is None else sdt.clamp(-self.max_dist, self.max_dist)
+
+    def loss(self, y_true, y_pred):
+        what = 'SignedDistanceMSE'
+        if not isinstance(y_pred, torch.Tensor):
+            raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(y_pred).__name__))
+        y_pred = materialize(y_pred)
+        if not y_pred.dtype.is_floating_point:
+            raise NotImplementedError('%s: a floating-point prediction, got %s' % (what, y_pred.dtype))
+        if y_true is None:
+            if y_pred.dim() < 3 or y_pred.shape[-1] != 2:
+                raise ValueError('%s: without y_true, y_pred must be [batch, *spatial, 2] (prediction, ids), got shape %s'
+                                 % (what, tuple(y_pred.shape)))
+            pred, ids = y_pred[..., 0], y_pred[..., 1].detach().round().to(torch.int32)
+        else:
+            if not isinstance(y_true, torch.Tensor):
+                raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(y_true).__name__))
+            if y_pred.dim() < 3 or y_pred.shape[-1] != 1:
+                raise ValueError('%s: y_pred must be [batch, *spatial, 1], got shape %s' % (what, tuple(y_pred.shape)))
+            pred, ids = y_pred[..., 0], materialize(y_true)
+            if ids.dim() == y_pred.dim():
+                if ids.shape[-1] != 1:
+                    raise ValueError('%s: y_true must be [batch, *spatial] or [batch, *spatial, 1], got shape %s' % (what, tuple(ids.shape)))
+                ids = ids[..., 0]
+            if ids.shape != pred.shape:
+                raise ValueError('%s: y_true %s does not match y_pred %s' % (what, tuple(y_true.shape), tuple(y_pred.shape)))
+        utils._edt_check_geometry(utils._edt_ids_checked(ids, what).shape, 1, what)
+        _lib.require_device(pred, ids)
+        target = self.target(ids)
+        return ((pred.to(torch.float32) - target) ** 2).flatten(1).mean(1)

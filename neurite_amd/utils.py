@@ -5,7 +5,8 @@ Mirrors the names, arguments, defaults and error behaviour of neurite/tf/utils/u
 interpn (:73), resize/zoom (:223,:265), volshape_to_ndgrid (:333), volshape_to_meshgrid (:356),
 ndgrid (:382), meshgrid (:398), sub2ind2d (:1068), prod_n (:1085), batch_channel_flatten (:1175),
 flatten_axes (:1195), barycenter (:512); plus voxelmorph's transform()/affine_to_dense_shift, which the reference
-calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159), and voxelmorph's jacobian_determinant (restated: DESIGN 4.6i).
+calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159), and voxelmorph's jacobian_determinant (restated: DESIGN 4.6i) and its
+dist_trf / signed_dist_trf / vol_to_sdt family (restated: DESIGN 4.6j).
 
 Tensors are torch tensors on a ROCm device in the reference's channels-last layout.  All sampling
 work is done by the HIP kernels in csrc/interpn.hip through the C ABI; nothing here falls back
@@ -22,6 +23,7 @@ from .deferred import materialize
 
 __all__ = ['interpn', 'resize', 'zoom', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
            'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter', 'jacobian_determinant',
+           'dist_trf', 'signed_dist_trf', 'vol_to_sdt', 'vol_to_sdt_batch', 'label_dist_trf',
            'rescale_dense_transform', 'rescale_affine', 'is_affine_shape', 'validate_affine_shape', 'make_square_affine', 'volshape_to_ndgrid',
            'volshape_to_meshgrid', 'ndgrid', 'meshgrid', 'sub2ind2d', 'prod_n', 'batch_channel_flatten',
            'flatten_batch_channel', 'flatten_axes']
@@ -1027,6 +1029,196 @@ def jacobian_determinant(disp):
     disp, batched = _jacdet_checked(disp, 'jacobian_determinant')
     det = _JacDetFn.apply(disp, False)
     return det if batched else det[0]
+
+
+# --------------------------------------------------------------------------------------
+# exact Euclidean distance transforms (csrc/edt.hip)
+# --------------------------------------------------------------------------------------
+
+_EDT_MAX_EXTENT, _EDT_MAX_LABELS = 1024, 256
+_edt_label_cache = {}
+
+
+def _edt_sampling(sampling, nd, what):
+    """None, a scalar or nd voxel sizes -> None or a tuple of nd float32 values held as Python floats"""
+    if sampling is None:
+        return None
+    vals = np.asarray(sampling, dtype=np.float64).reshape(-1)
+    if vals.size == 1:
+        vals = np.repeat(vals, nd)
+    if vals.size != nd:
+        raise ValueError('%s: sampling must be a scalar or %d voxel sizes, got %r' % (what, nd, sampling))
+    if not np.all(np.isfinite(vals)) or not np.all(vals > 0):
+        raise ValueError('%s: voxel sizes must be finite and positive, got %r' % (what, sampling))
+    return tuple(float(np.float32(v)) for v in vals)
+
+
+def _edt_check_geometry(shape, channels, what):
+    """the limits of csrc/edt.hip for out [B, *S, channels], before the device is looked at"""
+    batch, spatial = int(shape[0]), [int(v) for v in shape[1:]]
+    if len(spatial) not in (2, 3):
+        raise NotImplementedError('%s: 2 or 3 spatial axes, got %d (shape %s)' % (what, len(spatial), tuple(shape)))
+    if batch < 1 or any(v < 1 for v in spatial):
+        raise ValueError('%s: empty tensor of shape %s' % (what, tuple(shape)))
+    if any(v > _EDT_MAX_EXTENT for v in spatial):
+        raise NotImplementedError('%s: extents up to %d, got shape %s' % (what, _EDT_MAX_EXTENT, tuple(shape)))
+    if not 1 <= channels <= _EDT_MAX_LABELS:
+        raise NotImplementedError('%s: 1 to %d labels, got %d' % (what, _EDT_MAX_LABELS, channels))
+    if batch > 65535 or batch * int(np.prod(spatial, dtype=np.int64)) * channels >= 2 ** 31:
+        raise NotImplementedError('%s: up to 65535 batch entries and fewer than 2^31 output elements, got shape %s x %d labels'
+                                  % (what, tuple(shape), channels))
+
+
+def _edt_labels(labels, what):
+    """a label list -> a tuple of distinct Python ints that int32 holds"""
+    if isinstance(labels, torch.Tensor):
+        labels = labels.detach().cpu().numpy()
+    arr = np.asarray(labels).reshape(-1)
+    if arr.size and not np.all(arr == np.round(arr)):
+        raise ValueError('%s: label ids must be integers, got %r' % (what, labels))
+    ids = tuple(int(v) for v in arr)
+    if len(set(ids)) != len(ids):
+        raise ValueError('%s: label ids must be distinct, got %r' % (what, ids))
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in ids):
+        raise ValueError('%s: label ids must fit int32, got %r' % (what, ids))
+    return ids
+
+
+def _edt_label_tensor(ids, dev):
+    """the int32 device copy of a label tuple, made once per (device, list): no host-to-device copy on later calls, so they capture"""
+    key = (dev, ids)
+    t = _edt_label_cache.get(key)
+    if t is None:
+        t = torch.tensor(ids, dtype=torch.int32).to(dev)
+        _edt_label_cache[key] = t
+    return t
+
+
+def _edt_ids_checked(ids, what):
+    """an integer or bool label map, checked on the host (the callers convert it to int32 once its device is known)"""
+    if not isinstance(ids, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(ids).__name__))
+    ids = materialize(ids)
+    if ids.dtype.is_floating_point or ids.dtype.is_complex:
+        raise NotImplementedError('%s: an integer (or bool) label map, got %s' % (what, ids.dtype))
+    return ids
+
+
+def _edt_launch(out_shape, dev, mask=None, ids=None, labels=None, sampling=None, flags=0):
+    """nrt_edt_f32 into a new tensor of out_shape = [B, *S, channels]; mask uint8 [B, *S] or ids int32 [B, *S] + labels (device int32)"""
+    batch, spatial, channels = int(out_shape[0]), [int(v) for v in out_shape[1:-1]], int(out_shape[-1])
+    cshape = _lib.ints(spatial)
+    out = torch.empty(tuple(out_shape), dtype=torch.float32, device=dev)
+    ws, nws = None, 0
+    if flags & _lib.EDT_SIGNED:
+        nws = int(_lib.lib().nrt_edt_workspace_bytes(batch, cshape, len(spatial), channels))
+        ws = _lib.workspace(dev, max(nws, 16))
+    csamp = (C.c_float * len(spatial))(*sampling) if sampling is not None else None
+    _lib.call(dev, 'nrt_edt_f32', _lib.ptr(mask), _lib.ptr(ids), _lib.ptr(labels), 1 if labels is None else int(labels.numel()), batch,
+              cshape, len(spatial), csamp, int(flags), _lib.ptr(out), _lib.ptr(ws), nws)
+    return out
+
+
+def _dist_trf(bwvol, sampling, squared, batched, signed, what):
+    if not isinstance(bwvol, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(bwvol).__name__))
+    bwvol = materialize(bwvol)
+    if bwvol.dtype.is_complex:
+        raise NotImplementedError('%s: a real volume, got %s' % (what, bwvol.dtype))
+    vol = bwvol if batched else bwvol.unsqueeze(0)
+    if vol.dim() < 2:
+        raise ValueError('%s: expected [*spatial]%s, got shape %s' % (what, ' behind a batch axis' if batched else '', tuple(bwvol.shape)))
+    _edt_check_geometry(vol.shape, 1, what)
+    samp = _edt_sampling(sampling, vol.dim() - 1, what)
+    dev = _lib.require_device(vol)
+    if vol.dtype == torch.bool:
+        vol = vol.contiguous().view(torch.uint8)
+    elif vol.dtype != torch.uint8:
+        vol = vol.ne(0).view(torch.uint8)                # (any other dtype: "nonzero" is decided here, one elementwise op)
+    flags = (_lib.EDT_SIGNED if signed else 0) | (_lib.EDT_SQUARED if squared else 0)
+    out = _edt_launch(tuple(vol.shape) + (1,), dev, mask=vol.contiguous(), sampling=samp, flags=flags).squeeze(-1)
+    return out if batched else out[0]
+
+
+def dist_trf(bwvol, sampling=None, squared=False, batched=False):
+    """
+    Euclidean distance from every voxel to the nearest nonzero voxel of bwvol, 0 on the set: VoxelMorph's dist_trf,
+    scipy.ndimage.distance_transform_edt(~bwvol), restated (voxelmorph is not in the reference tree) and computed exactly
+    on the device (csrc/edt.hip) -- nothing travels to the host, so the call captures into a graph.
+
+    bwvol:    [*S], or [B, *S] with batched=True; len(S) in {2, 3}, every extent at most 1024.  bool and uint8 are read as they are;
+              any other real dtype goes through one `!= 0`.
+    sampling: None (unit voxels), a scalar, or len(S) voxel sizes, as scipy's argument.
+    squared:  the squared distance, without the root.
+    Returns float32 of bwvol's shape.  At unit spacing the result is the correctly rounded root of the exact integer squared distance
+    (scipy's float64 result rounded to float32); with a sampling, d^2 is within 6 * 2^-24 and d within 4 * 2^-24 relative of the exact
+    values at the float32 voxel sizes.  Not differentiable: the input is a set.
+
+    Deviation from scipy: an EMPTY set gives +inf everywhere.  scipy returns arbitrary finite values when its input has no background.
+    """
+    return _dist_trf(bwvol, sampling, squared, batched, False, 'dist_trf')
+
+
+def signed_dist_trf(bwvol, sampling=None, squared=False, batched=False):
+    """
+    VoxelMorph's signed_dist_trf (posdst * ~bw - negdst * bw; restated): +d(p, set) outside the set of nonzero voxels,
+    -d(p, complement) inside it; with squared=True the squared distances carry the sign.  Arguments, limits and accuracy as `dist_trf`.
+
+    Deviations: an EMPTY set gives +inf everywhere and a FULL set -inf everywhere (VoxelMorph's expression gives NaN from inf * 0 on
+    top of scipy's arbitrary values there).
+    """
+    return _dist_trf(bwvol, sampling, squared, batched, True, 'signed_dist_trf')
+
+
+def vol_to_sdt(X_label, sdt=True, sdt_vol_resize=1):
+    """
+    VoxelMorph's vol_to_sdt (restated): the signed distance transform of one volume [*S], its absolute value with
+    sdt=False.  sdt_vol_resize != 1 is not implemented.
+    """
+    if sdt_vol_resize != 1:
+        raise NotImplementedError('vol_to_sdt: sdt_vol_resize != 1 is not implemented')
+    X_dt = _dist_trf(X_label, None, False, False, True, 'vol_to_sdt')
+    return X_dt if sdt else X_dt.abs()
+
+
+def vol_to_sdt_batch(X_label, sdt=True, sdt_vol_resize=1):
+    """VoxelMorph's vol_to_sdt_batch (restated): `vol_to_sdt` of every entry of [B, *S, 1], returned as [B, *S, 1]; one launch set."""
+    if sdt_vol_resize != 1:
+        raise NotImplementedError('vol_to_sdt_batch: sdt_vol_resize != 1 is not implemented')
+    if not isinstance(X_label, torch.Tensor):
+        raise TypeError('vol_to_sdt_batch: expected a torch.Tensor, got %s' % type(X_label).__name__)
+    if X_label.dim() < 3 or X_label.shape[-1] != 1:
+        raise ValueError('vol_to_sdt_batch: expected [batch, *spatial, 1], got shape %s' % (tuple(X_label.shape),))
+    X_dt = _dist_trf(materialize(X_label)[..., 0], None, False, True, True, 'vol_to_sdt_batch').unsqueeze(-1)
+    return X_dt if sdt else X_dt.abs()
+
+
+def _label_dist_trf(ids, labels, sampling, flags, what, any_of=False):
+    """ids [B, *S] integer, labels a tuple of ints -> [B, *S, L] (or [B, *S, 1] with any_of), checked"""
+    ids = _edt_ids_checked(ids, what)
+    if ids.dim() < 2:
+        raise ValueError('%s: expected [batch, *spatial], got shape %s' % (what, tuple(ids.shape)))
+    if not 1 <= len(labels) <= _EDT_MAX_LABELS:
+        raise NotImplementedError('%s: 1 to %d labels, got %d' % (what, _EDT_MAX_LABELS, len(labels)))
+    channels = 1 if any_of else len(labels)
+    _edt_check_geometry(ids.shape, channels, what)
+    samp = _edt_sampling(sampling, ids.dim() - 1, what)
+    dev = _lib.require_device(ids)
+    ids = ids.to(torch.int32).contiguous()
+    return _edt_launch(tuple(ids.shape) + (channels,), dev, ids=ids, labels=_edt_label_tensor(labels, dev), sampling=samp,
+                       flags=flags | (_lib.EDT_ANY_OF if any_of else 0))
+
+
+def label_dist_trf(ids, labels, signed=False, sampling=None, squared=False):
+    """
+    The distance transform of every label of an integer label map at once (an extension): channel l of the result
+    [B, *S, L] is `dist_trf` (or `signed_dist_trf`) of ids == labels[l], and all L come from one read of the id map -- no one-hot
+    volume and no mask exist.  ids [B, *S] integer (bool counts as 0 / 1); labels: 1 to 256 distinct ids; a label that does not occur
+    gives +inf in its channel.  Limits and accuracy as `dist_trf`; B * prod(S) * L must stay below 2^31.
+    """
+    labels = _edt_labels(labels, 'label_dist_trf')
+    flags = (_lib.EDT_SIGNED if signed else 0) | (_lib.EDT_SQUARED if squared else 0)
+    return _label_dist_trf(ids, labels, sampling, flags, 'label_dist_trf')
 
 
 # --------------------------------------------------------------------------------------
