@@ -28,6 +28,10 @@ profiles/dispatch_arms/lc3d_kernels.txt).  The four bfloat16 lc3d_fwd_mfma<..., 
 
 --families conv_bf16 checks the bfloat16 inference kernels of csrc/conv_bf16.hip (tests/test_gpu_conv_bf16_arms.py; kernel table
 profiles/dispatch_arms/conv_bf16_kernels.txt): 17 instances, every one reachable.
+
+--families warp_fwd checks the warp forward kernels of csrc/interpn.hip, interpn_lean.hip and interpn_any.hip
+(tests/test_gpu_warp_forward_arms.py; kernel tables profiles/dispatch_arms/interpn_kernels.txt, interpn_lean_kernels.txt and
+interpn_any_kernels.txt): 210 instances.  The 18 instances interpn_lean<C, VPL, ABSOLUTE | SHIFT> are unreachable.
 """
 import argparse
 import csv
@@ -64,13 +68,20 @@ LC3D_FAMILIES = [r'lc3d_fwd<%s,\d+,\d+,(?:false|true),\d+>' % _T, r'lc3d_bwd<%s,
 # nrt_upsample_concat_bf16 and nrt_add_act_affine_bf16 (csrc/conv_bf16.hip): the whole translation unit but nrt_zero_words
 CONV_BF16_FAMILIES = [r'conv3d_bf16<\d+>', r'conv3d_pack_bf16<%s>' % _T, r'conv1x1_bf16<\d+>', r'softmax_lastdim_bf16<(?:false|true)>',
                       r'maxpool3d_bf16<\d+>', r'upsample_concat_bf16<\d+>', r'add_act_affine_bf16<\d+>']
+# the dispatchers of nrt_interpn_f32_ex / nrt_interpn_f32, nrt_interpn_add_f32, nrt_interpn_nearest_i32 and nrt_interpn_any (the wave-cache
+# kernel of variant 10 and the fused warp + Dice kernels live in other translation units and have their own tests)
+_A = r'(?:float|double|HalfTag|Bf16Tag)'
+WARP_FWD_FAMILIES = [r'interpn_generic<\d+,\d+,\d+,(?:float|int)>', r'interpn_rows<\d+,\d+,\d+>', r'interpn_tile<\d+,\d+>',
+                     r'interpn_zrun_c32<\d+,\d+,\d+>', r'interpn_lean_tile<\d+,\d+,\d+>', r'interpn_lean<\d+,\d+,\d+>',
+                     r'interpn_any_nd<%s,(?:false|true),\d+,\d+>' % _A, r'interpn_any<%s,(?:false|true)>' % _A, r'interpn_any_nearest_i32']
 FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
-               'lc3d': LC3D_FAMILIES, 'conv_bf16': CONV_BF16_FAMILIES}
+               'lc3d': LC3D_FAMILIES, 'conv_bf16': CONV_BF16_FAMILIES, 'warp_fwd': WARP_FWD_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
 # aligned, which include/neurite_amd.h rules out; a bfloat16 patch the matrix-core forward accepts has at most 56 16-byte pieces, so
-# its two-pieces-per-lane form (NPC = 2, more than 64) never runs (profiles/dispatch_arms/README.md)
+# its two-pieces-per-lane form (NPC = 2, more than 64) never runs; nrt_lean_launch sends every call with per-voxel locations (ABSOLUTE = 0,
+# SHIFT = 1) to interpn_lean_tile, so the row form interpn_lean only runs in LINSPACE mode (profiles/dispatch_arms/README.md)
 UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
-               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': []}
+               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': [], 'warp_fwd': [r'interpn_lean<\d+,\d+,[01]>']}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
