@@ -149,7 +149,8 @@ size_t nrt_dice_workspace_bytes(long long nvox, int nlabels, int batch);
  *   sums   [batch, 3, nlabels] float32 : sum_v t*p, sum_v t*t, sum_v p*p
  *   dice   [batch, nlabels]    float32 : laplace>0 ? (2*tp+eps)/(tt+pp+eps) : divide_no_nan(2*tp, tt+pp)
  *   minmax [4] float32 (may be NULL)   : min t, max t, min p, max p over the whole call
- *                                        (after normalisation if normalize != 0)
+ *                                        (after normalisation if normalize = 1)
+ *   normalize 0 or 1 (y / sum_l y first, :434-436); any other value is NRT_ERR_INVALID_ARG.
  * Deterministic: wavefront shuffles -> LDS -> per-block partials -> fixed-order second stage.
  */
 int nrt_dice_soft_f32(const float *y_true, const float *y_pred, long long nvox, int nlabels, int batch,

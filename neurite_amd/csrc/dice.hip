@@ -679,7 +679,8 @@ extern "C" size_t nrt_dice_workspace_bytes(long long nvox, int nlabels, int batc
 extern "C" int nrt_dice_soft_f32(const float *y_true, const float *y_pred, long long nvox, int nlabels, int batch,
                                  int normalize, float laplace_smoothing, float *sums, float *dice, float *minmax,
                                  void *workspace, size_t workspace_bytes, void *stream) {
-    return dice_soft_impl<float>(y_true, y_pred, nvox, nlabels, batch, normalize != 0, laplace_smoothing, sums, dice, minmax, workspace,
+    if (normalize != 0 && normalize != 1) return NRT_ERR_INVALID_ARG;      // 2 is the difference arm: nrt_sqdiff_sums_f32 only
+    return dice_soft_impl<float>(y_true, y_pred, nvox, nlabels, batch, normalize, laplace_smoothing, sums, dice, minmax, workspace,
                                  workspace_bytes, stream);
 }
 
@@ -691,7 +692,7 @@ extern "C" int nrt_sqdiff_sums_f32(const float *a, const float *b, long long nvo
 extern "C" int nrt_dice_soft(const void *y_true, const void *y_pred, int dtype, long long nvox, int nlabels, int batch, int normalize,
                              float laplace_smoothing, float *sums, float *dice, float *minmax, void *workspace, size_t workspace_bytes,
                              void *stream) {
-    normalize = normalize != 0;
+    if (normalize != 0 && normalize != 1) return NRT_ERR_INVALID_ARG;
     switch (dtype) {
         case NRT_DT_F32: return dice_soft_impl<float>(y_true, y_pred, nvox, nlabels, batch, normalize, laplace_smoothing, sums, dice, minmax,
                                                       workspace, workspace_bytes, stream);

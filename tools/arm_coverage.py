@@ -32,10 +32,15 @@ profiles/dispatch_arms/conv_bf16_kernels.txt): 17 instances, every one reachable
 --families warp_fwd checks the warp forward kernels of csrc/interpn.hip, interpn_lean.hip and interpn_any.hip
 (tests/test_gpu_warp_forward_arms.py; kernel tables profiles/dispatch_arms/interpn_kernels.txt, interpn_lean_kernels.txt and
 interpn_any_kernels.txt): 210 instances.  The 18 instances interpn_lean<C, VPL, ABSOLUTE | SHIFT> are unreachable.
+
+--families dice checks the Dice reductions of csrc/dice.hip and csrc/dice_reduce.h, --families cce the weighted cross-entropy of
+csrc/cce.hip (tests/test_gpu_dice_cce_arms.py; kernel tables profiles/dispatch_arms/dice_kernels.txt and cce_kernels.txt): 107 and 60
+instances, every one reachable.
 """
 import argparse
 import csv
 import re
+import subprocess
 import sys
 
 # the dispatchers of nrt_conv1x1_softmax_f32, nrt_softmax_lastdim_f32, nrt_softmax_bwd_f32, nrt_conv3d_wgrad2_f32 (its two
@@ -74,14 +79,24 @@ _A = r'(?:float|double|HalfTag|Bf16Tag)'
 WARP_FWD_FAMILIES = [r'interpn_generic<\d+,\d+,\d+,(?:float|int)>', r'interpn_rows<\d+,\d+,\d+>', r'interpn_tile<\d+,\d+>',
                      r'interpn_zrun_c32<\d+,\d+,\d+>', r'interpn_lean_tile<\d+,\d+,\d+>', r'interpn_lean<\d+,\d+,\d+>',
                      r'interpn_any_nd<%s,(?:false|true),\d+,\d+>' % _A, r'interpn_any<%s,(?:false|true)>' % _A, r'interpn_any_nearest_i32']
-FAMILY_SETS = {'conv': FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
+# the dispatchers of nrt_dice_soft / nrt_dice_soft_f32 / nrt_sqdiff_sums_f32, nrt_dice_hard_prob / _f32 / _minmax_f32, nrt_dice_hard_label_i32,
+# nrt_dice_from_sums_f32 and nrt_dice_mean_pair_f32 / nrt_dice_mean_f32 (csrc/dice.hip with the second stage of csrc/dice_reduce.h): the
+# whole translation unit but nrt_zero_words
+_ST = r'(?:float|DiceBf16|_Float16)'
+DICE_FAMILIES = [r'dice_soft_vec<\d+,(?:false|true),%s>' % _ST, r'dice_soft_generic<(?:false|true),%s>' % _ST,
+                 r'dice_hard_vec<\d+,(?:false|true),%s>' % _ST, r'dice_hard_prob_generic<%s>' % _ST, r'dice_hard_prob_direct<%s>' % _ST,
+                 r'dice_hard_label<(?:false|true)>', r'dice_hard_label_private', r'reduce_rows<(?:float,double|unsignedint,longlong)>',
+                 r'dice_soft_finalize', r'dice_counts_reduce', r'dice_from_counts', r'dice_from_sums', r'dice_mean_pair', r'minmax_rows']
+# the dispatcher of nrt_wcce / nrt_wcce_mean (csrc/cce.hip): the whole translation unit but nrt_zero_words
+CCE_FAMILIES = [r'wcce_vec<\d+,%s,(?:false|true),(?:false|true)>' % _T, r'wcce_generic<%s,(?:false|true)>' % _T]
+FAMILY_SETS = {'conv': FAMILIES, 'dice': DICE_FAMILIES, 'cce': CCE_FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
                'lc3d': LC3D_FAMILIES, 'conv_bf16': CONV_BF16_FAMILIES, 'warp_fwd': WARP_FWD_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
 # aligned, which include/neurite_amd.h rules out; a bfloat16 patch the matrix-core forward accepts has at most 56 16-byte pieces, so
 # its two-pieces-per-lane form (NPC = 2, more than 64) never runs; nrt_lean_launch sends every call with per-voxel locations (ABSOLUTE = 0,
 # SHIFT = 1) to interpn_lean_tile, so the row form interpn_lean only runs in LINSPACE mode (profiles/dispatch_arms/README.md)
 UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
-               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': [], 'warp_fwd': [r'interpn_lean<\d+,\d+,[01]>']}
+               'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': [], 'dice': [], 'cce': [], 'warp_fwd': [r'interpn_lean<\d+,\d+,[01]>']}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
 
@@ -114,11 +129,18 @@ def instances(paths):
     return sorted(found)
 
 
+def demangle(name):
+    """a name the profiler left mangled: instances over _Float16 (DF16_, which neither it nor an older c++filt knows; Dh, the same builtin
+    type before clang 15, prints as `half` -- tools/kernel_digest.py does the same)"""
+    out = subprocess.run(['c++filt', name.replace('DF16_', 'Dh')], capture_output=True, text=True).stdout.strip()
+    return re.sub(r'\bhalf\b', '_Float16', out) if 'DF16_' in name else out
+
+
 def launches(path):
     calls = {}
     with open(path, newline='') as f:
         for row in csv.DictReader(f):
-            n = norm(row['Name'])
+            n = norm(demangle(row['Name']) if row['Name'].startswith('_Z') else row['Name'])
             calls[n] = calls.get(n, 0) + int(row['Calls'])
     return calls
 

@@ -39,9 +39,12 @@ def digest(path):
         m['n'] = sum(1 for ln in lines if ln.startswith('\t'))
         m['hash'] = hashlib.sha1('\n'.join(lines).encode()).hexdigest()[:12]
         rows.append(name)
-    dem = subprocess.run(['c++filt'], input='\n'.join(rows), capture_output=True, text=True).stdout.splitlines()
+    # _Float16 is mangled DF16_, which an older c++filt leaves as it is; Dh (the same type before clang 15; like DF16_ a builtin, so no
+    # substitution index moves) it prints as `half`
+    dem = subprocess.run(['c++filt'], input='\n'.join(r.replace('DF16_', 'Dh') for r in rows), capture_output=True, text=True).stdout.splitlines()
     out = []
     for name, d in zip(rows, dem):
+        d = re.sub(r'\bhalf\b', '_Float16', d) if 'DF16_' in name else d
         d = re.sub(r'\(anonymous namespace\)::', '', d).split('(')[0].replace('void ', '')
         m = meta[name]
         out.append('%-62s v%-3d s%-3d spill%-2d scr%-4d lds%-6d occ%-2d n%-5d %s' %
