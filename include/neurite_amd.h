@@ -1093,6 +1093,46 @@ size_t nrt_surface_stats_workspace_bytes(int batch, const int *shape, int nd, in
 int nrt_surface_stats_f32(const int *t, const int *labels, int nlabels, const float *d2, int batch, const int *shape, int nd,
                           void *stats, unsigned *hist, long long nbins, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Connected-component labelling and the mask clean-up built on it (csrc/ccl.hip, csrc/ccl_core.h).  They replace a copy
+ * of every volume to the host, scipy.ndimage.label / binary_fill_holes there, and a copy back.
+ * The input is [batch, *shape], `shape` holds nd extents (2 or 3), and comes from exactly one of
+ *   mask   [batch, *shape] uint8: nonzero voxels are foreground (nlabels 1, labels NULL), or
+ *   ids    [batch, *shape] int32 with labels [nlabels] int32 (1 .. 256 distinct ids) on the device: ids outside the list are background.
+ * Two neighbouring voxels belong to one component when both are foreground and carry the same id; the neighbourhood is scipy's
+ * generate_binary_structure(nd, connectivity), connectivity 1 .. nd (4 / 8 neighbours in 2-D, 6 / 18 / 26 in 3-D).
+ *   nrt_ccl_label_i32   components [batch, *shape] int32: 0 on the background, else the number of the voxel's component; the
+ *                 components of an entry are numbered 1, 2, ... in raster (C) order of their first voxel, per entry: the numbering of
+ *                 scipy.ndimage.label.  count [batch] int32: the components of each entry.
+ *   nrt_ccl_select      the components are sized and tested, per (entry, label slot; one slot for a mask).  mode is a sum of
+ *                 NRT_CCL_LARGEST      keep the largest component of each (entry, slot); ties go to the lowest component number;
+ *                 NRT_CCL_MIN_SIZE     keep components of at least min_size voxels;
+ *                 NRT_CCL_BORDER_FREE  keep components without a voxel at the border of the volume (first or last along an axis);
+ *                 NRT_CCL_INVERT       (mask only) the foreground is the ZERO voxels, and the voxels of the set itself are written
+ *                                      as kept: with BORDER_FREE the output is binary_fill_holes(mask, structure);
+ *                 a component is kept when it passes every test asked for (mode 0 keeps all).  out, if given: for a mask
+ *                 [batch, *shape] uint8, 1 where the voxel is kept, else 0; for ids [batch, *shape] int32, the id map with the voxels
+ *                 of rejected components set to `fill` (ids outside the list pass through).  table, if given: [batch, nlabels, 2]
+ *                 int32, the number of components and the size of the largest (0 0 where the slot is empty).  One of the two at least.
+ * workspace: nrt_ccl_workspace_bytes (nlabels 1 for a mask), 8-byte aligned; the call initialises what it uses of it, every time.
+ * Integer atomics only, no workgroup waits for another, no host synchronisation (the calls capture into a graph), no allocation;
+ * the results do not depend on the schedule: bit-identical run to run.  Checked before any launch, in this order:
+ * NRT_ERR_INVALID_ARG for a NULL components, count or shape, table and out both NULL, both or neither of mask and ids, ids without
+ * labels, mask with labels or nlabels != 1, an unknown mode bit, min_size < 0, INVERT with ids, batch < 1, nd outside {2, 3}, an extent
+ * < 1, connectivity outside 1 .. nd, nlabels outside 1 .. 256; NRT_ERR_UNSUPPORTED for batch > 65535 or 2^31 or more voxels
+ * (32-bit indexing); last, NRT_ERR_WORKSPACE for a missing, misaligned or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define NRT_CCL_LARGEST 1
+#define NRT_CCL_MIN_SIZE 2
+#define NRT_CCL_BORDER_FREE 4
+#define NRT_CCL_INVERT 8
+size_t nrt_ccl_workspace_bytes(int batch, const int *shape, int nd, int nlabels);
+int nrt_ccl_label_i32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
+                      int connectivity, int *components, int *count, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_ccl_select(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
+                   int connectivity, int mode, int min_size, int fill, int *table, void *out, void *workspace, size_t workspace_bytes,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ INTERP_LINEAR, INTERP_NEAREST = 0, 1
 DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32 = 0, 1, 2, 3, 4
 SEG_WANT_DICE, SEG_WANT_CCE = 1, 2
 EDT_SURFACE, EDT_INVERT, EDT_SIGNED, EDT_SQUARED, EDT_ANY_OF = 1, 2, 4, 8, 16
+CCL_LARGEST, CCL_MIN_SIZE, CCL_BORDER_FREE, CCL_INVERT = 1, 2, 4, 8
 
 _lib = None
 
@@ -188,6 +189,9 @@ _SIGNATURES = {
     'nrt_edt_f32': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _fp, _i, _vp, _vp, _sz, _vp]),
     'nrt_surface_stats_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
     'nrt_surface_stats_f32': (_i, [_vp, _vp, _i, _vp, _i, _ip, _i, _vp, _vp, _ll, _vp, _sz, _vp]),
+    'nrt_ccl_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
+    'nrt_ccl_label_i32': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_ccl_select': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -23,7 +23,7 @@ from .errors import InvalidArgumentError
 
 __all__ = ['Dice', 'SoftDice', 'HardDice', 'CategoricalCrossentropy', 'WeightedCategoricalCrossentropy',
            'dice_partial_sums', 'MutualInformation', 'MeanSquaredErrorProb', 'JointSegLoss',
-           'JacobianDeterminant', 'JacobianStats', 'SurfaceDistance']
+           'JacobianDeterminant', 'JacobianStats', 'SurfaceDistance', 'ComponentCount']
 
 _INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64, torch.bool)
 
@@ -1192,3 +1192,40 @@ class SurfaceDistance:
     def hd95(self, y_true, y_pred):
         """hd_percentile at this object's percentile (95 by default)"""
         return self.distances(y_true, y_pred)['hd_percentile']
+
+
+class ComponentCount:
+    """
+    The number of connected components of every label of an integer label map, the cheapest topology check of a segmentation
+    (csrc/ccl.hip): an anatomical structure that should be one piece has one component, and every further one is a
+    spurious island.  THIS PROJECT'S metric: neither the reference nor VoxelMorph counts components.
+
+    labels:       1 to 256 distinct integer ids; a bool mask is accepted with labels=[1].
+    connectivity: 1 .. len(S), as scipy.ndimage.generate_binary_structure(nd, connectivity).
+    Label maps are [B, *S], len(S) in {2, 3}, B * prod(S) < 2^31.  All labels come from one labelling pass; nothing travels to the
+    host, so the calls capture into a graph.  Not differentiable: the input is a set.
+        counts(ids)   int32 [B, L]: the components of each label (0 where it does not occur)
+        largest(ids)  int32 [B, L]: the voxels of each label's largest component
+        extra(ids)    int32 [B, L]: clamp(counts - 1, 0), the spurious islands
+    """
+
+    def __init__(self, labels, connectivity=1):
+        self.labels = utils._edt_labels(labels, 'ComponentCount')
+        if not 1 <= len(self.labels) <= utils._EDT_MAX_LABELS:
+            raise NotImplementedError('ComponentCount: 1 to %d labels, got %d' % (utils._EDT_MAX_LABELS, len(self.labels)))
+        if isinstance(connectivity, bool) or connectivity != int(connectivity) or not 1 <= int(connectivity) <= 3:
+            raise ValueError('ComponentCount: connectivity 1 to 3, got %r' % (connectivity,))
+        self.connectivity = int(connectivity)
+
+    def table(self, ids):
+        """int32 [B, L, 2]: (components, size of the largest) per entry and label"""
+        return utils._ccl_select(ids, self.labels, self.connectivity, True, 'ComponentCount', want_table=True, want_out=False)[1]
+
+    def counts(self, ids):
+        return self.table(ids)[..., 0]
+
+    def largest(self, ids):
+        return self.table(ids)[..., 1]
+
+    def extra(self, ids):
+        return (self.counts(ids) - 1).clamp_(min=0)

@@ -2703,6 +2703,28 @@ class SynthStrip(nn.Module):
         out = self.unet(synth_image)
         return torch.cat([out, synth_labels.to(torch.float32)], -1)
 
+    def brain_mask(self, image, border=1.0, connectivity=1):
+        """
+        The brain mask of an image: the stripping model predicts a signed distance to the brain boundary, and the mask is
+        `sdt < border` (border in voxels, outwards), its largest connected component, with the holes of that component filled.  This is the
+        post-processing of FreeSurfer's mri_synthstrip, restated, not recorded: FreeSurfer is not in the reference tree.
+
+        image: [B, *inshape] or [B, *inshape, 1] float32, already at the model's resolution and intensity range (nothing is resampled).
+        Returns bool [B, *inshape].  Runs under no_grad, entirely on the device (utils.largest_component, utils.fill_holes).
+        """
+        inshape = tuple(self.config['params']['inshape'])
+        if not isinstance(image, torch.Tensor):
+            raise TypeError('SynthStrip.brain_mask: expected a torch.Tensor, got %s' % type(image).__name__)
+        if tuple(image.shape[1:]) == inshape:
+            image = image.unsqueeze(-1)
+        if image.dim() != len(inshape) + 2 or tuple(image.shape[1:]) != inshape + (1,):
+            raise ValueError('SynthStrip.brain_mask: expected [B, %s] or [B, %s, 1], got shape %s'
+                             % (', '.join(map(str, inshape)), ', '.join(map(str, inshape)), tuple(image.shape)))
+        with torch.no_grad():
+            sdt = self.get_strip_model()(image)[..., 0]
+            mask = utils.largest_component(sdt < float(border), connectivity, batched=True)
+            return utils.fill_holes(mask, connectivity, batched=True)
+
     def save(self, path):
         """unet weights + constructor arguments (npz), reloadable with SynthStrip.load"""
         cfg = json.dumps({'class_name': 'SynthStrip', 'config': self.get_config()})

@@ -6,7 +6,8 @@ interpn (:73), resize/zoom (:223,:265), volshape_to_ndgrid (:333), volshape_to_m
 ndgrid (:382), meshgrid (:398), sub2ind2d (:1068), prod_n (:1085), batch_channel_flatten (:1175),
 flatten_axes (:1195), barycenter (:512); plus voxelmorph's transform()/affine_to_dense_shift, which the reference
 calls but does not vendor (neurite/tf/models.py:806-807, 1157-1159), and voxelmorph's jacobian_determinant (restated: DESIGN 4.6i) and its
-dist_trf / signed_dist_trf / vol_to_sdt family (restated: DESIGN 4.6j).
+dist_trf / signed_dist_trf / vol_to_sdt family (restated: DESIGN 4.6j); and connected components with the mask clean-up built on them
+(scipy.ndimage.label / binary_fill_holes on the device: DESIGN 4.6k).
 
 Tensors are torch tensors on a ROCm device in the reference's channels-last layout.  All sampling
 work is done by the HIP kernels in csrc/interpn.hip through the C ABI; nothing here falls back
@@ -24,6 +25,7 @@ from .deferred import materialize
 __all__ = ['interpn', 'resize', 'zoom', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
            'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter', 'jacobian_determinant',
            'dist_trf', 'signed_dist_trf', 'vol_to_sdt', 'vol_to_sdt_batch', 'label_dist_trf',
+           'connected_components', 'largest_component', 'keep_largest_components', 'remove_small_components', 'fill_holes',
            'rescale_dense_transform', 'rescale_affine', 'is_affine_shape', 'validate_affine_shape', 'make_square_affine', 'volshape_to_ndgrid',
            'volshape_to_meshgrid', 'ndgrid', 'meshgrid', 'sub2ind2d', 'prod_n', 'batch_channel_flatten',
            'flatten_batch_channel', 'flatten_axes']
@@ -1219,6 +1221,151 @@ def label_dist_trf(ids, labels, signed=False, sampling=None, squared=False):
     labels = _edt_labels(labels, 'label_dist_trf')
     flags = (_lib.EDT_SIGNED if signed else 0) | (_lib.EDT_SQUARED if squared else 0)
     return _label_dist_trf(ids, labels, sampling, flags, 'label_dist_trf')
+
+
+# --------------------------------------------------------------------------------------
+# connected components and the mask clean-up built on them (csrc/ccl.hip)
+# --------------------------------------------------------------------------------------
+
+def _ccl_check_geometry(shape, connectivity, what):
+    """the limits of csrc/ccl.hip for an input [B, *S], before the device is looked at"""
+    batch, spatial = int(shape[0]), [int(v) for v in shape[1:]]
+    if len(spatial) not in (2, 3):
+        raise NotImplementedError('%s: 2 or 3 spatial axes, got %d (shape %s)' % (what, len(spatial), tuple(shape)))
+    if batch < 1 or any(v < 1 for v in spatial):
+        raise ValueError('%s: empty tensor of shape %s' % (what, tuple(shape)))
+    if isinstance(connectivity, bool) or connectivity != int(connectivity) or not 1 <= int(connectivity) <= len(spatial):
+        raise ValueError('%s: connectivity 1 to %d, got %r' % (what, len(spatial), connectivity))
+    if batch > 65535 or batch * int(np.prod(spatial, dtype=np.int64)) >= 2 ** 31:
+        raise NotImplementedError('%s: up to 65535 batch entries and fewer than 2^31 voxels, got shape %s' % (what, tuple(shape)))
+
+
+def _ccl_source(x, labels, connectivity, batched, what, invert=False):
+    """x (a mask, or with labels an id map) -> (dev, mask uint8 or None, ids int32 or None, label tensor or None, L, shape [B, *S])"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor, got %s' % (what, type(x).__name__))
+    x = materialize(x)
+    if labels is not None:
+        labels = _edt_labels(labels, what)
+        if not 1 <= len(labels) <= _EDT_MAX_LABELS:
+            raise NotImplementedError('%s: 1 to %d labels, got %d' % (what, _EDT_MAX_LABELS, len(labels)))
+        if x.dtype.is_floating_point or x.dtype.is_complex:
+            raise NotImplementedError('%s: an integer (or bool) label map, got %s' % (what, x.dtype))
+    elif x.dtype.is_complex:
+        raise NotImplementedError('%s: a real volume, got %s' % (what, x.dtype))
+    vol = x if batched else x.unsqueeze(0)
+    if vol.dim() < 2:
+        raise ValueError('%s: expected [*spatial]%s, got shape %s' % (what, ' behind a batch axis' if batched else '', tuple(x.shape)))
+    _ccl_check_geometry(vol.shape, connectivity, what)
+    dev = _lib.require_device(vol)
+    if labels is not None:
+        return dev, None, vol.to(torch.int32).contiguous(), _edt_label_tensor(labels, dev), len(labels), tuple(vol.shape)
+    if vol.dtype == torch.bool:
+        vol = vol.contiguous().view(torch.uint8)
+    elif vol.dtype != torch.uint8:
+        vol = vol.ne(0).view(torch.uint8)                # (any other dtype: "nonzero" is decided here, one elementwise op)
+    return dev, vol.contiguous(), None, None, 1, tuple(vol.shape)
+
+
+def _ccl_workspace(dev, shape, nlabels):
+    cshape = _lib.ints(shape[1:])
+    nws = int(_lib.lib().nrt_ccl_workspace_bytes(shape[0], cshape, len(shape) - 1, nlabels))
+    return cshape, _lib.workspace(dev, max(nws, 16)), nws
+
+
+def _ccl_select(x, labels, connectivity, batched, what, mode=0, min_size=0, fill=0, want_table=False, want_out=True):
+    """nrt_ccl_select -> (out or None: uint8 [B, *S] for a mask, int32 for an id map; table int32 [B, L, 2] or None)"""
+    dev, mask, ids, lab, nlabels, shape = _ccl_source(x, labels, connectivity, batched, what)
+    cshape, ws, nws = _ccl_workspace(dev, shape, nlabels)
+    out = torch.empty(shape, dtype=torch.uint8 if ids is None else torch.int32, device=dev) if want_out else None
+    table = torch.empty((shape[0], nlabels, 2), dtype=torch.int32, device=dev) if want_table else None
+    _lib.call(dev, 'nrt_ccl_select', _lib.ptr(mask), _lib.ptr(ids), _lib.ptr(lab), nlabels, shape[0], cshape, len(shape) - 1,
+              int(connectivity), int(mode), int(min_size), int(fill), _lib.ptr(table), _lib.ptr(out), _lib.ptr(ws), nws)
+    return out, table
+
+
+def _ccl_like(out, x, batched):
+    """a uint8 0 / 1 mask [B, *S] as a mask of x's dtype and batching"""
+    out = out.view(torch.bool) if x.dtype == torch.bool else out if x.dtype == torch.uint8 else out.to(x.dtype)
+    return out if batched else out[0]
+
+
+def _ccl_fill(fill, what):
+    if isinstance(fill, bool) or fill != int(fill) or not -2 ** 31 <= int(fill) < 2 ** 31:
+        raise ValueError('%s: fill must be an integer that int32 holds, got %r' % (what, fill))
+    return int(fill)
+
+
+def connected_components(x, connectivity=1, labels=None, batched=False):
+    """
+    Connected components of a mask or of every listed label of an id map at once: scipy.ndimage.label(x,
+    generate_binary_structure(nd, connectivity)), computed on the device (csrc/ccl.hip) -- nothing travels to the host, so
+    the call captures into a graph.
+
+    x:            [*S], or [B, *S] with batched=True; len(S) in {2, 3}, B * prod(S) < 2^31.  Without `labels` a mask: bool and uint8 are
+                  read as they are, any other real dtype goes through one `!= 0`.  With `labels` (1 to 256 distinct ids) an integer id
+                  map: the listed ids are foreground, and two neighbours belong to one component when they carry the SAME id.
+    connectivity: 1 .. len(S): neighbours differ in at most that many coordinates (4 / 8 in 2-D, 6 / 18 / 26 in 3-D).
+    Returns (components, count): components int32 of x's shape, 0 on the background, numbered 1, 2, ... in raster order of each
+    component's first voxel, per batch entry (scipy's numbering, bit for bit); count int32 [B] on the device, 0-d when not batched.
+    Not differentiable: the input is a set.
+    """
+    what = 'connected_components'
+    dev, mask, ids, lab, nlabels, shape = _ccl_source(x, labels, connectivity, batched, what)
+    cshape, ws, nws = _ccl_workspace(dev, shape, nlabels)
+    comp = torch.empty(shape, dtype=torch.int32, device=dev)
+    count = torch.empty((shape[0],), dtype=torch.int32, device=dev)
+    _lib.call(dev, 'nrt_ccl_label_i32', _lib.ptr(mask), _lib.ptr(ids), _lib.ptr(lab), nlabels, shape[0], cshape, len(shape) - 1,
+              int(connectivity), _lib.ptr(comp), _lib.ptr(count), _lib.ptr(ws), nws)
+    return (comp, count) if batched else (comp[0], count[0])
+
+
+def largest_component(mask, connectivity=1, batched=False):
+    """
+    The largest connected component of a mask, per batch entry, as a mask of the input's dtype; of several of the largest size, the first
+    in raster order (np.argmax of the bincount of scipy.ndimage.label).  An empty mask stays empty.  Arguments and limits as
+    `connected_components`; on the device, graph-capturable, not differentiable.
+    """
+    out, _ = _ccl_select(mask, None, connectivity, batched, 'largest_component', mode=_lib.CCL_LARGEST)
+    return _ccl_like(out, mask, batched)
+
+
+def keep_largest_components(ids, labels, connectivity=1, fill=0, batched=False):
+    """
+    An integer id map with everything but the largest component of each listed label set to `fill` (ties: the first component in raster
+    order); ids outside the list pass through unchanged.  One labelling pass serves all labels.  Returns int32 of ids' shape.
+    Arguments and limits as `connected_components`; on the device, graph-capturable, not differentiable.
+    """
+    what = 'keep_largest_components'
+    if labels is None:
+        raise ValueError('%s: a label list is required' % what)
+    out, _ = _ccl_select(ids, labels, connectivity, batched, what, mode=_lib.CCL_LARGEST, fill=_ccl_fill(fill, what))
+    return out if batched else out[0]
+
+
+def remove_small_components(x, min_size, connectivity=1, labels=None, fill=0, batched=False):
+    """
+    Drops the connected components of fewer than min_size voxels.  Without `labels`, x is a mask and the result a mask of its dtype; with
+    `labels`, x is an integer id map and the result the int32 id map with the dropped voxels set to `fill` (ids outside the list pass
+    through).  Arguments and limits as `connected_components`; on the device, graph-capturable, not differentiable.
+    """
+    what = 'remove_small_components'
+    if isinstance(min_size, bool) or min_size != int(min_size) or not 0 <= int(min_size) < 2 ** 31:
+        raise ValueError('%s: min_size must be an integer in [0, 2^31), got %r' % (what, min_size))
+    out, _ = _ccl_select(x, labels, connectivity, batched, what, mode=_lib.CCL_MIN_SIZE, min_size=int(min_size), fill=_ccl_fill(fill, what))
+    if labels is None:
+        return _ccl_like(out, x, batched)
+    return out if batched else out[0]
+
+
+def fill_holes(mask, connectivity=1, batched=False):
+    """
+    scipy.ndimage.binary_fill_holes(mask, generate_binary_structure(nd, connectivity)): the mask together with every connected
+    component of its complement (under that connectivity) that does not touch the border of the volume.  Returns a mask of the input's
+    dtype.  Arguments and limits as `connected_components`; on the device, graph-capturable, not differentiable.
+    """
+    out, _ = _ccl_select(mask, None, connectivity, batched, 'fill_holes', mode=_lib.CCL_BORDER_FREE | _lib.CCL_INVERT)
+    return _ccl_like(out, mask, batched)
 
 
 # --------------------------------------------------------------------------------------
