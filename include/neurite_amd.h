@@ -1133,6 +1133,43 @@ int nrt_ccl_select(const void *mask, const int *ids, const int *labels, int nlab
                    int connectivity, int mode, int min_size, int fill, int *table, void *out, void *workspace, size_t workspace_bytes,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact percentiles of every batch entry of a volume and the percentile intensity normalisation (csrc/select.hip,
+ * csrc/select_core.h).  They replace torch.quantile (a sort and a sorted copy of every volume, no mask) or a round trip
+ * through the host.
+ *   nrt_percentile   x [batch, voxels] stored as `dtype` (NRT_DT_F32 / NRT_DT_BF16 / NRT_DT_F16); mask NULL or [batch, voxels] uint8
+ *                 (nonzero = selected).  The population of an entry is its selected and, with NRT_PCT_IGNORE_NAN, non-NaN elements:
+ *                 n of them, sorted ascending as s (-0.0 == +0.0, NaN last).  positions: nq (1 .. 8) fractions f in [0, 1], float64,
+ *                 on the HOST (read during the call).  pos = (n - 1) f in float64, a = s[floor(pos)], b = s[ceil(pos)],
+ *                 t = pos - floor(pos), and with a, b widened to float64 and the result rounded to float32 once
+ *                   NRT_PCT_LINEAR    a + (b - a) t  if t < 0.5, else  b - (b - a)(1 - t)      (NumPy's formula)
+ *                   NRT_PCT_LOWER     a            NRT_PCT_HIGHER  b            NRT_PCT_MIDPOINT  (a + b) / 2
+ *                 out [batch, nq] float32; out_lower, out_upper [batch, nq] float32 (a and b) and out_count [batch] int32 (n) may
+ *                 be NULL.  An empty population gives NaN; so does, without NRT_PCT_IGNORE_NAN, a population with a NaN in it (all
+ *                 three outputs).  +-inf are ordinary values (inf - inf in the interpolation is NaN, as in NumPy).
+ *   nrt_rescale_clip_f32   y [batch, voxels] float32 = (x - lo) / (hi - lo) in float32 with lo = lo[b * stride], hi = hi[b * stride]
+ *                 read on the device; 0 where hi == lo; with clip != 0 clipped to [0, 1] (a NaN stays); then, unless
+ *                 (out_min, out_max) is (0, 1), out_min + y * (out_max - out_min); NaN where lo or hi is NaN.
+ * workspace: nrt_select_workspace_bytes, 16-byte aligned; the call initialises what it uses of it, every time.  A radix select on the
+ * monotone key of the floats: three counting passes over x (two for the 16-bit types), integer atomics only, no workgroup waits for
+ * another, no host synchronisation (the calls capture into a graph), no allocation; the results do not depend on the schedule:
+ * bit-identical run to run.  Checked before any launch, in this order: NRT_ERR_INVALID_ARG for a NULL x, positions, out (lo, hi, y), an
+ * unknown dtype, method or flag, batch < 1, voxels < 1, nq outside 1 .. 8, a position outside [0, 1] or NaN (stride < 1, a NaN
+ * out_min / out_max); NRT_ERR_UNSUPPORTED for batch > 65535 or batch * voxels >= 2^31 (32-bit indexing); last, NRT_ERR_WORKSPACE for a
+ * missing, misaligned or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define NRT_PCT_LINEAR 0
+#define NRT_PCT_LOWER 1
+#define NRT_PCT_HIGHER 2
+#define NRT_PCT_MIDPOINT 3
+#define NRT_PCT_IGNORE_NAN 1
+size_t nrt_select_workspace_bytes(int batch, long long voxels, int nq);
+int nrt_percentile(const void *x, int dtype, const void *mask, int batch, long long voxels, const double *positions, int nq, int method,
+                   int flags, float *out, float *out_lower, float *out_upper, int *out_count, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int nrt_rescale_clip_f32(const void *x, int dtype, int batch, long long voxels, const float *lo, const float *hi, int stride, int clip,
+                         float out_min, float out_max, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,12 +24,15 @@ DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32 = 0, 1, 2, 3, 4
 SEG_WANT_DICE, SEG_WANT_CCE = 1, 2
 EDT_SURFACE, EDT_INVERT, EDT_SIGNED, EDT_SQUARED, EDT_ANY_OF = 1, 2, 4, 8, 16
 CCL_LARGEST, CCL_MIN_SIZE, CCL_BORDER_FREE, CCL_INVERT = 1, 2, 4, 8
+PCT_LINEAR, PCT_LOWER, PCT_HIGHER, PCT_MIDPOINT = 0, 1, 2, 3
+PCT_IGNORE_NAN = 1
 
 _lib = None
 
 _vp, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
 _fp = C.POINTER(C.c_float)
+_dp = C.POINTER(C.c_double)
 
 _SIGNATURES = {
     'nrt_status_string': (C.c_char_p, [_i]),
@@ -192,6 +195,9 @@ _SIGNATURES = {
     'nrt_ccl_workspace_bytes': (_sz, [_i, _ip, _i, _i]),
     'nrt_ccl_label_i32': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'nrt_ccl_select': (_i, [_vp, _vp, _vp, _i, _i, _ip, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_select_workspace_bytes': (_sz, [_i, _ll, _i]),
+    'nrt_percentile': (_i, [_vp, _i, _vp, _i, _ll, _dp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nrt_rescale_clip_f32': (_i, [_vp, _i, _i, _ll, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
 }
 
 

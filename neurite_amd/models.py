@@ -2703,14 +2703,18 @@ class SynthStrip(nn.Module):
         out = self.unet(synth_image)
         return torch.cat([out, synth_labels.to(torch.float32)], -1)
 
-    def brain_mask(self, image, border=1.0, connectivity=1):
+    def brain_mask(self, image, border=1.0, connectivity=1, normalize=False):
         """
         The brain mask of an image: the stripping model predicts a signed distance to the brain boundary, and the mask is
         `sdt < border` (border in voxels, outwards), its largest connected component, with the holes of that component filled.  This is the
         post-processing of FreeSurfer's mri_synthstrip, restated, not recorded: FreeSurfer is not in the reference tree.
 
-        image: [B, *inshape] or [B, *inshape, 1] float32, already at the model's resolution and intensity range (nothing is resampled).
-        Returns bool [B, *inshape].  Runs under no_grad, entirely on the device (utils.largest_component, utils.fill_holes).
+        image: [B, *inshape] or [B, *inshape, 1] float32, already at the model's resolution (nothing is resampled) and, with
+        normalize=False, at its intensity range.  normalize=True applies mri_synthstrip's intensity step first, per batch entry:
+        the minimum subtracted, divided by the 99th percentile of the result, clipped to [0, 1]
+        (utils.percentile_norm(image, 0, 99, clip=True, batched=True); also restated, not recorded).
+        Returns bool [B, *inshape].  Runs under no_grad, entirely on the device (utils.percentile_norm, utils.largest_component,
+        utils.fill_holes).
         """
         inshape = tuple(self.config['params']['inshape'])
         if not isinstance(image, torch.Tensor):
@@ -2721,6 +2725,8 @@ class SynthStrip(nn.Module):
             raise ValueError('SynthStrip.brain_mask: expected [B, %s] or [B, %s, 1], got shape %s'
                              % (', '.join(map(str, inshape)), ', '.join(map(str, inshape)), tuple(image.shape)))
         with torch.no_grad():
+            if normalize:
+                image = utils.percentile_norm(image, 0, 99, clip=True, batched=True)
             sdt = self.get_strip_model()(image)[..., 0]
             mask = utils.largest_component(sdt < float(border), connectivity, batched=True)
             return utils.fill_holes(mask, connectivity, batched=True)
