@@ -222,7 +222,10 @@ int nrt_dice_mean_f32(const float *dice, const float *weights, int nlabels, int 
  *   fixed  [batch, out_shape, nlabels];  warped [batch, out_shape, nlabels] or NULL (not written).
  *   sums / dice / minmax as nrt_dice_soft_f32 with y_true = fixed, y_pred = warped.
  * 3-D only, nlabels a multiple of 4 in [4, 256] (4 * 2^k labels: lane groups of nlabels / 4 lanes; any other count: lane groups
- * of the next power of two, the lanes past nlabels / 4 idle).  tune: tile shape knob (0 = default).
+ * of the next power of two, the lanes past nlabels / 4 idle).  tune: tile shape knob (0 = default): log2 of the tile extents
+ * along x, y, z in bits 0-3, 4-7, 8-11, bit 14 the x-march schedule ((y,z) patches of 2^lty x 2^ltz voxels marched along x).  Extents
+ * too small for a block are widened, never refused: z to a wave's run of 64 / G voxels, y until a tile -- on the x-march the
+ * (y,z) patch -- holds the 256 / G voxels of a pass (G = lanes per voxel, above).
  * Size limits (NRT_ERR_UNSUPPORTED beyond them; use nrt_interpn_f32 + nrt_dice_soft_f32): one batch entry of moving /
  * fixed / warped below 4 GiB, shape[0] * shape[1] and shape[2] below 2^24 for both shapes (32-bit row offsets, 24-bit
  * index multiplies).

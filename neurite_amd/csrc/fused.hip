@@ -351,7 +351,6 @@ size_t fused_ws_bytes(unsigned nblocks, int L, int batch) {
 // nblocks = partial rows per batch entry
 void fused_geom(const int *out_shape, int G, int batch, int tune, TileGeom &tg, unsigned &nblocks) {
     tile_geometry(out_shape, G, tune, 3 | (3 << 4) | (4 << 8), tg, nblocks);   // default 8 x 8 x 16 tiles (profiles/r01)
-    if (nblocks > (unsigned)DICE_MAX_BLOCKS) nblocks = DICE_MAX_BLOCKS;        // multiple of 8; blocks loop over tiles
     int t = tune <= 0 ? 0 : tune;
     if (t == 0 && G == 8 && xmarch_applies(out_shape, batch)) {
         // default for 32 labels: x-march over 4 x 8 (y,z) patches, blocks dealt to the XCDs region by region
@@ -360,6 +359,18 @@ void fused_geom(const int *out_shape, int G, int batch, int tune, TileGeom &tg, 
         t = xmarch_default_tune();
         tile_geometry(out_shape, G, t, t, tg, nblocks);
     }
+    if (((t >> 14) & 1) && !tg.plane_major) {
+        // x-march: a pass is 256 / G voxels of ONE x-plane run of the patch, and the kernel marches npass = xlen * patch / (256 / G)
+        // passes.  tile_geometry only makes ltx + lty + ltz cover a pass; a (y,z) patch smaller than a pass would round npass down and
+        // leave the last planes of a piece unwarped (status NRT_OK).  Widen the patch along y until it holds a pass
+        int lty = tg.lty;
+        while ((1 << (lty + tg.ltz)) < 256 / G) ++lty;
+        if (lty != tg.lty) {
+            t = (t & ~((15 << 4) | (15 << 8))) | (lty << 4) | (tg.ltz << 8);
+            tile_geometry(out_shape, G, t, t, tg, nblocks);
+        }
+    }
+    if (nblocks > (unsigned)DICE_MAX_BLOCKS) nblocks = DICE_MAX_BLOCKS;        // multiple of 8; blocks loop over tiles
     if (((t >> 14) & 1) && !tg.plane_major && out_shape[0] > 0) {
         // segments left to us (bits 16-23 zero): whole columns + pieces for the last round; an explicit count: equal pieces
         unsigned grid;

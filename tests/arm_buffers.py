@@ -1,7 +1,7 @@
 """
 Guarded device buffers for the tests that call the C ABI directly (tests/test_gpu_dispatch_arms.py,
 tests/test_gpu_warp_backward_arms.py, tests/test_gpu_filter_arms.py, tests/test_gpu_conv_fwd_arms.py, tests/test_gpu_lc3d_arms.py,
-tests/test_gpu_conv_bf16_arms.py, tests/test_gpu_warp_forward_arms.py, tests/test_gpu_dice_cce_arms.py): the alignment of every pointer is exact, and a write outside an output is caught.
+tests/test_gpu_conv_bf16_arms.py, tests/test_gpu_warp_forward_arms.py, tests/test_gpu_dice_cce_arms.py, tests/test_gpu_warp_dice_arms.py): the alignment of every pointer is exact, and a write outside an output is caught.
 """
 
 import numpy as np

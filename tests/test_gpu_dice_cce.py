@@ -3,6 +3,8 @@ GPU parity tests of Dice (soft / hard) and label-weighted categorical cross-entr
 vectors of the reference's own source and against the oracle.
 Tolerances: hard / one-hot Dice BIT-EXACT (integer counting); soft Dice and CCE 1e-5 relative
 (float32 reduction order is unspecified in TensorFlow; the oracle accumulates in float64).
+The fused warp + Dice tests of this file go through neurite_amd.fused (SHIFT mode) and hold the sums to 1e-5; every dispatch arm of
+those kernels, in all three location modes, with exact sums and a derived bound, is in tests/test_gpu_warp_dice_arms.py.
 """
 
 import os

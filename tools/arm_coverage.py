@@ -36,6 +36,10 @@ interpn_any_kernels.txt): 210 instances.  The 18 instances interpn_lean<C, VPL, 
 --families dice checks the Dice reductions of csrc/dice.hip and csrc/dice_reduce.h, --families cce the weighted cross-entropy of
 csrc/cce.hip (tests/test_gpu_dice_cce_arms.py; kernel tables profiles/dispatch_arms/dice_kernels.txt and cce_kernels.txt): 107 and 60
 instances, every one reachable.
+
+--families warp_dice checks the fused warp + soft Dice forward of csrc/fused.hip and csrc/fused_wc.h (tests/test_gpu_warp_dice_arms.py;
+kernel table profiles/dispatch_arms/fused_kernels.txt): 168 warp_dice_tile, 144 warp_dice_tile_pad and 60 warp_dice_wc instances.  96
+are unreachable: the 78 with STORE = true on bfloat16 storage and the other 18 of warp_dice_tile_pad<2, ...>.
 """
 import argparse
 import csv
@@ -89,13 +93,20 @@ DICE_FAMILIES = [r'dice_soft_vec<\d+,(?:false|true),%s>' % _ST, r'dice_soft_gene
                  r'dice_soft_finalize', r'dice_counts_reduce', r'dice_from_counts', r'dice_from_sums', r'dice_mean_pair', r'minmax_rows']
 # the dispatcher of nrt_wcce / nrt_wcce_mean (csrc/cce.hip): the whole translation unit but nrt_zero_words
 CCE_FAMILIES = [r'wcce_vec<\d+,%s,(?:false|true),(?:false|true)>' % _T, r'wcce_generic<%s,(?:false|true)>' % _T]
-FAMILY_SETS = {'conv': FAMILIES, 'dice': DICE_FAMILIES, 'cce': CCE_FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
+# the dispatchers of nrt_warp_dice_soft_f32 / nrt_warp_dice_soft_bf16 (csrc/fused.hip, csrc/fused_wc.h) and, for the wave-cache kernel without
+# its Dice half, of nrt_interpn_f32_ex variant 10 (the backward warp_dice_wc_bwd is another family)
+_B = r'(?:false|true)'
+WARP_DICE_FAMILIES = [r'warp_dice_tile<\d+,\d+,%s,\d+,%s>' % (_B, _T), r'warp_dice_tile_pad<\d+,\d+,%s,\d+,%s>' % (_B, _T),
+                      r'warp_dice_wc<\d+,%s,%s,%s,%s,%s>' % (_B, _B, _B, _B, _B)]
+FAMILY_SETS = {'conv': FAMILIES, 'warp_dice': WARP_DICE_FAMILIES, 'dice': DICE_FAMILIES, 'cce': CCE_FAMILIES, 'warp_bwd': WARP_BWD_FAMILIES, 'conv_wgrad': CONV_WGRAD_FAMILIES, 'conv_fwd': CONV_FWD_FAMILIES,
                'lc3d': LC3D_FAMILIES, 'conv_bf16': CONV_BF16_FAMILIES, 'warp_fwd': WARP_FWD_FAMILIES}
 # instances no contract-conforming call can launch: the per-parity-group folded form is only taken when a pointer is not 16-byte
 # aligned, which include/neurite_amd.h rules out; a bfloat16 patch the matrix-core forward accepts has at most 56 16-byte pieces, so
 # its two-pieces-per-lane form (NPC = 2, more than 64) never runs; nrt_lean_launch sends every call with per-voxel locations (ABSOLUTE = 0,
-# SHIFT = 1) to interpn_lean_tile, so the row form interpn_lean only runs in LINSPACE mode (profiles/dispatch_arms/README.md)
-UNREACHABLE = {'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
+# SHIFT = 1) to interpn_lean_tile, so the row form interpn_lean only runs in LINSPACE mode; nrt_warp_dice_soft_bf16 has no `warped`
+# parameter and the implementation refuses `warped` for 16-bit storage, so STORE = true never meets unsigned short, and fused_group
+# gives G = 2 for 8 labels only, which is no padded count, so warp_dice_tile_pad<2, ...> is never chosen (profiles/dispatch_arms/README.md)
+UNREACHABLE = {'warp_dice': [r'warp_dice_tile(?:_pad)?<\d+,\d+,true,\d+,unsignedshort>', r'warp_dice_tile_pad<2,.*>'], 'conv': [], 'warp_bwd': [], 'conv_wgrad': [r'conv3d_wgrad<\d+,\d+,3,2,false>'], 'conv_fwd': [],
                'lc3d': [r'lc3d_fwd_mfma<unsignedshort,\d+,\d+,\d+,2>'], 'conv_bf16': [], 'dice': [], 'cce': [], 'warp_fwd': [r'interpn_lean<\d+,\d+,[01]>']}
 FAMILY = re.compile('^(?:%s)$' % '|'.join(FAMILIES))
 
