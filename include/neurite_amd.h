@@ -10,7 +10,11 @@
  *
  * Conventions
  *  - All tensor pointers are DEVICE pointers (HIP), row-major, channels-last, exactly the
- *    reference layout [B, *spatial, C]; int* shape arguments are HOST pointers.
+ *    reference layout [B, *spatial, C].
+ *  - The spelling of a parameter says where its memory lives: `T name[]` is a HOST array that is
+ *    read during the call (shapes, kernel sizes, voxel spacings, percentile positions); `T *name`
+ *    is DEVICE memory or an opaque handle (`void *stream`).  The Python binding derives its
+ *    argument types from these declarations (neurite_amd/_lib.py).
  *  - Every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default
  *    stream), allocates nothing and never synchronises.  Scratch memory is supplied by the
  *    caller: ask nrt_*_workspace_bytes() and pass a device buffer of at least that size.
@@ -87,7 +91,7 @@ typedef enum { NRT_INTERP_LINEAR = 0, NRT_INTERP_NEAREST = 1 } nrt_interp_method
  * round-half-even, pure data movement; fill: out*(!oob) + oob*fill on the UNCLIPPED location.
  */
 int nrt_interpn_f32(const float *vol, const float *loc, float *out,
-                    int ndim, const int *vol_shape, const int *out_shape, int channels,
+                    int ndim, const int vol_shape[], const int out_shape[], int channels,
                     int batch, long long vol_batch_stride, long long loc_batch_stride,
                     int loc_mode, int method, int has_fill, float fill_value, void *stream);
 
@@ -101,14 +105,14 @@ int nrt_interpn_f32(const float *vol, const float *loc, float *out,
  *   any other value: NRT_ERR_INVALID_ARG
  * tune: variant-specific knob (variant 3: z-chunk length | order | patch | region bits; variant 5: tile geometry). */
 int nrt_interpn_f32_ex(const float *vol, const float *loc, float *out,
-                       int ndim, const int *vol_shape, const int *out_shape, int channels,
+                       int ndim, const int vol_shape[], const int out_shape[], int channels,
                        int batch, long long vol_batch_stride, long long loc_batch_stride,
                        int loc_mode, int method, int has_fill, float fill_value,
                        int variant, int tune, void *stream);
 
 /* Nearest-neighbour lookup on int32 volumes (label maps); fill arithmetic done in int32. */
 int nrt_interpn_nearest_i32(const int32_t *vol, const float *loc, int32_t *out,
-                            int ndim, const int *vol_shape, const int *out_shape, int channels,
+                            int ndim, const int vol_shape[], const int out_shape[], int channels,
                             int batch, long long vol_batch_stride, long long loc_batch_stride,
                             int loc_mode, int has_fill, int32_t fill_value, void *stream);
 
@@ -117,8 +121,8 @@ int nrt_interpn_nearest_i32(const int32_t *vol, const float *loc, int32_t *out,
  * 4..8 dimensions (TensorFlow itself stops at rank-8 tensors).  `dtype` is an nrt_dtype value (below).  loc is cast to the volume dtype and the arithmetic runs in that
  * dtype, one rounding per operation, as TensorFlow evaluates it.  loc: float32 [batch, out_shape, ndim] (float64 when
  * loc_is_f64, float64 volumes with NRT_LOC_ABSOLUTE only), NULL for NRT_LOC_LINSPACE.  vol / out are `dtype`. */
-int nrt_interpn_any(const void *vol, const void *loc, void *out, int dtype, int ndim, const int *vol_shape,
-                    const int *out_shape, int channels, int batch, long long vol_batch_stride,
+int nrt_interpn_any(const void *vol, const void *loc, void *out, int dtype, int ndim, const int vol_shape[],
+                    const int out_shape[], int channels, int batch, long long vol_batch_stride,
                     long long loc_batch_stride, int loc_mode, int loc_is_f64, int method, int has_fill,
                     double fill_value, void *stream);
 
@@ -127,14 +131,14 @@ int nrt_interpn_any(const void *vol, const void *loc, void *out, int dtype, int 
  * neurite/tf/models.py:802-804, 1131, 1149-1154 (VecInt / ComposeTransform next to SpatialTransformer).
  * addend [batch, out_shape, channels]; same rounding as the two separate TF ops (interp, then one add). */
 int nrt_interpn_add_f32(const float *vol, const float *loc, const float *addend, float *out, int ndim,
-                        const int *vol_shape, const int *out_shape, int channels, int batch,
+                        const int vol_shape[], const int out_shape[], int channels, int batch,
                         long long vol_batch_stride, long long loc_batch_stride, long long addend_batch_stride,
                         int loc_mode, int has_fill, float fill_value, void *stream);
 
 /* voxelmorph.utils.affine_to_dense_shift ('ij' indexing; called on affine inputs of SpatialTransformer / AffineToDenseShift and by
  * the synthesis models, neurite/tf/models.py:1131-1154): out[b, q, :] = A_b [q - c; 1] - (q - c), c = (shape - 1) / 2 when
  * shift_center else 0.  matrix [batch, ndim, ndim + 1], out [batch, *shape, ndim]; ndim 2 or 3. */
-int nrt_affine_to_dense_shift_f32(const float *matrix, int batch, int ndim, const int *shape, int shift_center, float *out,
+int nrt_affine_to_dense_shift_f32(const float *matrix, int batch, int ndim, const int shape[], int shift_center, float *out,
                                   void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -230,9 +234,9 @@ int nrt_dice_mean_f32(const float *dice, const float *weights, int nlabels, int 
  * fixed / warped below 4 GiB, shape[0] * shape[1] and shape[2] below 2^24 for both shapes (32-bit row offsets, 24-bit
  * index multiplies).
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_warp_dice_workspace_bytes(const int *out_shape, int nlabels, int batch, int tune);
+size_t nrt_warp_dice_workspace_bytes(const int out_shape[], int nlabels, int batch, int tune);
 int nrt_warp_dice_soft_f32(const float *moving, const float *loc, const float *fixed, float *warped,
-                           const int *vol_shape, const int *out_shape, int nlabels, int batch,
+                           const int vol_shape[], const int out_shape[], int nlabels, int batch,
                            long long loc_batch_stride, int loc_mode, int has_fill, float fill_value,
                            float laplace_smoothing, float *sums, float *dice, float *minmax,
                            int tune, void *workspace, size_t workspace_bytes, void *stream);
@@ -243,8 +247,8 @@ int nrt_warp_dice_soft_f32(const float *moving, const float *loc, const float *f
  * sums / dice are bit-identical to nrt_warp_dice_soft_f32 on the widened maps.  An extension of this package (the reference
  * has no fused form; TensorFlow would blend bfloat16 tensors in bfloat16 -- nrt_interpn_any does that for interpn).
  * No `warped` output. */
-int nrt_warp_dice_soft_bf16(const void *moving, const float *loc, const void *fixed, const int *vol_shape,
-                            const int *out_shape, int nlabels, int batch, long long loc_batch_stride, int loc_mode,
+int nrt_warp_dice_soft_bf16(const void *moving, const float *loc, const void *fixed, const int vol_shape[],
+                            const int out_shape[], int nlabels, int batch, long long loc_batch_stride, int loc_mode,
                             int has_fill, float fill_value, float laplace_smoothing, float *sums, float *dice,
                             float *minmax, int tune, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -252,7 +256,7 @@ int nrt_warp_dice_soft_bf16(const void *moving, const float *loc, const void *fi
  * "warp_dice_tile<8, 1, false, 3, float>", "warp_dice_tile_pad<8, 1, false, 3, float>" for 24 labels); "" for arguments the entry
  * point rejects.  The returned buffer is thread-local.
  * Measurement plumbing (bench.py joins its timing with the counter passes under profiles/ by this name); no reference counterpart. */
-const char *nrt_warp_dice_kernel_name(const int *out_shape, const int *vol_shape, int nlabels, int batch, int loc_mode, int has_fill,
+const char *nrt_warp_dice_kernel_name(const int out_shape[], const int vol_shape[], int nlabels, int batch, int loc_mode, int has_fill,
                                       int store, int want_minmax, int tune);
 
 /* ------------------------------------------------------------------------------------------
@@ -272,14 +276,14 @@ const char *nrt_warp_dice_kernel_name(const int *out_shape, const int *vol_shape
  * The backward is wrt loc only: grad_loc [batch, out_shape, 3] from the forward's sums and grad_dice [batch, nlabels]; it is 0 for
  * out-of-bounds voxels when has_fill is set, and for a label whose denominator is 0.
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_warp_dice_labels_workspace_bytes(const int *out_shape, int nlabels, int batch);
+size_t nrt_warp_dice_labels_workspace_bytes(const int out_shape[], int nlabels, int batch);
 int nrt_warp_dice_labels_f32(const int32_t *moving, const float *loc, const int32_t *fixed, float *warped /* or NULL */,
-                             const int *vol_shape, const int *out_shape, int nlabels, int batch,
+                             const int vol_shape[], const int out_shape[], int nlabels, int batch,
                              long long loc_batch_stride, int loc_mode, int has_fill, float fill_value,
                              float laplace_smoothing, float *sums, float *dice,
                              void *workspace, size_t workspace_bytes, void *stream);
 int nrt_warp_dice_labels_bwd_f32(const int32_t *moving, const float *loc, const int32_t *fixed, const float *sums,
-                                 const float *grad_dice, float *grad_loc, const int *vol_shape, const int *out_shape,
+                                 const float *grad_dice, float *grad_loc, const int vol_shape[], const int out_shape[],
                                  int nlabels, int batch, long long loc_batch_stride, int loc_mode, int has_fill,
                                  float laplace_smoothing, void *stream);
 
@@ -328,8 +332,8 @@ typedef enum { NRT_ACT_NONE = 0, NRT_ACT_ELU = 1, NRT_ACT_RELU = 2, NRT_ACT_SIGM
 #define NRT_ACT_MUL_B 0x100
 
 /* Weights re-ordered for the MFMA kernel ("packed"): query the size, pack once per layer. */
-size_t nrt_conv3d_packed_weight_floats(const int *ksize, int cin, int cout);
-int nrt_conv3d_pack_weights_f32(const float *weights /* Keras [kx,ky,kz,cin,cout] */, const int *ksize,
+size_t nrt_conv3d_packed_weight_floats(const int ksize[], int cin, int cout);
+int nrt_conv3d_pack_weights_f32(const float *weights /* Keras [kx,ky,kz,cin,cout] */, const int ksize[],
                                 int cin, int cout, float *packed, void *stream);
 
 /*
@@ -345,9 +349,9 @@ int nrt_conv3d_pack_weights_f32(const float *weights /* Keras [kx,ky,kz,cin,cout
  * direct kernel under variant 0, except that the 2x2x2 arm is taken where it has been measured faster (profiles/conv_even: 16 .. 64
  * channels on both sides and at least 4 * 40^3 output voxels over the batch).
  */
-int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const int *up,
+int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const int up[],
                    const float *weights, const float *packed_weights, const float *bias, float *out,
-                   int batch, const int *shape, const int *ksize, int cout, int dilation,
+                   int batch, const int shape[], const int ksize[], int cout, int dilation,
                    int padding_same, int activation, int variant, void *stream);
 
 /*
@@ -357,18 +361,18 @@ int nrt_conv3d_f32(const float *src0, int c0, const float *src1, int c1, const i
  * while it is in LDS instead of reading the full-resolution tensor back.  3x3x3 SAME, weights in Keras layout [3,3,3,1,cout],
  * cout 16 or 32, shape a multiple of (4, 4, 16); bit-identical to nrt_conv3d_f32 followed by nrt_maxpool3d_f32.
  */
-int nrt_conv3d_c1_pool_supported(const int *shape, int cout);
+int nrt_conv3d_c1_pool_supported(const int shape[], int cout);
 int nrt_conv3d_c1_pool_f32(const float *src /* [batch, shape, 1] */, const float *weights, const float *bias, float *out,
-                           float *pool_out, int batch, const int *shape, int cout, int activation, void *stream);
+                           float *pool_out, int batch, const int shape[], int cout, int activation, void *stream);
 /*
  * The same pattern below the first level (round 6): a 3x3x3 SAME convolution over c0 = 16 k input channels (packed weights of
  * nrt_conv3d_pack_weights_f32) and the MaxPooling3D(2) of its activated output from one kernel (models.py:1378-1388 + 1436-1438) --
  * `out` [batch, shape, cout] as nrt_conv3d_f32 (variant 5) writes it, `pool_out` [batch, shape / 2, cout] in addition.  cout 32, 48 or
  * 64, shape a multiple of (4, 4, 16); bit-identical to nrt_conv3d_f32 followed by nrt_maxpool3d_f32.
  */
-int nrt_conv3d_pool_supported(int c0, int cout, const int *shape, int batch);
+int nrt_conv3d_pool_supported(int c0, int cout, const int shape[], int batch);
 int nrt_conv3d_pool_f32(const float *src /* [batch, shape, c0] */, int c0, const float *packed_weights, const float *bias, float *out,
-                        float *pool_out, int batch, const int *shape, int cout, int activation, void *stream);
+                        float *pool_out, int batch, const int shape[], int cout, int activation, void *stream);
 
 /*
  * The decoder convolution of models.unet (neurite/tf/models.py:1531-1555: UpSampling3D(2) -> concatenate([skip, up]) ->
@@ -380,11 +384,11 @@ int nrt_conv3d_pool_f32(const float *src /* [batch, shape, c0] */, int c0, const
  *   nrt_conv3d_up2_packed_weight_floats size of the folded, fragment-ordered weights
  *   nrt_conv3d_up2_pack_weights_f32     weights Keras layout [3,3,3,c0+c1,cout] -> packed
  */
-int nrt_conv3d_up2_supported(int c0, int c1, int cout, const int *shape);
+int nrt_conv3d_up2_supported(int c0, int c1, int cout, const int shape[]);
 size_t nrt_conv3d_up2_packed_weight_floats(int c0, int c1, int cout);
 int nrt_conv3d_up2_pack_weights_f32(const float *weights, int c0, int c1, int cout, float *packed, void *stream);
 int nrt_conv3d_up2_f32(const float *skip /* [batch, shape, c0] */, int c0, const float *lo /* [batch, shape/2, c1] */, int c1,
-                       const float *packed_weights, const float *bias, float *out, int batch, const int *shape, int cout,
+                       const float *packed_weights, const float *bias, float *out, int batch, const int shape[], int cout,
                        int activation, void *stream);
 /*
  * The LAST decoder convolution of models.unet with the network's head folded in (neurite/tf/models.py:1545-1555 the convolution,
@@ -395,11 +399,11 @@ int nrt_conv3d_up2_f32(const float *skip /* [batch, shape, c0] */, int c0, const
  * fragment order), both head arrays 16-byte aligned.  Same values as nrt_conv3d_up2_f32 followed by nrt_conv1x1_softmax_f32 up
  * to the float32 summation order of the 16-term head products.
  */
-int nrt_conv3d_up2_head_supported(int c0, int c1, int cout, int labels, const int *shape);
+int nrt_conv3d_up2_head_supported(int c0, int c1, int cout, int labels, const int shape[]);
 int nrt_conv3d_up2_head_pack_f32(const float *head_weights /* [16, labels] */, int labels, float *packed /* [16 * labels] */, void *stream);
 int nrt_conv3d_up2_head_f32(const float *skip, int c0, const float *lo, int c1, const float *packed_weights, const float *bias,
                             const float *packed_head_weights, const float *head_bias /* [labels] */, int labels,
-                            float *out /* [batch, shape, labels] */, int batch, const int *shape, int cout, int activation,
+                            float *out /* [batch, shape, labels] */, int batch, const int shape[], int cout, int activation,
                             void *stream);
 
 /*
@@ -411,8 +415,8 @@ int nrt_conv3d_up2_head_f32(const float *skip, int c0, const float *lo, int c1, 
  *                             use the taps e = (p ? 1 : 2) - t, t in {0, 1}, per axis (all other weights are taken as zero);
  *                             packed_weights = nrt_conv3d_pack_weights_f32 of [3,3,3, 8 * group, cout]; group % 16 == 0
  */
-int nrt_space_to_depth2_f32(const float *x, float *y, int batch, const int *shape, int channels, void *stream);
-int nrt_conv3d_s2d_taps_f32(const float *x, int group, const float *packed_weights, float *out, int batch, const int *shape,
+int nrt_space_to_depth2_f32(const float *x, float *y, int batch, const int shape[], int channels, void *stream);
+int nrt_conv3d_s2d_taps_f32(const float *x, int group, const float *packed_weights, float *out, int batch, const int shape[],
                             int cout, void *stream);
 
 /* 1x1 convolution with the channel softmax (or an activation) fused; cout <= 64. x [nvox, cin]. */
@@ -421,11 +425,11 @@ int nrt_conv1x1_softmax_f32(const float *x, const float *weights /* [cin, cout] 
                             void *stream);
 int nrt_softmax_lastdim_f32(const float *x, float *y, long long n, int channels, void *stream);
 /* MaxPooling3D, stride = pool; SAME keeps partial windows (output ceil(n/p)), VALID drops them. */
-int nrt_maxpool3d_f32(const float *x, float *y, int batch, const int *shape, int channels,
-                      const int *pool, int padding_same, void *stream);
+int nrt_maxpool3d_f32(const float *x, float *y, int batch, const int shape[], int channels,
+                      const int pool[], int padding_same, void *stream);
 /* y = concat(skip [batch, shape, c0] (may be NULL with c0 = 0), upsample_nearest(lo [batch, shape/up, c1])) */
 int nrt_upsample_concat_f32(const float *skip, int c0, const float *lo, int c1, float *y, int batch,
-                            const int *shape, const int *up, void *stream);
+                            const int shape[], const int up[], void *stream);
 /* y = act(a + b) * scale[c] + shift[c]   (b, scale/shift optional): residual merge / inference BatchNorm */
 int nrt_add_act_affine_f32(const float *a, const float *b, const float *scale, const float *shift,
                            float *y, long long n, int channels, int activation, void *stream);
@@ -444,18 +448,18 @@ int nrt_add_act_affine_f32(const float *a, const float *b, const float *scale, c
  *   nrt_conv1x1_softmax_bf16             weights bf16 [cin, cout], cout <= 64
  *   nrt_softmax_lastdim_bf16, nrt_maxpool3d_bf16, nrt_upsample_concat_bf16, nrt_add_act_affine_bf16: as the float32 forms
  *   (pooling and up-sampling are exact).  No atomics: results are run-to-run bit-identical. */
-size_t nrt_conv3d_packed_weight_bytes_bf16(const int *ksize, int cin, int cout);
-int nrt_conv3d_pack_weights_bf16(const void *weights, int dtype, const int *ksize, int cin, int cout, void *packed, void *stream);
-int nrt_conv3d_bf16(const void *src0, int c0, const void *src1, int c1, const int *up, const void *packed_weights,
-                    const float *bias, void *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
+size_t nrt_conv3d_packed_weight_bytes_bf16(const int ksize[], int cin, int cout);
+int nrt_conv3d_pack_weights_bf16(const void *weights, int dtype, const int ksize[], int cin, int cout, void *packed, void *stream);
+int nrt_conv3d_bf16(const void *src0, int c0, const void *src1, int c1, const int up[], const void *packed_weights,
+                    const float *bias, void *out, int batch, const int shape[], const int ksize[], int cout, int dilation,
                     int padding_same, int activation, void *stream);
 int nrt_conv1x1_softmax_bf16(const void *x, const void *weights, const float *bias, void *y, long long nvox, int cin, int cout,
                              int softmax, int activation, void *stream);
 int nrt_softmax_lastdim_bf16(const void *x, void *y, long long n, int channels, void *stream);
-int nrt_maxpool3d_bf16(const void *x, void *y, int batch, const int *shape, int channels, const int *pool, int padding_same,
+int nrt_maxpool3d_bf16(const void *x, void *y, int batch, const int shape[], int channels, const int pool[], int padding_same,
                        void *stream);
-int nrt_upsample_concat_bf16(const void *skip, int c0, const void *lo, int c1, void *y, int batch, const int *shape,
-                             const int *up, void *stream);
+int nrt_upsample_concat_bf16(const void *skip, int c0, const void *lo, int c1, void *y, int batch, const int shape[],
+                             const int up[], void *stream);
 int nrt_add_act_affine_bf16(const void *a, const void *b, const float *scale, const float *shift, void *y, long long n,
                             int channels, int activation, void *stream);
 
@@ -478,23 +482,23 @@ int nrt_add_act_affine_bf16(const void *a, const void *b, const float *scale, co
  * ------------------------------------------------------------------------------------------ */
 int nrt_act_bwd_f32(const float *grad_out, const float *y, int activation, float *grad_pre, long long n, void *stream);
 int nrt_conv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad_weights, float *grad_bias, int batch,
-                         const int *shape, int cin, int cout, const int *ksize, int dilation, void *stream);
+                         const int shape[], int cin, int cout, const int ksize[], int dilation, void *stream);
 /* the same with the forward kernel's fused loader: the layer input was concat(x [.., c0], UpSampling3D(x_lo [.., c1])), which
  * is read from its two sources and never materialised (c0 % 4 == 0; x_lo may be NULL with c1 = 0) */
-int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, int c1, const int *up, const float *grad_pre,
-                          float *grad_weights, float *grad_bias, int batch, const int *shape, int cout, const int *ksize,
+int nrt_conv3d_wgrad2_f32(const float *x, int c0, const float *x_lo, int c1, const int up[], const float *grad_pre,
+                          float *grad_weights, float *grad_bias, int batch, const int shape[], int cout, const int ksize[],
                           int dilation, void *stream);
 /* folded form for the up-sampled channels of a decoder convolution (see nrt_conv3d_up2_f32): x_lo [batch, shape, cin] is the
  * low-resolution tensor, grad_pre_s2d [batch, shape, 8 * group] = nrt_space_to_depth2_f32 of the layer's grad_pre (group = cout);
  * grad_folded [8 parity groups][8 taps (tx, ty, tz)][cin][group] += sum_q x_lo[q + p + t - 1] (x) grad_pre_s2d[q][P], ZERO-FILLED by
  * the caller; the 27-tap gradient is dW[d] = sum over the (p, t) with d in S(p, t) per axis (S(0,0) = {0}, S(0,1) = {1,2},
  * S(1,0) = {0,1}, S(1,1) = {2}) -- a 27 x 64 matrix product over cin * group values (host side) */
-int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre_s2d, float *grad_folded, int batch, const int *shape, int cin,
+int nrt_conv3d_wgrad_s2d_f32(const float *x_lo, const float *grad_pre_s2d, float *grad_folded, int batch, const int shape[], int cin,
                              int group, void *stream);
-int nrt_maxpool3d_bwd_f32(const float *x, const float *grad_out, float *grad_x, int batch, const int *shape,
-                          int channels, const int *pool, int padding_same, void *stream);
+int nrt_maxpool3d_bwd_f32(const float *x, const float *grad_out, float *grad_x, int batch, const int shape[],
+                          int channels, const int pool[], int padding_same, void *stream);
 int nrt_upsample_sum_f32(const float *grad_up, int grad_channels, int channel_offset, float *grad_lo, int channels,
-                         int batch, const int *lo_shape, const int *up, void *stream);
+                         int batch, const int lo_shape[], const int up[], void *stream);
 int nrt_softmax_bwd_f32(const float *y, const float *grad_out, float *grad_in, long long nvox, int channels, void *stream);
 /* BatchNormalization in training mode (Keras axis -1; models.py:1431-1434, 1585-1588): per-channel sums over [rows, channels],
  * out[c] += sum_r a[r][c] * (b ? b[r][c] : 1)  (ZERO-FILLED by the caller), and y = coef_a[c] a + coef_b[c] b + coef_c[c] */
@@ -514,11 +518,11 @@ int nrt_channel_axpby_f32(const float *a, const float *b, const float *coef_a, c
  * transpose_flip != 0: per entry the kernel flipped in space and transposed in its channel axes is packed instead -- the weights of the
  * input gradient (what tf.GradientTape derives for :2607-2611), a convolution from cout to cin channels: packed
  * [batch, nrt_conv3d_packed_weight_floats(ksize, cout, cin)]. */
-int nrt_hyperconv3d_pack_weights_f32(const float *weights, int batch, const int *ksize, int cin, int cout, int transpose_flip,
+int nrt_hyperconv3d_pack_weights_f32(const float *weights, int batch, const int ksize[], int cin, int cout, int transpose_flip,
                                      float *packed, void *stream);
 /* 1 when nrt_hyperconv3d_f32 (variant 0) runs these arguments on the matrix cores and therefore reads `packed_weights` (then `weights`
  * may be NULL); 0 when it reads `weights` in the Keras layout.  The rule of nrt_conv3d_f32; no reference counterpart. */
-int nrt_hyperconv3d_uses_packed(const int *shape, const int *ksize, int cin, int cout, int dilation, int padding_same);
+int nrt_hyperconv3d_uses_packed(const int shape[], const int ksize[], int cin, int cout, int dilation, int padding_same);
 /* out[b] = act(conv3d(src[b], W[b]) + bias[b]), cross-correlation, SAME or VALID: neurite/tf/layers.py:2592-2612 with the bias and
  * activation of call (:2580-2590).
  *   src [batch, shape, cin]; weights [batch, kx,ky,kz, cin, cout] or NULL; packed_weights from nrt_hyperconv3d_pack_weights_f32 or NULL
@@ -528,14 +532,14 @@ int nrt_hyperconv3d_uses_packed(const int *shape, const int *ksize, int cin, int
  * ReLU, NRT_ERR_INVALID_ARG beyond) and limits are those of nrt_conv3d_f32; there is no second source and no pool / head fold.
  * No atomics: run-to-run bit-identical, and bit-identical to nrt_conv3d_f32 per entry when every entry carries the same set. */
 int nrt_hyperconv3d_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias, float *out,
-                        int batch, const int *shape, const int *ksize, int cout, int dilation, int padding_same, int activation,
+                        int batch, const int shape[], const int ksize[], int cout, int dilation, int padding_same, int activation,
                         int variant, void *stream);
 /* Per-entry weight and bias gradient (what tf.GradientTape derives for neurite/tf/layers.py:2580-2612 with respect to the kernel and
  * bias inputs): grad_weights [batch, kx,ky,kz, cin, cout] and grad_bias [batch, cout] (or NULL), NOT summed over the batch.  Contract of
  * nrt_conv3d_wgrad_f32 otherwise: SAME padding, both outputs ZERO-FILLED by the caller (float atomics, one per weight and block: the sums
  * are not run-to-run bit-identical), ksize entries 1 .. 4, dilation <= 2.  A block only accumulates tiles of one batch entry. */
 int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad_weights, float *grad_bias, int batch,
-                              const int *shape, int cin, int cout, const int *ksize, int dilation, void *stream);
+                              const int shape[], int cin, int cout, const int ksize[], int dilation, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * LocallyConnected3D, implementation 1 ('valid' padding, channels-last)
@@ -548,7 +552,7 @@ int nrt_hyperconv3d_wgrad_f32(const float *x, const float *grad_pre, float *grad
  * variant 0 auto | 1 generic | 2 weight-streaming wave-per-position kernels.
  * ------------------------------------------------------------------------------------------ */
 int nrt_lc3d_f(const void *x, const void *kernel, const void *bias, void *y, int dtype, int batch,
-               const int *in_shape, int cin, const int *ksize, const int *strides, int cout,
+               const int in_shape[], int cin, const int ksize[], const int strides[], int cout,
                int activation, int variant, void *stream);
 /* Backward of the same layer (autodiff of the batch_dot of layers.py:1189 + bias/activation :1098-1101):
  *   grad_kernel [O, F, cout] and grad_bias [O, cout] (`dtype`, written once, may be NULL), grad_x float32
@@ -556,15 +560,15 @@ int nrt_lc3d_f(const void *x, const void *kernel, const void *bias, void *y, int
  *   y = the layer output (needed when activation != 0), grad_out [batch, out_shape, cout].
  *   cout * itemsize must be a multiple of 16 (the weight-streaming lane layout). */
 int nrt_lc3d_bwd_f(const void *x, const void *kernel, const void *y, const void *grad_out, void *grad_kernel,
-                   void *grad_bias, float *grad_x, int dtype, int batch, const int *in_shape, int cin,
-                   const int *ksize, const int *strides, int cout, int activation, void *stream);
+                   void *grad_bias, float *grad_x, int dtype, int batch, const int in_shape[], int cin,
+                   const int ksize[], const int strides[], int cout, int activation, void *stream);
 
 /* Zero-pad (crop == 0) a channels-last volume [batch, in_shape, row] into [batch, out_shape, row] with pad_before voxels
  * in front of every axis, or (crop != 0) copy the interior of a padded volume back out -- `in` is then the padded
  * [batch, out_shape, row] tensor and `out` the [batch, in_shape, row] one.  row_bytes = channels * itemsize (even).
  * padding='same' of LocallyConnected3D implementations 2 / 3 (neurite/tf/layers.py:934-936, 1474-1482: the window is
  * clipped at the border) is the 'valid' layer on the input padded by kernel_size // 2; the crop is its gradient. */
-int nrt_pad3d(const void *in, void *out, int batch, const int *in_shape, const int *pad_before, const int *out_shape,
+int nrt_pad3d(const void *in, void *out, int batch, const int in_shape[], const int pad_before[], const int out_shape[],
               int row_bytes, int crop, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -582,15 +586,15 @@ int nrt_pad3d(const void *in, void *out, int batch, const int *in_shape, const i
  *   upstream gradient either one device scalar (grad_scalar) or per voxel (grad_per_voxel), times `scale`.
  * ------------------------------------------------------------------------------------------ */
 int nrt_interpn_bwd_f32(const float *vol, const float *loc, const float *grad_out, float *grad_vol,
-                        float *grad_loc, int ndim, const int *vol_shape, const int *out_shape, int channels,
+                        float *grad_loc, int ndim, const int vol_shape[], const int out_shape[], int channels,
                         int batch, long long vol_batch_stride, long long loc_batch_stride, int loc_mode,
                         int has_fill, void *stream);
 
 /* Backward of nearest-neighbour interpn (neurite/tf/utils/utils.py:193-204) wrt the volume: tf.gather's scatter-add of
  * grad_out [batch, out_shape, channels] into grad_vol [batch, vol_shape, channels] (ZERO-FILLED by the caller; float atomics),
  * masked where a fill value applies.  The location has no gradient (tf.round). */
-int nrt_interpn_nearest_bwd_f32(const float *loc, const float *grad_out, float *grad_vol, int ndim, const int *vol_shape,
-                                const int *out_shape, int channels, int batch, long long vol_batch_stride,
+int nrt_interpn_nearest_bwd_f32(const float *loc, const float *grad_out, float *grad_vol, int ndim, const int vol_shape[],
+                                const int out_shape[], int channels, int batch, long long vol_batch_stride,
                                 long long loc_batch_stride, int loc_mode, int has_fill, void *stream);
 int nrt_dice_soft_bwd_f32(const float *y_true, const float *y_pred, const float *sums, const float *grad_dice,
                           long long nvox, int nlabels, int batch, float laplace_smoothing, float *grad_pred,
@@ -608,7 +612,7 @@ int nrt_dice_soft_bwd_norm_f32(const float *y_true, const float *y_pred, const f
  * register-pipelined kernel of rounds 2-4: same bits); the grad_loc of nrt_interpn_bwd_f32 at 32 channels likewise.  nlabels: the
  * forward's counts (a multiple of 4 in [4, 256]); counts that are not 4 * 2^k run on padded lane groups, without atomics. */
 int nrt_warp_dice_bwd_f32(const float *moving, const float *loc, const float *fixed, const float *sums,
-                          const float *grad_dice, float *grad_loc, const int *vol_shape, const int *out_shape,
+                          const float *grad_dice, float *grad_loc, const int vol_shape[], const int out_shape[],
                           int nlabels, int batch, long long loc_batch_stride, int loc_mode, int has_fill,
                           float laplace_smoothing, void *stream);
 int nrt_wcce_bwd_f32(const float *y_true, const float *y_pred, const float *label_weights,
@@ -859,10 +863,10 @@ int nrt_dense_bwd_f32(const float *g, const float *x, const float *w, float *gx,
  * reduced size < 1, k outside 1 .. 8; NRT_ERR_UNSUPPORTED for another dtype, a reduced size >= 2^24 (coordinates stop being exact in
  * float32) and outer * R * inner >= 2^31 elements; NRT_ERR_WORKSPACE for a missing or short workspace.
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_barycenter_workspace_bytes(int dtype, long long outer, const int *red_shape, int k, long long inner);
-int nrt_barycenter(const void *x, int dtype, long long outer, const int *red_shape, int k, long long inner, int normalize,
+size_t nrt_barycenter_workspace_bytes(int dtype, long long outer, const int red_shape[], int k, long long inner);
+int nrt_barycenter(const void *x, int dtype, long long outer, const int red_shape[], int k, long long inner, int normalize,
                    int shift_center, float *y, float *sums, void *workspace, size_t workspace_bytes, void *stream);
-int nrt_barycenter_bwd(const float *gy, const float *y, const float *sums, int dtype, long long outer, const int *red_shape, int k,
+int nrt_barycenter_bwd(const float *gy, const float *y, const float *sums, int dtype, long long outer, const int red_shape[], int k,
                        long long inner, int normalize, int shift_center, void *gx, void *workspace, size_t workspace_bytes,
                        void *stream);
 
@@ -905,12 +909,12 @@ int nrt_maxnorm_f32(float *w, int k0, long long rest, float max_value, float eps
  * (variant 0 or 1) or, for nrt_conv3d_pad_f32, the 2x2x2 MFMA arm (variant 6, under the conditions stated at nrt_conv3d_f32;
  * its halo follows pad_before); another variant is NRT_ERR_UNSUPPORTED.  A pad_before outside its range or NULL: NRT_ERR_INVALID_ARG.
  * ------------------------------------------------------------------------------------------ */
-int nrt_conv3d_pad_f32(const float *src0, int c0, const float *src1, int c1, const int *up, const float *weights,
-                       const float *packed_weights, const float *bias, float *out, int batch, const int *shape, const int *ksize,
-                       int cout, int dilation, const int *pad_before, int activation, int variant, void *stream);
+int nrt_conv3d_pad_f32(const float *src0, int c0, const float *src1, int c1, const int up[], const float *weights,
+                       const float *packed_weights, const float *bias, float *out, int batch, const int shape[], const int ksize[],
+                       int cout, int dilation, const int pad_before[], int activation, int variant, void *stream);
 int nrt_hyperconv3d_pad_f32(const float *src, int cin, const float *weights, const float *packed_weights, const float *bias,
-                            float *out, int batch, const int *shape, const int *ksize, int cout, int dilation,
-                            const int *pad_before, int activation, int variant, void *stream);
+                            float *out, int batch, const int shape[], const int ksize[], int cout, int dilation,
+                            const int pad_before[], int activation, int variant, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Patch-wise volume prediction, neurite/tf/utils/seg.py (csrc/seg.hip): the arg-max of a probability map with the probability of a
@@ -945,9 +949,9 @@ typedef enum { NRT_QUILT_MEAN = 0, NRT_QUILT_MEDIAN = 1 } nrt_quilt_reduce;
 int nrt_seg_argmax(const void *pred, int dtype, long long n_vox, int channels, void *labels, int labels_i64, const void *of_labels,
                    int of_labels_i64, float *prob, void *stream);
 int nrt_seg_recode(const void *seg, int seg_i64, long long n, const float *lookup, long long n_lookup, float *out, void *stream);
-int nrt_patch_extract(const void *vol, int dtype, int ndim, const int *vol_shape, int channels, const int *patch_size,
-                      const int *patch_stride, const int *grid_size, long long n0, long long count, void *patches, void *stream);
-int nrt_patch_quilt(const void *patches, int dtype, int ndim, const int *patch_size, const int *patch_stride, const int *grid_size,
+int nrt_patch_extract(const void *vol, int dtype, int ndim, const int vol_shape[], int channels, const int patch_size[],
+                      const int patch_stride[], const int grid_size[], long long n0, long long count, void *patches, void *stream);
+int nrt_patch_quilt(const void *patches, int dtype, int ndim, const int patch_size[], const int patch_stride[], const int grid_size[],
                     int channels, int reduce, float *vol, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -979,14 +983,14 @@ int nrt_patch_quilt(const void *patches, int dtype, int ndim, const int *patch_s
  * NRT_ERR_UNSUPPORTED for a window outside 1 .. 15, channels outside 1 .. 16 (NCC) and 2^31 or more elements in a tensor;
  * NRT_ERR_WORKSPACE for a missing or short workspace.
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_ncc_workspace_bytes(int batch, const int *shape, int channels, const int *win);
-int nrt_ncc_f32(const float *I, const float *J, int batch, const int *shape, int channels, const int *win, float eps, float *sums,
+size_t nrt_ncc_workspace_bytes(int batch, const int shape[], int channels, const int win[]);
+int nrt_ncc_f32(const float *I, const float *J, int batch, const int shape[], int channels, const int win[], float eps, float *sums,
                 float *cc, float *loss, void *workspace, size_t workspace_bytes, void *stream);
-int nrt_ncc_bwd_f32(const float *I, const float *J, const float *gcc, const float *gloss, int batch, const int *shape, int channels,
-                    const int *win, float eps, float *gI, float *gJ, void *workspace, size_t workspace_bytes, void *stream);
-int nrt_grad_loss_f32(const float *y, int batch, const int *shape, int nd, int channels, int penalty, float loss_mult, float *loss,
+int nrt_ncc_bwd_f32(const float *I, const float *J, const float *gcc, const float *gloss, int batch, const int shape[], int channels,
+                    const int win[], float eps, float *gI, float *gJ, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_grad_loss_f32(const float *y, int batch, const int shape[], int nd, int channels, int penalty, float loss_mult, float *loss,
                       void *workspace, size_t workspace_bytes, void *stream);
-int nrt_grad_loss_bwd_f32(const float *y, const float *gloss, int batch, const int *shape, int nd, int channels, int penalty,
+int nrt_grad_loss_bwd_f32(const float *y, const float *gloss, int batch, const int shape[], int nd, int channels, int penalty,
                           float loss_mult, float *gy, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1010,12 +1014,12 @@ int nrt_grad_loss_bwd_f32(const float *y, const float *gloss, int batch, const i
  * matrix_batch that is neither 1 nor batch, another method; NRT_ERR_UNSUPPORTED for ndim outside {2, 3}, 2^31 or more elements in a
  * tensor and batch > 65535; NRT_ERR_WORKSPACE for a missing or short workspace.
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_affine_warp_workspace_bytes(int ndim, const int *out_shape, int channels, int batch);
-int nrt_affine_warp_f32(const float *vol, const float *matrix, float *out, int ndim, const int *vol_shape, const int *out_shape,
+size_t nrt_affine_warp_workspace_bytes(int ndim, const int out_shape[], int channels, int batch);
+int nrt_affine_warp_f32(const float *vol, const float *matrix, float *out, int ndim, const int vol_shape[], const int out_shape[],
                         int channels, int batch, int matrix_batch, int shift_center, int method, int has_fill, float fill_value,
                         void *stream);
 int nrt_affine_warp_bwd_f32(const float *vol, const float *matrix, const float *grad_out, float *grad_matrix, int ndim,
-                            const int *vol_shape, const int *out_shape, int channels, int batch, int matrix_batch, int shift_center,
+                            const int vol_shape[], const int out_shape[], int channels, int batch, int matrix_batch, int shift_center,
                             int method, int has_fill, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1045,10 +1049,10 @@ int nrt_affine_warp_bwd_f32(const float *vol, const float *matrix, const float *
  * NRT_ERR_UNSUPPORTED for nd outside {2, 3}, 2^31 or more elements in a tensor and batch > 65535; NRT_ERR_WORKSPACE for a missing or
  * short workspace.
  * ------------------------------------------------------------------------------------------ */
-size_t nrt_jacdet_workspace_bytes(int batch, const int *shape, int nd);
-int nrt_jacdet_f32(const float *disp, int batch, const int *shape, int nd, float *det, void *stats, float *loss, void *workspace,
+size_t nrt_jacdet_workspace_bytes(int batch, const int shape[], int nd);
+int nrt_jacdet_f32(const float *disp, int batch, const int shape[], int nd, float *det, void *stats, float *loss, void *workspace,
                    size_t workspace_bytes, void *stream);
-int nrt_jacdet_bwd_f32(const float *disp, const float *gdet, const float *gloss, int batch, const int *shape, int nd, float *gdisp,
+int nrt_jacdet_bwd_f32(const float *disp, const float *gdet, const float *gloss, int batch, const int shape[], int nd, float *gdisp,
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1089,11 +1093,11 @@ int nrt_jacdet_bwd_f32(const float *disp, const float *gdet, const float *gloss,
 #define NRT_EDT_SIGNED 4
 #define NRT_EDT_SQUARED 8
 #define NRT_EDT_ANY_OF 16
-size_t nrt_edt_workspace_bytes(int batch, const int *shape, int nd, int channels);
-int nrt_edt_f32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
-                const float *sampling, int flags, float *out, void *workspace, size_t workspace_bytes, void *stream);
-size_t nrt_surface_stats_workspace_bytes(int batch, const int *shape, int nd, int nlabels);
-int nrt_surface_stats_f32(const int *t, const int *labels, int nlabels, const float *d2, int batch, const int *shape, int nd,
+size_t nrt_edt_workspace_bytes(int batch, const int shape[], int nd, int channels);
+int nrt_edt_f32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int shape[], int nd,
+                const float sampling[], int flags, float *out, void *workspace, size_t workspace_bytes, void *stream);
+size_t nrt_surface_stats_workspace_bytes(int batch, const int shape[], int nd, int nlabels);
+int nrt_surface_stats_f32(const int *t, const int *labels, int nlabels, const float *d2, int batch, const int shape[], int nd,
                           void *stats, unsigned *hist, long long nbins, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1129,10 +1133,10 @@ int nrt_surface_stats_f32(const int *t, const int *labels, int nlabels, const fl
 #define NRT_CCL_MIN_SIZE 2
 #define NRT_CCL_BORDER_FREE 4
 #define NRT_CCL_INVERT 8
-size_t nrt_ccl_workspace_bytes(int batch, const int *shape, int nd, int nlabels);
-int nrt_ccl_label_i32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
+size_t nrt_ccl_workspace_bytes(int batch, const int shape[], int nd, int nlabels);
+int nrt_ccl_label_i32(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int shape[], int nd,
                       int connectivity, int *components, int *count, void *workspace, size_t workspace_bytes, void *stream);
-int nrt_ccl_select(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int *shape, int nd,
+int nrt_ccl_select(const void *mask, const int *ids, const int *labels, int nlabels, int batch, const int shape[], int nd,
                    int connectivity, int mode, int min_size, int fill, int *table, void *out, void *workspace, size_t workspace_bytes,
                    void *stream);
 
@@ -1167,7 +1171,7 @@ int nrt_ccl_select(const void *mask, const int *ids, const int *labels, int nlab
 #define NRT_PCT_MIDPOINT 3
 #define NRT_PCT_IGNORE_NAN 1
 size_t nrt_select_workspace_bytes(int batch, long long voxels, int nq);
-int nrt_percentile(const void *x, int dtype, const void *mask, int batch, long long voxels, const double *positions, int nq, int method,
+int nrt_percentile(const void *x, int dtype, const void *mask, int batch, long long voxels, const double positions[], int nq, int method,
                    int flags, float *out, float *out_lower, float *out_upper, int *out_count, void *workspace, size_t workspace_bytes,
                    void *stream);
 int nrt_rescale_clip_f32(const void *x, int dtype, int batch, long long voxels, const float *lo, const float *hi, int stride, int clip,
