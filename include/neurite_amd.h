@@ -288,6 +288,52 @@ int nrt_warp_dice_labels_bwd_f32(const int32_t *moving, const float *loc, const 
                                  float laplace_smoothing, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Warp integer LABEL MAPS by linear interpolation + arg-max, and fuse several of them by a weighted vote  (csrc/warp_argmax.hip)
+ * An extension of this package (the reference warps one-hot maps and takes tf.argmax).  With M = one_hot(moving, nlabels) in float32
+ * the ids are argmax_l and prob is max_l of nrt_interpn_f32's tri-linear warp of M, without M: per label l the warped value is
+ *   p_l = the float32 sum, starting from 0, of the weights fl(fl(wx wy) wz) of the corners that carry l, added in corner order
+ *         000 ... 111 (at most 8 labels per voxel have p_l != 0).
+ * The winner is the label with the largest p_l > 0; an exact tie goes to the smaller id; no label with p_l > 0: id 0, prob 0 (what
+ * np.argmax of the dense row gives).
+ *   moving [batch, vol_shape] int32; out_ids [batch, out_shape] int32; out_prob [batch, out_shape] float32 or NULL (not written;
+ *   the ids are the same either way).  3-D only.
+ * nlabels = L in 1 ... 2^31 - 1: an id outside [0, L) is an all-zero row, as tf.one_hot has it: it never wins and is never used as an
+ * index.  nlabels = 0: every int32 value is a label (ids compare as signed integers).
+ * has_fill: a voxel whose unclipped location lies outside the volume gets fill_label and prob 0 (with nlabels >= 1 and fill_label 0
+ * that is the one-hot pipeline under fill_value = 0); without has_fill the edge is clamped, as everywhere else.
+ *   nrt_warp_labels_argmax_i32         loc [batch, out_shape, 3] with loc_mode NRT_LOC_SHIFT or NRT_LOC_ABSOLUTE (loc_batch_stride in
+ *                                      floats, 0: one transform for every batch entry), or loc = NULL with NRT_LOC_LINSPACE: the
+ *                                      align-corners grid of resize.
+ *   nrt_affine_warp_labels_argmax_i32  matrix [matrix_batch, 3, 4] float32, matrix_batch = batch or 1; the location of output voxel q
+ *                                      is formed in registers exactly as nrt_affine_warp_f32 forms it: p = (float)q - c (c =
+ *                                      (out_shape - 1) / 2 when shift_center, else 0), s_i = (((M_i0 p_0 + M_i1 p_1) + M_i2 p_2) +
+ *                                      M_i3) - p_i, loc_i = (float)q_i + s_i, one rounding per operation.
+ *   nrt_fuse_labels_i32                atlases [n_atlases, vol_shape] int32, loc [n_atlases, out_shape, 3] displacements
+ *                                      (NRT_LOC_SHIFT; loc_atlas_stride in floats, 0: one field for every atlas), weights [n_atlases]
+ *                                      float32, finite and >= 0, or NULL for all ones.  V_l = the float32 sum, starting from 0, over
+ *                                      the atlases in order n = 0 ... of fl(w_n p_{n,l}); a label absent from atlas n adds +0.
+ *                                      out_ids [out_shape] = the label with the largest V_l > 0, ties and the all-zero case as
+ *                                      above; out_votes [out_shape] = its V_l (not normalised) or NULL.  has_fill: an atlas whose
+ *                                      location is out of bounds adds nothing; every atlas out of bounds: fill_label, votes 0.
+ *                                      Exact for every input, 8 n_atlases distinct ids at one voxel included (a voxel with more
+ *                                      than 32 candidates leaves the in-LDS list for a slower list-free pass with the same sums).
+ * Non-finite locations: every gather index stays inside the volume; the values are unspecified.
+ * No atomics, no workspace, no host synchronisation; results are run-to-run bit-identical.
+ * Checked before any launch: NRT_ERR_INVALID_ARG for a NULL moving / atlases, out_ids, matrix, shape or (unless NRT_LOC_LINSPACE) loc,
+ * an extent, batch or n_atlases < 1, nlabels < 0, an unknown loc_mode, NRT_LOC_LINSPACE given with a loc, a negative stride, a
+ * matrix_batch that is neither 1 nor batch; NRT_ERR_UNSUPPORTED for 2^31 or more voxels in a map, batch > 65535, n_atlases > 16.
+ * ------------------------------------------------------------------------------------------ */
+int nrt_warp_labels_argmax_i32(const int32_t *moving, const float *loc /* NULL for NRT_LOC_LINSPACE */, int32_t *out_ids,
+                               float *out_prob /* or NULL */, const int vol_shape[], const int out_shape[], int nlabels, int batch,
+                               long long loc_batch_stride, int loc_mode, int has_fill, int fill_label, void *stream);
+int nrt_affine_warp_labels_argmax_i32(const int32_t *moving, const float *matrix, int32_t *out_ids, float *out_prob /* or NULL */,
+                                      const int vol_shape[], const int out_shape[], int nlabels, int batch, int matrix_batch,
+                                      int shift_center, int has_fill, int fill_label, void *stream);
+int nrt_fuse_labels_i32(const int32_t *atlases, const float *loc, const float *weights /* or NULL */, int32_t *out_ids,
+                        float *out_votes /* or NULL */, const int vol_shape[], const int out_shape[], int nlabels, int n_atlases,
+                        long long loc_atlas_stride, int has_fill, int fill_label, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Label-weighted categorical cross-entropy
  * replaces: neurite/tf/metrics.py:640-650 + tf.keras.losses.CategoricalCrossentropy
  * ------------------------------------------------------------------------------------------ */

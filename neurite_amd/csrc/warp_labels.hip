@@ -24,11 +24,10 @@
 // backward (warp_labels_bwd)  one lane per output voxel, the per-label coefficients of d dice / d p (two floats per label) in LDS.
 //   d/d loc_d = sum over corners c of g(id_c) d wt_c / d loc_d with g(l) = ca_l [fixed == l] + cb_l p_l; no reduction.
 #include "dice_reduce.h"
-#include "interpn_core.h"
+#include "wl_core.h"
 
 namespace {
 
-constexpr int WL_BLOCK = 256;
 constexpr int WL_WAVES = WL_BLOCK / NRT_WAVE;
 constexpr int WL_MAX_BLOCKS = 2048;          // per batch entry: 8 blocks per CU
 constexpr int WL_MIN_STEPS = 4;              // a block walks at least this many steps of 256 voxels (where the volume has them)
@@ -55,46 +54,6 @@ __device__ __forceinline__ float wl_wave_sum(float r) {
     r += __shfl_xor(r, 16, NRT_WAVE);
     r += __shfl_xor(r, 32, NRT_WAVE);
     return r;
-}
-
-// location, the 8 corner ids and the per-dimension weights of output voxel q
-template <int MODE>
-__device__ __forceinline__ void wl_corners(const InterpArgs &a, const float *locb, const int *__restrict__ mov, unsigned q, int (&lab)[8],
-                                           float (&w0)[3], float (&w1)[3], float (&p)[NRT_MAXD], bool &oob) {
-    int qd[NRT_MAXD];
-    decode<3>(a, q, qd);
-    load_loc<3, MODE>(a, locb, q, qd, p);
-    oob = a.has_fill ? out_of_bounds<3>(a, p) : false;
-    int i0[3], i1[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) corner_1d(p[d], a.S[d], i0[d], i1[d], w0[d], w1[d]);
-    // corner = 4 cx + 2 cy + cz; every index lies inside the volume.  The two z-neighbours of an (x, y) row are one 8-byte request, 4
-    // requests per voxel instead of 8: the pair starts at zb = min(z0, S_z - 2), and z0, z1 are each zb or zb + 1 (z1 = z0 at the far
-    // face).  Worth 3 - 4 % where the gathers are incoherent (rough field 1.05 -> 1.01 ms forward, 1.62 -> 1.57 with the backward at
-    // 4 x 160^3 x 32), nothing on the smooth bench field, where the kernels are bound by VALU issue
-    if (a.S[2] >= 2) {
-        const int zb = min(i0[2], a.S[2] - 2);
-#pragma unroll
-        for (int c = 0; c < 8; c += 2) {
-            const int idx = (((c & 4) ? i1[0] : i0[0]) * a.S[1] + ((c & 2) ? i1[1] : i0[1])) * a.S[2] + zb;
-            int pair[2];
-            __builtin_memcpy(pair, mov + idx, sizeof(pair));     // (4-byte aligned; the compiler picks the request)
-            lab[c] = i0[2] == zb ? pair[0] : pair[1];
-            lab[c + 1] = i1[2] == zb ? pair[0] : pair[1];
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int idx = (((c & 4) ? i1[0] : i0[0]) * a.S[1] + ((c & 2) ? i1[1] : i0[1])) * a.S[2] + ((c & 1) ? i1[2] : i0[2]);
-            lab[c] = mov[idx];
-        }
-    }
-}
-
-__device__ __forceinline__ void wl_weights(const float (&w0)[3], const float (&w1)[3], float (&wt)[8]) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        wt[c] = nrt_mul(nrt_mul((c & 4) ? w1[0] : w0[0], (c & 2) ? w1[1] : w0[1]), (c & 1) ? w1[2] : w0[2]);
 }
 
 // grid (nrt_xcd_grid(nblk), batch); dynamic LDS WL_WAVES * 3 L floats; part [batch][nblk][3][L]

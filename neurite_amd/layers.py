@@ -4,6 +4,8 @@ neurite_amd.layers -- the layers of neurite's hot path as torch.nn.Modules over 
 Resize / Zoom           neurite/tf/layers.py:91-185
 SpatialTransformer      voxelmorph.layers.SpatialTransformer as the reference calls it
                         (neurite/tf/models.py:806-807 and 1157-1159; not vendored in the reference)
+LabelTransformer, LabelResize   the two above for integer label maps: linear interpolation + arg-max without a one-hot tensor
+                        (an extension of this package; fused.warp_labels)
 HyperConv* / HyperDense* neurite/tf/layers.py:2515-3033 (kernel and bias are inputs, one set per batch entry)
 LocalBias, LocalLinear  neurite/tf/layers.py:746-808   (one bias / one linear map per voxel and feature)
 LocalCrossLinear        :1535-1607                     (one Cin x Cout matrix per voxel; up to 64 features each way)
@@ -31,7 +33,7 @@ from . import augment
 from . import deferred
 from . import utils
 
-__all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LocallyConnected3D', 'VecInt', 'RescaleTransform',
+__all__ = ['Resize', 'Zoom', 'SpatialTransformer', 'LabelTransformer', 'LabelResize', 'LocallyConnected3D', 'VecInt', 'RescaleTransform',
            'ComposeTransform', 'AffineToDenseShift', 'GaussianBlur', 'Subsample', 'RandomCrop', 'GaussianNoise', 'PerlinNoise',
            'HyperConv', 'HyperConv2D', 'HyperConv3D', 'HyperConvFromDense', 'HyperConv2DFromDense', 'HyperConv3DFromDense',
            'HyperDense', 'HyperDenseFromDense', 'LocalBias', 'LocalLinear', 'LocalCrossLinear', 'LocalParamLayer',
@@ -301,6 +303,82 @@ class SpatialTransformer(_Layer):
                                          dict(vol=vol_c, shift=shift_c, single_transform=self.single_transform,
                                               fill_value=self.fill_value))
         return run()
+
+
+class LabelTransformer(_Layer):
+    """
+    SpatialTransformer for integer label maps: linear interpolation of the (never built) one-hot map + arg-max, in one kernel
+    (fused.warp_labels, csrc/warp_argmax.hip).  An extension of this package.
+
+    call([ids, trf]):  ids [B, *S] (or [B, *S, 1]) of any integer dtype, trf a dense field [B, *S', D] or an affine [B, 3, 4] / [B, 4, 4]
+    ->  ids [B, *S'] in the dtype of the input (with the trailing axis of 1 if the input had it).  nb_labels=None: every int32 value is a
+    label; nb_labels=L: ids outside [0, L) are background.  fill_label: None clamps the edge, an id marks what is sampled outside the
+    volume.  No gradient flows through it.
+    """
+
+    def __init__(self, nb_labels=None, indexing='ij', single_transform=False, fill_label=None, shift_center=True, **kwargs):
+        super().__init__(**kwargs)
+        assert indexing in ['ij', 'xy'], "indexing has to be 'ij' (matrix) or 'xy' (cartesian)"
+        self.nb_labels = nb_labels
+        self.indexing = indexing
+        self.single_transform = single_transform
+        self.fill_label = fill_label
+        self.shift_center = shift_center
+
+    def get_config(self):
+        config = super().get_config().copy()
+        config.update({'nb_labels': self.nb_labels, 'indexing': self.indexing, 'single_transform': self.single_transform,
+                       'fill_label': self.fill_label, 'shift_center': self.shift_center})
+        return config
+
+    def build(self, input_shape):
+        if len(input_shape) > 2:
+            raise Exception('LabelTransformer must be called on a list of length 2.')
+        self.built = True
+
+    def call(self, inputs):
+        assert len(inputs) == 2, 'inputs has to be len 2, found: %d' % len(inputs)
+        ids, trf = inputs
+        from . import fused
+        out = fused.warp_labels(ids, trf, nb_labels=self.nb_labels, indexing=self.indexing, single_transform=self.single_transform,
+                                fill_label=self.fill_label, shift_center=self.shift_center)
+        return out.unsqueeze(-1) if ids.dim() == out.dim() + 1 else out
+
+
+class LabelResize(_Layer):
+    """
+    Resize for integer label maps: the align-corners linear zoom of the (never built) one-hot map + arg-max, in one kernel
+    (utils.resize_labels on every batch entry in one launch).  An extension of this package.
+
+    call(ids):  ids [B, *S] (or [B, *S, 1]), 2-D or 3-D, of any integer dtype  ->  [B, *S'] with S' = int(S * zoom_factor), same dtype.
+    zoom_factor: a scalar or one factor per spatial axis.
+    """
+
+    def __init__(self, zoom_factor, nb_labels=None, **kwargs):
+        super().__init__(**kwargs)
+        self.zoom_factor = zoom_factor
+        self.nb_labels = nb_labels
+
+    def get_config(self):
+        config = super().get_config().copy()
+        config.update({'zoom_factor': self.zoom_factor, 'nb_labels': self.nb_labels})
+        return config
+
+    def call(self, inputs):
+        if isinstance(inputs, (list, tuple)):
+            assert len(inputs) == 1, "inputs has to be len 1. found: %d" % len(inputs)
+            inputs = inputs[0]
+        from . import fused
+        if not isinstance(inputs, torch.Tensor):
+            raise TypeError('LabelResize: expected a torch.Tensor, got %s' % type(inputs).__name__)
+        zf = self.zoom_factor
+        if isinstance(zf, (list, tuple)):
+            nd = len(zf)
+        else:                                       # [B, X, Y] is 2-D, [B, X, Y, Z] 3-D, a fifth axis the trailing 1
+            nd = min(inputs.dim() - 1, 3)
+            zf = [zf] * nd
+        out = fused._resize_labels(inputs, list(zf), self.nb_labels, 'LabelResize')
+        return out.unsqueeze(-1) if inputs.dim() == out.dim() + 1 else out
 
 
 # ------------------------------------------------------------------------------------------

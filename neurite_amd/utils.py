@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from .deferred import materialize
 
-__all__ = ['interpn', 'resize', 'zoom', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
+__all__ = ['interpn', 'resize', 'zoom', 'resize_labels', 'zoom_labels', 'transform', 'affine_to_dense_shift', 'integrate_vec', 'compose',
            'gaussian_kernel', 'separable_conv', 'minmax_norm', 'soft_quantize', 'barycenter', 'jacobian_determinant',
            'dist_trf', 'signed_dist_trf', 'vol_to_sdt', 'vol_to_sdt_batch', 'label_dist_trf',
            'connected_components', 'largest_component', 'keep_largest_components', 'remove_small_components', 'fill_holes',
@@ -306,6 +306,27 @@ def resize(vol, zoom_factor, interp_method='linear'):
 
 
 zoom = resize
+
+
+def resize_labels(ids, zoom_factor, nb_labels=None):
+    """
+    Align-corners resize of one (un-batched) integer label map [X, Y, Z] or [X, Y] by linear interpolation + arg-max: what
+    resize(one_hot(ids), zoom_factor).argmax(-1) gives, without the one-hot tensor (fused.warp_labels on resize's grid, which is formed
+    in registers; csrc/warp_argmax.hip).  zoom_factor: a scalar or one factor per axis; the output shape follows resize's rule
+    (int(size * factor)).  Any torch integer dtype, returned as it came; ties go to the smaller id.  nb_labels = L: ids outside
+    [0, L) are background; None: every int32 value is a label.  Not differentiable.
+    """
+    from . import fused
+    if not isinstance(ids, torch.Tensor):
+        raise TypeError('resize_labels: expected a torch.Tensor, got %s' % type(ids).__name__)
+    if not isinstance(zoom_factor, (list, tuple)):
+        zoom_factor = [zoom_factor] * ids.dim()
+    if len(zoom_factor) != ids.dim():
+        raise ValueError('resize_labels: %d zoom factors for a label map of rank %d' % (len(zoom_factor), ids.dim()))
+    return fused._resize_labels(ids.unsqueeze(0), list(zoom_factor), nb_labels, 'resize_labels')[0]
+
+
+zoom_labels = resize_labels
 
 
 def transform(vol, loc_shift, interp_method='linear', indexing='ij', fill_value=None):
