@@ -1223,6 +1223,47 @@ int nrt_percentile(const void *x, int dtype, const void *mask, int batch, long l
 int nrt_rescale_clip_f32(const void *x, int dtype, int batch, long long voxels, const float *lo, const float *hi, int stride, int clip,
                          float out_min, float out_max, float *y, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-label region statistics of an integer id map and the confusion matrix of two id maps (csrc/labelstats.hip,
+ * csrc/labelstats_core.h).  They replace a [batch, *shape, nlabels] one-hot tensor and its reductions, torch.bincount /
+ * scatter_add (float atomics: sums that change from run to run), or a copy to the host and scipy.ndimage.sum / center_of_mass /
+ * find_objects there.
+ * The label slots: labels [nlabels] int32 on the device, 1 .. 256 distinct ids of any int32 value; slot l collects the voxels with
+ * ids == labels[l].  With labels NULL slot l is the id l, and ids outside [0, nlabels) belong to no slot.  An id that is in no slot is
+ * never used as an index.
+ *   nrt_label_stats   ids [batch, *shape] int32, `shape` holds nd extents (2 or 3); image NULL or [batch, *shape, channels], channels
+ *                 last, 1 .. 4 channels, stored as `dtype` (NRT_DT_F32 / NRT_DT_BF16 / NRT_DT_F16) and widened to float32.  Outputs,
+ *                 each but counts may be NULL:
+ *                   counts     [batch, nlabels] int64          the voxels of the slot
+ *                   coord_sums [batch, nlabels, nd] int64      the sum of the voxel index along each axis
+ *                   bbox       [batch, nlabels, 2, nd] int32   the smallest and the largest index along each axis, both inclusive;
+ *                                                              an empty slot holds (shape[a], -1)
+ *                   sums       [batch, nlabels, channels, 2] float64   the sum of x and of x * x (float32 products); a NaN propagates
+ *                   minmax     [batch, nlabels, channels, 2] float32   min and max as fminf / fmaxf form them: a NaN is skipped, and
+ *                                                              an empty or all-NaN slot holds (+inf, -inf)
+ *                 sums and minmax need the image.  The integer outputs are exact.  The float sums: every wave adds its voxels of a slot
+ *                 in a fixed lane order and its 64-voxel steps in their order in float32, a block adds its four waves and the call the
+ *                 blocks of an entry (32 runs of consecutive blocks, then the runs) in a fixed order in float64; the shares follow
+ *                 from the geometry alone.
+ *   nrt_label_confusion_i32   a, b [batch, voxels] int32; counts [batch, nlabels + 1, nlabels + 1] int64, zeroed by the call:
+ *                 counts[e, i, j] = the voxels of entry e whose a is in slot i and whose b is in slot j; the last row and column
+ *                 collect the ids that are in no slot, so every voxel is counted exactly once.
+ * workspace: nrt_label_stats_workspace_bytes (channels 0 without an image) / nrt_label_confusion_workspace_bytes, 16-byte aligned; the
+ * call initialises what it uses of it, every time.  No float atomics; integer atomics where they commute; no workgroup waits for
+ * another, no host synchronisation (the calls capture into a graph), no allocation; the results do not depend on the schedule:
+ * bit-identical run to run.  Checked before any launch, in this order: NRT_ERR_INVALID_ARG for a NULL ids (a, b), counts or shape, sums
+ * or minmax without an image, an unknown dtype with an image, batch < 1, nd outside {2, 3}, an extent (voxels) < 1, channels outside
+ * 1 .. 4 with an image, nlabels outside 1 .. 256; NRT_ERR_UNSUPPORTED for batch > 65535 or batch * voxels >= 2^31 (32-bit indexing);
+ * last, NRT_ERR_WORKSPACE for a missing, misaligned or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_label_stats_workspace_bytes(int batch, const int shape[], int nd, int nlabels, int channels);
+int nrt_label_stats(const int *ids, const int *labels, int nlabels, const void *image, int dtype, int channels, int batch,
+                    const int shape[], int nd, long long *counts, long long *coord_sums, int *bbox, double *sums, float *minmax,
+                    void *workspace, size_t workspace_bytes, void *stream);
+size_t nrt_label_confusion_workspace_bytes(int batch, long long voxels, int nlabels);
+int nrt_label_confusion_i32(const int *a, const int *b, const int *labels, int nlabels, int batch, long long voxels, long long *counts,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

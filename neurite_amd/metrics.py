@@ -23,7 +23,7 @@ from .errors import InvalidArgumentError
 
 __all__ = ['Dice', 'SoftDice', 'HardDice', 'CategoricalCrossentropy', 'WeightedCategoricalCrossentropy',
            'dice_partial_sums', 'MutualInformation', 'MeanSquaredErrorProb', 'JointSegLoss',
-           'JacobianDeterminant', 'JacobianStats', 'SurfaceDistance', 'ComponentCount']
+           'JacobianDeterminant', 'JacobianStats', 'SurfaceDistance', 'ComponentCount', 'LabelOverlap']
 
 _INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64, torch.bool)
 
@@ -1229,3 +1229,60 @@ class ComponentCount:
 
     def extra(self, ids):
         return (self.counts(ids) - 1).clamp_(min=0)
+
+
+class LabelOverlap:
+    """
+    The confusion matrix of two integer label maps and the overlap scores that follow from it (csrc/labelstats.hip): one
+    pass over both id maps, integers only -- exact, bit-identical run to run, no one-hot tensor.  THIS PROJECT'S metric: the
+    reference's hard Dice gives one score per label and does not say which structure a miss went to.
+
+    labels: 1 to 256 distinct ids of any int32 value, in any order; or an int nb for the ids 0 .. nb - 1.
+    Label maps are [B, *S] integer tensors of equal shape, B * prod(S) < 2^31; other dtypes raise TypeError, as in Dice's max_label
+    path.  Nothing travels to the host, so the calls capture into a graph.  Not differentiable: the inputs are sets.
+        confusion(y_true_ids, y_pred_ids)  int64 [B, L + 1, L + 1]: [b, i, j] = the voxels whose true id is labels[i] and whose
+                                           predicted id is labels[j]; the last row and column collect the ids that are not listed, so
+                                           every voxel is counted exactly once
+        scores(y_true_ids, y_pred_ids)     a dict of float64 [B, L], formed from the confusion matrix on the device; with tp the
+                                           diagonal, n_t the row sums and n_p the column sums:  dice = 2 tp / (n_t + n_p);
+                                           jaccard = tp / (n_t + n_p - tp);  sensitivity = tp / n_t;  precision = tp / n_p;
+                                           volume_similarity = 1 - |n_p - n_t| / (n_p + n_t);  count_true = n_t;  count_pred = n_p.
+                                           A ratio with a zero denominator is NaN.
+    """
+
+    def __init__(self, labels):
+        self.labels, self.nb_labels = utils._ls_labels(labels, 'LabelOverlap')
+
+    def confusion(self, y_true_ids, y_pred_ids):
+        what = 'LabelOverlap'
+        for name, y in (('y_true_ids', y_true_ids), ('y_pred_ids', y_pred_ids)):
+            if not isinstance(y, torch.Tensor):
+                raise TypeError('%s: %s must be a torch.Tensor, got %s' % (what, name, type(y).__name__))
+            if y.dtype not in _INT_DTYPES:
+                raise TypeError('%s: %s must hold integer label ids, got %s' % (what, name, y.dtype))
+        if y_true_ids.shape != y_pred_ids.shape:
+            raise ValueError('%s: y_true_ids and y_pred_ids must have the same shape, got %s and %s'
+                             % (what, tuple(y_true_ids.shape), tuple(y_pred_ids.shape)))
+        if y_true_ids.dim() < 2:
+            raise ValueError('%s: expected [batch, *spatial], got shape %s' % (what, tuple(y_true_ids.shape)))
+        utils._ls_check_geometry(y_true_ids.shape, what, spatial_axes=None)
+        dev = _lib.require_device(y_true_ids, y_pred_ids)
+        t = y_true_ids.detach().to(torch.int32).contiguous()
+        p = y_pred_ids.detach().to(torch.int32).contiguous()
+        batch, n = int(t.shape[0]), self.nb_labels
+        voxels = t.numel() // batch
+        nws = int(_lib.lib().nrt_label_confusion_workspace_bytes(batch, voxels, n))
+        ws = _lib.workspace(dev, max(nws, 16))
+        counts = torch.empty((batch, n + 1, n + 1), dtype=torch.int64, device=dev)
+        lab = utils._edt_label_tensor(self.labels, dev) if self.labels is not None else None
+        _lib.call(dev, 'nrt_label_confusion_i32', _lib.ptr(t), _lib.ptr(p), _lib.ptr(lab), n, batch, voxels, _lib.ptr(counts),
+                  _lib.ptr(ws), nws, what=what)
+        return counts
+
+    def scores(self, y_true_ids, y_pred_ids):
+        n = self.nb_labels
+        table = self.confusion(y_true_ids, y_pred_ids).to(torch.float64)
+        tp = table.diagonal(dim1=1, dim2=2)[:, :n]
+        n_t, n_p = table.sum(2)[:, :n], table.sum(1)[:, :n]
+        return {'dice': 2.0 * tp / (n_t + n_p), 'jaccard': tp / (n_t + n_p - tp), 'sensitivity': tp / n_t, 'precision': tp / n_p,
+                'volume_similarity': 1.0 - (n_p - n_t).abs() / (n_p + n_t), 'count_true': n_t, 'count_pred': n_p}

@@ -19,7 +19,7 @@ from . import augment
 from . import layers
 from . import utils
 
-__all__ = ['labels_to_image', 'SynthModel', 'labels_to_image_new', 'SynthModelNew']
+__all__ = ['labels_to_image', 'SynthModel', 'labels_to_image_new', 'SynthModelNew', 'intensity_priors']
 
 
 class SynthModel(nn.Module):
@@ -196,6 +196,41 @@ def labels_to_image(in_shape, in_label_list, out_label_list=None, out_shape=None
     # models.py:763-769: the generator is appended to `input_model` (one output = the label map); the returned model takes
     # input_model's inputs
     return _Chained(input_model, model)
+
+
+def intensity_priors(pairs, labels, channel=0):
+    """
+    The per-label intensity bounds `labels_to_image` takes, estimated from real (image, segmentation) pairs: THIS PROJECT'S set-up
+    helper (the reference leaves the bounds to the caller).  Every pair goes through `utils.label_stats` on the device
+    (csrc/labelstats.hip); the extrema over the pairs are kept on the device and read back once, at the end.
+
+    pairs:   an iterable of (image, ids): ids an integer id map [*S], len(S) in {2, 3}; image of ids' shape, or of ids' shape + [C].
+    labels:  1 to 256 distinct ids.  `labels_to_image` sorts its in_label_list, so the results are in the order of np.unique(labels).
+    channel: the image channel the bounds are taken from.
+    Returns {'mean_min', 'mean_max', 'std_min', 'std_max'}: Python lists with one float per label, the smallest and largest of the
+    label's mean and (population) standard deviation over the pairs in which it occurs; None for a label that occurs in no pair --
+    fill those in before handing the lists to labels_to_image(in_label_list=labels, mean_min=..., ...).
+    """
+    what = 'intensity_priors'
+    if isinstance(labels, (int, np.integer)):
+        raise ValueError('%s: a list of label ids, as labels_to_image takes it, got %r' % (what, labels))
+    order = sorted(utils._ls_labels(labels, what)[0])             # (np.unique's order)
+    if isinstance(channel, bool) or channel != int(channel) or int(channel) < 0:
+        raise ValueError('%s: channel must be a non-negative integer, got %r' % (what, channel))
+    channel = int(channel)
+    lo = hi = None
+    for image, ids in pairs:
+        st = utils.label_stats(ids, image, order)
+        if channel >= st['mean'].shape[-1]:
+            raise ValueError('%s: channel %d of an image with %d channel(s)' % (what, channel, st['mean'].shape[-1]))
+        both = torch.stack([st['mean'][:, channel], st['std'][:, channel]])                # [2, L]; NaN where the label is absent
+        lo = both if lo is None else torch.fmin(lo, both)                                  # (fmin / fmax skip a NaN)
+        hi = both if hi is None else torch.fmax(hi, both)
+    if lo is None:
+        raise ValueError('%s: no pairs' % what)
+    host = torch.stack([lo, hi]).cpu().numpy()                                              # the one read-back
+    pick = lambda v: [None if np.isnan(x) else float(x) for x in v]                        # noqa: E731
+    return {'mean_min': pick(host[0, 0]), 'mean_max': pick(host[1, 0]), 'std_min': pick(host[0, 1]), 'std_max': pick(host[1, 1])}
 
 
 class _Chained(torch.nn.Module):
