@@ -8,14 +8,16 @@
 // Structure.  The x-march schedule of warp_dice_tile is kept (a block of four waves owns a 4 x 8 (y,z) patch and walks x, one
 // x-plane per pass; blocks dealt to the XCDs region by region).  A wave owns a 2 x 4 sub-patch: 8 voxels per pass = one voxel
 // per 8-lane group, lane p of a group holds labels 4p..4p+3 (16 bytes of every row).  Each wave has its own direct-mapped cache
-// of 128 rows (16 KB) + 16 overflow rows in LDS; NOTHING is shared between waves, so there is no barrier, no claim protocol and
-// no atomic anywhere: a wave's LDS operations execute in program order.  The work of a pass:
+// of 128 rows (16 KB) + 16 overflow rows in LDS; NOTHING is shared between waves, so there is no barrier and no protocol between
+// waves: a wave's LDS operations execute in program order.  The work of a pass:
 //   M1a  every lane computes the corner geometry of its group's voxel and takes ONE of the 64 (voxel, corner) references of the
-//        pass: row id `rid`, slot = (ix & 3, iy & 3, iz & 7); reads tag[slot];
-//   M1b  references that miss write {rid, lane}; everybody reads the tag back;
-//   M1c  tag.rid == rid: the row is (or will be) in the slot -- `served`; the missing lane whose own tag came back is its `loader`;
-//        a reference whose slot now names another row of this same pass is an `orphan` (about 2 % of the references on the bench
-//        field): it gets an overflow row for this pass only.  Loaders + orphans are compacted (ballot / mbcnt) into a fetch list
+//        pass: row id `rid`, slot = (ix & 3, iy & 3, iz & 7); it EXCHANGES rid with tag[slot] (ds_wrxchg_rtn_b32: the lanes of one
+//        exchange that name one slot are served one after the other, each getting what the one before left) and reads the word back;
+//   M1c  what the exchange returned is not rid: `miss`; what the read returns is rid: the row is (or will be) in the slot -- `served`;
+//        loader = miss and served.  Among the lanes of a row the first one after a lane of ANOTHER row (or after the tag from before
+//        the pass) loads it: one loader per row unless r1, r2, r1 meet in one slot -- then both r1 lanes load (same bytes, same LDS
+//        row; 0.06 per pass on the bench field).  A reference whose slot now names another row of this same pass is an `orphan`
+//        (about 2 % of the references on the bench field): it gets an overflow row for this pass only.  Loaders + orphans are compacted (ballot / mbcnt) into a fetch list
 //        in LDS (two words per entry: byte offset of the row in the volume, of its LDS row), transposed so that 8-lane groups read their entries back
 //        with two ds_read_b128 and fetch one 128-byte row each: ceil(n / 8) load instructions per pass instead of 8 (n = 23 on
 //        the bench field); the source row of every reference is broadcast to its group through 128 bytes
@@ -35,7 +37,18 @@
 // Every LDS round trip of the management has a stretch of the blend's arithmetic to hide behind; the row loads of pass p + 1 go out
 // first thing in step p, BEFORE the wait for pass p's own rows (a late row does not hold back the next requests), one step before they
 // are stored -- the lead matters: requested half a step later the launch takes 12 % longer (profiles/r05_lab/wc_probes.jsonl).  The fixed row, the locations and the stored row go through buffer descriptors with the
-// pass offset in an SGPR (no per-pass address arithmetic); tags are 32-bit (row id << 6 | lane).
+// pass offset in an SGPR (no per-pass address arithmetic); tags are 32-bit (then row id << 6 | lane, with
+// M1b = "references that miss store their tag, everybody reads it back" between M1a's tag read and M1c).
+//
+// The tag exchange (profiles/wc_tag_exchange/): the management was THREE LDS round trips (tag read | tag store where
+// it missed + read back | list), each behind a third of the blend.  The exchange and the read behind it are one round trip that tells both
+// what the slot held and what it holds after all lanes; the tag is the row id alone (nothing reads a lane out of it), the trash tag entry
+// the hits stored to is gone.  A step of the fused forward is now
+//     M2(p + 1) | D(p), B-reads(p) | M1a(p + 2) | blend corners 0..3 | M1c | corners 4..7 | Dice sums
+// (the list round trip of M1c behind half the blend and the sums, the exchange behind the other half), and of the stand-alone warp and the
+// backward forms  ... | M1a(p + NST) | blend corners 0..7 | M1c | gradient  (the whole blend hides the exchange; M1c between the halves
+// costs 6 - 10 registers: up to 253 in the backward forms).  -DWC_M1C_EARLY=0 gives the fused forward the second form too: measured
+// level with the first on one stream and behind it in one alternation of five on three (profiles/wc_tag_exchange/README.md).
 //
 // Model of the request stream (tools/wc_sim.py, bench field): 4.8 distinct rows per voxel inside a pass, 2.7 fetched per voxel with
 // the cache (8 through L1 in the register kernel), 0.16 orphan references per voxel.
@@ -61,19 +74,22 @@ namespace {
 #ifndef WC_FIXED_GROUPS
 #define WC_FIXED_GROUPS 4                                       // groups of 8 fetch-list entries whose row loads go out whatever n is (3 or 4)
 #endif
+#ifndef WC_M1C_EARLY
+#define WC_M1C_EARLY 1                                          // fused forward: M1c between the halves of the blend (0: behind it)
+#endif
 constexpr int WC_SLOTS = 128;                                   // direct-mapped rows per wave
 constexpr int WC_OVF = 16;                                      // overflow rows (orphans of the current pass)
 constexpr int WC_TRASH_ROW = WC_SLOTS + WC_OVF;                 // where the list entries without a row store (branch-free masking)
 constexpr int WC_ROWS = WC_TRASH_ROW + 1;
 constexpr unsigned WC_NOROW = 0x01ffffffu;                      // row id of "no row": its bytes lie past every volume this kernel takes (wc_applies)
-constexpr unsigned WC_TAGS_OFF = WC_ROWS * 128;                 // u32 tag per slot (row id << 6 | lane), + one trash entry
-constexpr unsigned WC_LIST_OFF = WC_TAGS_OFF + 528;             // fetch list: 64 x {row offset in the volume, LDS row offset}, transposed
+constexpr unsigned WC_TAGS_OFF = WC_ROWS * 128;                 // u32 tag per slot: the id of its row (512 of the 528 bytes)
+constexpr unsigned WC_LIST_OFF = WC_TAGS_OFF + 528;            // fetch list: 64 x {row offset in the volume, LDS row offset}, transposed
                                                                 // (entry e at (e & 7) * 8 + (e >> 3))
 constexpr unsigned WC_BC_OFF = WC_LIST_OFF + 512;               // u16 byte offset of the source row of every (voxel, corner) reference
 constexpr unsigned WC_WAVE_BYTES = WC_BC_OFF + 128;             // 19728
 constexpr unsigned WC_BLOCK_BYTES = 4 * WC_WAVE_BYTES;          // 78912: two blocks per CU
 static_assert(WC_LIST_OFF % 16 == 0 && WC_BC_OFF % 16 == 0 && WC_WAVE_BYTES % 16 == 0, "LDS layout");
-static_assert((WC_SLOTS + 1) * 4 <= 528 && WC_ROWS <= 256, "LDS layout");
+static_assert(WC_SLOTS * 4 <= 528 && WC_ROWS <= 256, "LDS layout");
 static_assert(2 * WC_BLOCK_BYTES <= 160 * 1024, "two blocks per CU");
 
 // LDS pointers carry their address space explicitly: a volatile access through a generic pointer compiles to flat_load / flat_store
@@ -185,6 +201,12 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
     tags[lane] = ~0u;                                            // no row id is 0x3ffffff
     tags[lane + 64] = ~0u;
     const bool cx1 = (p & 4) != 0, cy1 = (p & 2) != 0, cz1 = (p & 1) != 0;
+    // nrt_mad24 takes vector operands: the two strides live in VGPRs across the march (else a v_mov from the SGPR each, every pass).
+    // Not in the backward forms, which the two registers would take past the 247 they have had so far
+    unsigned SYv = SY, SZv = SZ;
+    if (!BWD) asm volatile("" : "+v"(SYv), "+v"(SZv));
+    // (the stand-alone warp and the backward forms keep M1c behind the blend: header comment)
+    constexpr bool M1C_EARLY = WC_M1C_EARLY && DICE && !BWD;
 
     nrt_f2 stp_l = {0, 0}, stp_h = {0, 0}, stt_l = {0, 0}, stt_h = {0, 0}, spp_l = {0, 0}, spp_h = {0, 0};
     float mnt = INFINITY, mxt = -INFINITY, mnp = INFINITY, mxp = -INFINITY;
@@ -208,7 +230,7 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         float pn[3];                 // location of the pass that will use this state next
     };
     // a pass under management: from the tag read (m1a) to the fetch list (m1c)
-    struct Mg { float w0x, w0y, w0z; bool oob, miss; unsigned rid, slot, t1, t2, mytag; float mk[3]; };
+    struct Mg { float w0x, w0y, w0z; bool oob; unsigned rid, slot, told, tfin; float mk[3]; };
     // NST states: a pass is managed NST steps before it is blended and its rows are requested NST - 1 steps before.  Memory operations of a
     // wave complete IN ORDER, stores included: a row requested one step ahead waits for the acknowledgement of the store of the pass in front
     // of it; requested two steps ahead it does not.  Measured, alternating libraries on one box (profiles/r06_lab/e6_three_states_standalone.jsonl,
@@ -266,30 +288,28 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
             m.mk[2] = (fminf(fmaxf(pz, 0.0f), mxz) == pz) ? 1.0f : 0.0f;
         }
         const unsigned ix = cx1 ? i1x : i0x, iy = cy1 ? i1y : i0y, iz = cz1 ? i1z : i0z;      // corner p of the group's voxel
-        m.rid = nrt_mad24(nrt_mad24(ix, SY, iy), SZ, iz);
+        m.rid = nrt_mad24(nrt_mad24(ix, SYv, iy), SZv, iz);
         m.slot = ((ix & 3u) << 5) | ((iy & 3u) << 3) | (iz & 7u);
-        m.mytag = (m.rid << 6) | (unsigned)lane;
-        m.t1 = tags[m.slot];
-    };
-    // M1b: references that miss claim their slot (hits store to the trash entry), everybody reads the tag back
-    auto m1b = [&](Mg &m) {
-        m.miss = (m.t1 ^ m.mytag) >= 64u;
-        tags[m.miss ? m.slot : (unsigned)WC_SLOTS] = m.mytag;
-        m.t2 = tags[m.slot];
+        // every lane swaps its row id into the slot's tag and reads the word back: the LDS serialises the lanes of one exchange that name
+        // one address and executes a wave's operations in order, so `told` is what the lane in front left (or the tag from before the
+        // pass) and `tfin` what the last lane of the pass left
+        m.told = __hip_atomic_exchange((__attribute__((address_space(3))) unsigned *)(wl + WC_TAGS_OFF) + m.slot, m.rid, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+        m.tfin = tags[m.slot];
     };
     // M1c: roles, fetch list, source rows of the group's 8 corners; leaves the pass in s (its row loads are issue(s))
     auto m1c = [&](int pass, const Mg &m, Pass &s) {
-        const unsigned x2 = m.t2 ^ m.mytag;
-        const bool served = x2 < 64u;
-        const bool loader = m.miss && x2 == 0u;
-        const bool orphan = !served;
-        const unsigned long long Ml = __builtin_amdgcn_ballot_w64(loader), Mo = __builtin_amdgcn_ballot_w64(orphan);
-        const unsigned long long Mf = Ml | Mo;
+        const bool miss = m.told != m.rid;                       // what was there before me
+        const bool orphan = m.tfin != m.rid;                     // what is there after all of us: the row lost the slot
+        // loader = miss && served: two lanes of one row with another row's lane between them both load it -- same bytes, same LDS row.
+        // The AND is taken on the scalar side (a ballot of `miss && !orphan` materialises the AND of two compares in a VGPR)
+        const unsigned long long Mm = __builtin_amdgcn_ballot_w64(miss), Mo = __builtin_amdgcn_ballot_w64(orphan);
+        const unsigned long long Mf = Mm | Mo;                   // (= (Mm & ~Mo) | Mo: the loaders' own ballot is never needed)
         const int no = __builtin_popcountll(Mo);
         int n = __builtin_popcountll(Mf);
         const unsigned ro = __builtin_amdgcn_mbcnt_hi((unsigned)(Mo >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)Mo, 0u));
         const unsigned rf = __builtin_amdgcn_mbcnt_hi((unsigned)(Mf >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)Mf, 0u));
-        bool fetcher = loader || orphan;
+        bool fetcher = miss || orphan;                           // a loader or an orphan, never both: n <= 64
         unsigned src = orphan ? (unsigned)WC_SLOTS + ro : m.slot;
         // EVERY lane writes one entry of the fetch list: loaders and orphans their row and its destination at positions 0 .. n - 1,
         // the others a row past the volume (reads as zeros, touches no memory) with the trash row as destination at n .. 63 -- so
@@ -393,6 +413,10 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         wt2[3] = (nrt_f2){wxy1[1], wxy1[1]} * wz2;
         nrt_f2 al = {0.0f, 0.0f}, ah = {0.0f, 0.0f};
         constexpr bool BLEND = BWD != 2;                          // (the gradient of the plain warp does not need the warped row)
+        // (M1c below replaces the pass in s: what the second half of the blend, the sums and the gradient need of this one)
+        const unsigned xqcur = (unsigned)s.xq;
+        const float cw0x = s.w0x, cw0y = s.w0y, cw0z = s.w0z, cmx = s.mk[0], cmy = s.mk[1], cmz = s.mk[2];
+        const bool coob = s.oob;
 #pragma unroll
         for (int corner = 0; corner < (BLEND ? 4 : 0); ++corner) {
             const float wt = wt2[corner >> 1][corner & 1];
@@ -404,8 +428,10 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         // empty asm statements pin it, they take part in the chain of side effects the barriers are on)
         asm volatile("" : "+v"(al), "+v"(ah));
         __builtin_amdgcn_sched_barrier(0);
-        m1b(m);
-        __builtin_amdgcn_sched_barrier(0);
+        if (M1C_EARLY) {
+            m1c(min(pass + NST, last), m, s);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int corner = 4; corner < (BLEND ? 8 : 4); ++corner) {
             const float wt = wt2[corner >> 1][corner & 1];
@@ -414,24 +440,22 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
             ah = ah + w2 * (nrt_f2){R[corner][2], R[corner][3]};
         }
         nrt_f4 acc = {al[0], al[1], ah[0], ah[1]};
-        const unsigned xqcur = (unsigned)s.xq;
-        // (M1c below replaces the pass in s: what the gradient needs of this one)
-        const float cw0x = s.w0x, cw0y = s.w0y, cw0z = s.w0z, cmx = s.mk[0], cmy = s.mk[1], cmz = s.mk[2];
-        const bool coob = s.oob;
         if (!BWD) {
             if (FILL) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) acc[c] = apply_fill(acc[c], s.oob, a.fill_f);
+                for (int c = 0; c < 4; ++c) acc[c] = apply_fill(acc[c], coob, a.fill_f);
             }
-            if (STORE) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wc_u4, acc), ores, out_lane, (unsigned)s.xq * row_step, 2);
+            if (STORE) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wc_u4, acc), ores, out_lane, xqcur * row_step, 2);
         }
         // the Dice sums / the gradient wait behind M1c: they cover the round trip of its list, and the fixed row (a stream from HBM, the
         // slowest load of the pass, requested at the start of the last step) is first touched here
         const nrt_f4 Tcur = s.T;
         asm volatile("" : "+v"(acc));
         __builtin_amdgcn_sched_barrier(0);
-        m1c(min(pass + NST, last), m, s);
-        __builtin_amdgcn_sched_barrier(0);
+        if (!M1C_EARLY) {
+            m1c(min(pass + NST, last), m, s);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (BWD) {
             // d loss / d warped for this lane's four labels, then its slope along the three axes (interpn_core.h: loc_grad_rows)
             nrt_f2 gl2 = {Tcur[0], Tcur[1]}, gh2 = {Tcur[2], Tcur[3]};       // BWD == 2: the incoming gradient row itself
@@ -488,13 +512,13 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
             fetch_loc(0, A);
             fetch_loc(min(1, last), B);
             fetch_loc(min(2, last), C);
-            m1a(0, A, m); m1b(m); m1c(0, m, A);
+            m1a(0, A, m); m1c(0, m, A);
             issue(A);
             fetch_loc(min(3, last), A);
-            m1a(min(1, last), B, m); m1b(m); m1c(min(1, last), m, B);
+            m1a(min(1, last), B, m); m1c(min(1, last), m, B);
             issue(B);
             fetch_loc(min(4, last), B);
-            m1a(min(2, last), C, m); m1b(m); m1c(min(2, last), m, C);
+            m1a(min(2, last), C, m); m1c(min(2, last), m, C);
             fetch_loc(min(5, last), C);
             issue_x(A);
             __builtin_amdgcn_sched_barrier(0);
@@ -519,10 +543,10 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
         }
         fetch_loc(0, A);
         fetch_loc(min(1, last), B);
-        m1a(0, A, m); m1b(m); m1c(0, m, A);
+        m1a(0, A, m); m1c(0, m, A);
         issue(A);
         fetch_loc(min(2, last), A);
-        m1a(min(1, last), B, m); m1b(m); m1c(min(1, last), m, B);
+        m1a(min(1, last), B, m); m1c(min(1, last), m, B);
         fetch_loc(min(3, last), B);
         __builtin_amdgcn_sched_barrier(0);
         int pass = 0;
