@@ -179,6 +179,7 @@ __global__ __launch_bounds__(256) void affine_warp_bwd(AffWarpArgs a) {
     __shared__ float s_part[4][K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
+// (a butterfly like nrt_wave_sum, but DESCENDING, 32 ... 1: another association, other bits; by hand, a helper changed the registers)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
     }

@@ -16,6 +16,7 @@
 // scatter-add on GPU; everything else is deterministic.
 
 #include "interpn_core.h"
+#include "wave_ops.h"
 #include "wc.h"
 
 namespace {
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(256) void interpn_bwd_rows(InterpBwdArgs ba) {
             }
             if (gl) {
 #pragma unroll
-                for (int d = 0; d < 3; ++d)
+                for (int d = 0; d < 3; ++d)      // (nrt_wave_sum<G> by hand: the helper changes this kernel's instruction stream)
 #pragma unroll
                     for (int off = 1; off < G; off <<= 1) gacc[d] += __shfl_xor(gacc[d], off, 64);
                 if (live[u] && lg == 0) {
@@ -480,19 +481,6 @@ __global__ __launch_bounds__(256) void dice_soft_bwd_vec(const nrt_f4 *__restric
     }
 }
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // G = C/4 lanes per voxel
 template <int G, int LOGITS>
 __global__ __launch_bounds__(256) void wcce_bwd_vec(const nrt_f4 *__restrict__ t, const nrt_f4 *__restrict__ p,
@@ -523,16 +511,16 @@ __global__ __launch_bounds__(256) void wcce_bwd_vec(const nrt_f4 *__restrict__ t
         }
         nrt_f4 o;
         if (LOGITS) {
-            const float mx = group_max<G>(fmaxf(fmaxf(pv[0], pv[1]), fmaxf(pv[2], pv[3])));
+            const float mx = nrt_wave_max<G>(fmaxf(fmaxf(pv[0], pv[1]), fmaxf(pv[2], pv[3])));
             float ex[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) ex[k] = expf(pv[k] - mx);
-            const float se = group_sum<G>((ex[0] + ex[1]) + (ex[2] + ex[3]));
-            const float st = group_sum<G>((tt[0] + tt[1]) + (tt[2] + tt[3]));
+            const float se = nrt_wave_sum<G>((ex[0] + ex[1]) + (ex[2] + ex[3]));
+            const float st = nrt_wave_sum<G>((tt[0] + tt[1]) + (tt[2] + tt[3]));
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = g * (st * ex[k] / se - tt[k]);
         } else {
-            const float s = group_sum<G>((pv[0] + pv[1]) + (pv[2] + pv[3]));
+            const float s = nrt_wave_sum<G>((pv[0] + pv[1]) + (pv[2] + pv[3]));
             float q[4], rq = 0.0f;
             bool in[4];
 #pragma unroll
@@ -541,7 +529,7 @@ __global__ __launch_bounds__(256) void wcce_bwd_vec(const nrt_f4 *__restrict__ t
                 in[k] = q[k] >= 1e-7f && q[k] <= 1.0f - 1e-7f;
                 rq += in[k] ? tt[k] : 0.0f;
             }
-            rq = group_sum<G>(rq);
+            rq = nrt_wave_sum<G>(rq);
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = -g * ((in[k] ? tt[k] / q[k] : 0.0f) - rq) / s;
         }
@@ -669,6 +657,7 @@ __device__ __forceinline__ void warp_dice_bwd_rows_body(const InterpBwdArgs &ba,
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
                 if (!lane_live) gacc[d] = 0.0f;           // exact zeros (a NaN weight times a zero row would not be)
+                // (nrt_wave_sum<G> by hand: the helper changes this kernel's instruction stream)
 #pragma unroll
                 for (int off = 1; off < G; off <<= 1) gacc[d] += __shfl_xor(gacc[d], off, 64);
             }
@@ -812,13 +801,7 @@ __global__ __launch_bounds__(256, 3) void warp_dice_bwd_xm(InterpBwdArgs ba, con
         // sum over the voxel's 8 lanes on the DPP network (quad xor 1, quad xor 2, then the mirrored half: after the two quad steps a
         // quad's lanes hold the same value, so i <-> 7 - i adds the other quad exactly as xor 4 would); no LDS round trips
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            float r = gacc[d];
-            r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xF, 0xF, true));
-            r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x4E, 0xF, 0xF, true));
-            r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x141, 0xF, 0xF, true));
-            gacc[d] = r;
-        }
+        for (int d = 0; d < 3; ++d) gacc[d] = nrt_dpp_sum8(gacc[d]);
         if (LIVE && lg == 0) {
             float *dst = gl + (size_t)Q * 3;
             dst[0] = gacc[0]; dst[1] = gacc[1]; dst[2] = gacc[2];
@@ -962,7 +945,7 @@ __global__ __launch_bounds__(BS_NT) void interpn_bwd_vol_sort(InterpBwdArgs ba) 
             unsigned c[SPT], tot = 0u;
 #pragma unroll
             for (int j = 0; j < SPT; ++j) { c[j] = cnt[threadIdx.x * SPT + j]; tot += c[j] | (c[j] ? 0x10000u : 0u); }
-            unsigned incl = tot;
+            unsigned incl = tot;      // (nrt_wave_scan_incl by hand: the helper changes this kernel's instruction stream)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const unsigned o = (unsigned)__shfl_up((int)incl, off, 64);
@@ -1092,7 +1075,7 @@ __global__ __launch_bounds__(256) void interpn_bwd_vol_sort_any(InterpBwdArgs ba
             unsigned c[SPT], tot = 0u;
 #pragma unroll
             for (int j = 0; j < SPT; ++j) { c[j] = cnt[threadIdx.x * SPT + j]; tot += c[j] | (c[j] ? 0x10000u : 0u); }
-            unsigned incl = tot;
+            unsigned incl = tot;      // (nrt_wave_scan_incl by hand: the helper changes this kernel's instruction stream)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const unsigned o = (unsigned)__shfl_up((int)incl, off, 64);

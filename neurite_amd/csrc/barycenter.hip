@@ -28,7 +28,7 @@
 //
 // No atomics.  Every sum has a fixed partition and a fixed order given the shapes and the alignment of the pointers: results are
 // run-to-run bit-identical.  Products are accumulated with fmaf (one rounding per term).
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 
@@ -228,6 +228,7 @@ __device__ __forceinline__ void bc_block_sum(const float (&v)[W], float (*red)[N
 #pragma unroll
     for (int c = 0; c < W; ++c) {
         s[c] = v[c];
+        // (nrt_wave_sum_from by hand: through the helper bc_fwd_inner<., 8> changes its SGPRs)
         for (int off = lanes_x; off < NRT_WAVE; off <<= 1) s[c] += __shfl_xor(s[c], off, NRT_WAVE);
     }
     __syncthreads();                                        // the previous row has been read
@@ -241,11 +242,6 @@ __device__ __forceinline__ void bc_block_sum(const float (&v)[W], float (*red)[N
 #pragma unroll
         for (int c = 0; c < W; ++c) dst[c] = s[c];
     }
-}
-
-__device__ __forceinline__ float bc_wave_sum(float s) {
-    for (int off = 1; off < NRT_WAVE; off <<= 1) s += __shfl_xor(s, off, NRT_WAVE);
-    return s;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -384,11 +380,11 @@ bc_fwd_trail(const void *__restrict__ x, float *__restrict__ part, BcDims P, BcP
 #pragma unroll
     for (int d = 0; d < kMaxK - 1; ++d) {
         if (d < P.k - 1) {
-            const float s = bc_wave_sum(a.acc[d][0]);
+            const float s = nrt_wave_sum(a.acc[d][0]);
             if (lane == 0) red[wave][d] = s;
         }
     }
-    const float st = bc_wave_sum(a.t[0]), sd = bc_wave_sum(a.den[0]);
+    const float st = nrt_wave_sum(a.t[0]), sd = nrt_wave_sum(a.den[0]);
     if (lane == 0) {
         red[wave][P.k - 1] = st;
         red[wave][P.k] = sd;

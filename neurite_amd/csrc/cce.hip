@@ -11,7 +11,7 @@
 // widened to fp32 in registers; all arithmetic and the reduction are fp32 (final stage float64).
 // Reduction: lane partials -> wave shuffles -> LDS -> per-block partial -> fixed-order second stage.
 
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -119,18 +119,15 @@ __global__ __launch_bounds__(CCE_BLOCK) void wcce_vec(const void *__restrict__ y
         float lq[4];
         if (LOGITS) {
             float m = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3]));
-#pragma unroll
-            for (int off = 1; off < G; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, NRT_WAVE));
+            m = nrt_wave_max<G>(m);
             float se = (lse_exp(p[0] - m) + lse_exp(p[1] - m)) + (lse_exp(p[2] - m) + lse_exp(p[3] - m));
-#pragma unroll
-            for (int off = 1; off < G; off <<= 1) se += __shfl_xor(se, off, NRT_WAVE);
+            se = nrt_wave_sum<G>(se);
             const float lse = lse_log(se);
 #pragma unroll
             for (int k = 0; k < 4; ++k) lq[k] = (p[k] - m) - lse;
         } else {
             float s = (p[0] + p[1]) + (p[2] + p[3]);
-#pragma unroll
-            for (int off = 1; off < G; off <<= 1) s += __shfl_xor(s, off, NRT_WAVE);
+            s = nrt_wave_sum<G>(s);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float q = p[k] / s;
@@ -147,6 +144,7 @@ __global__ __launch_bounds__(CCE_BLOCK) void wcce_vec(const void *__restrict__ y
         }
         if (!real) l = 0.0f;
         if (PERVOX) {
+            // (nrt_wave_sum<G> by hand: through the helper wcce_vec<1> takes 20 more VGPRs)
             float lv = l;
 #pragma unroll
             for (int off = 1; off < G; off <<= 1) lv += __shfl_xor(lv, off, NRT_WAVE);
@@ -154,6 +152,7 @@ __global__ __launch_bounds__(CCE_BLOCK) void wcce_vec(const void *__restrict__ y
         }
         acc += l;
     }
+    // (nrt_wave_sum by hand: through the helper wcce_vec<1> takes 20 more VGPRs)
     for (int off = 1; off < NRT_WAVE; off <<= 1) acc += __shfl_xor(acc, off, NRT_WAVE);
     __shared__ float red[CCE_BLOCK / NRT_WAVE];
     if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = acc;
@@ -229,6 +228,7 @@ __global__ __launch_bounds__(CCE_BLOCK) void wcce_generic(const void *__restrict
             acc += l;
         }
     }
+    // (nrt_wave_sum by hand, as in wcce_vec)
     for (int off = 1; off < NRT_WAVE; off <<= 1) acc += __shfl_xor(acc, off, NRT_WAVE);
     __shared__ float red[CCE_BLOCK / NRT_WAVE];
     if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = acc;

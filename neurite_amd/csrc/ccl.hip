@@ -24,7 +24,7 @@
 // parent word only decreases (ccl_core.h).  Every other pass reads what an earlier launch finished.  The final parent array does not
 // depend on the schedule (the root is the component's smallest index), the sums and maxima are integer, so the results are
 // bit-identical run to run.  No host synchronisation, no allocation: the calls capture into a graph.
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 #include "ccl_core.h"
 
@@ -86,10 +86,7 @@ __device__ __forceinline__ void ccl_block(const CclGeom &g, unsigned &entry, uns
 // inclusive maximum of x over the threads of the block up to this one; every thread of the block calls it
 __device__ __forceinline__ int ccl_block_scan_max(int x, int *red) {
     const int lane = threadIdx.x & (NRT_WAVE - 1), wave = threadIdx.x / NRT_WAVE;
-    for (int off = 1; off < NRT_WAVE; off <<= 1) {
-        const int y = __shfl_up(x, off, NRT_WAVE);
-        if (lane >= off) x = max(x, y);
-    }
+    x = nrt_wave_scan_incl(x, lane, nrt_op_max());
     __syncthreads();
     if (lane == NRT_WAVE - 1) red[wave] = x;
     __syncthreads();
@@ -144,25 +141,10 @@ ccl_merge(CclSrc src, CclGeom g, int connectivity, int *parent) {
     }
 }
 
-// sum over the block; every thread of the block calls it
-__device__ __forceinline__ int ccl_block_sum(int x, int *red) {
-    for (int off = 1; off < NRT_WAVE; off <<= 1) x += __shfl_xor(x, off, NRT_WAVE);
-    __syncthreads();
-    if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = x;
-    __syncthreads();
-    int s = 0;
-    for (int w = 0; w < kWaves; ++w) s += red[w];
-    return s;
-}
-
 // exclusive prefix of x over the threads of the block, and the block's total; every thread of the block calls it
 __device__ __forceinline__ int ccl_block_scan(int x, int *red, int &total) {
     const int lane = threadIdx.x & (NRT_WAVE - 1), wave = threadIdx.x / NRT_WAVE;
-    int incl = x;
-    for (int off = 1; off < NRT_WAVE; off <<= 1) {
-        const int y = __shfl_up(incl, off, NRT_WAVE);
-        if (lane >= off) incl += y;
-    }
+    const int incl = nrt_wave_scan_incl(x, lane, nrt_op_sum());
     __syncthreads();
     if (lane == NRT_WAVE - 1) red[wave] = incl;
     __syncthreads();
@@ -187,7 +169,7 @@ ccl_flatten(CclGeom g, int *parent, int *__restrict__ counts) {
         const int r = ccl_find_compress<CclDevMem>(pe, (int)v);
         reps += r == (int)v;
     }
-    reps = ccl_block_sum(reps, red);
+    reps = nrt_block_sum<kWaves>(reps, red);
     if (threadIdx.x == 0) counts[blockIdx.x] = reps;
 }
 

@@ -24,7 +24,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "nrt_common.h"
+#include "wave_ops.h"
 #include "activations.h"
 
 namespace {
@@ -506,13 +506,11 @@ __global__ __launch_bounds__(256) void conv1x1_vec(const float *__restrict__ x, 
             }
             if (softmax) {
                 float m = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-#pragma unroll
-                for (int off = 1; off < G; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+                m = nrt_wave_max<G>(m);
                 float sum = 0.0f;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { acc[e] = softmax_exp(acc[e] - m); sum += acc[e]; }
-#pragma unroll
-                for (int off = 1; off < G; off <<= 1) sum += __shfl_xor(sum, off, 64);
+                sum = nrt_wave_sum<G>(sum);
                 const float inv = softmax_rcp(sum);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[e] *= inv;
@@ -577,13 +575,11 @@ __global__ __launch_bounds__(256) void conv1x1_rows(const float *__restrict__ x,
                 }
                 if (softmax) {
                     float m = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-#pragma unroll
-                    for (int off = 1; off < G; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+                    m = nrt_wave_max<G>(m);
                     float sum = 0.0f;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { acc[e] = softmax_exp(acc[e] - m); sum += acc[e]; }
-#pragma unroll
-                    for (int off = 1; off < G; off <<= 1) sum += __shfl_xor(sum, off, 64);
+                    sum = nrt_wave_sum<G>(sum);
                     const float inv = softmax_rcp(sum);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[e] *= inv;
@@ -792,14 +788,12 @@ __global__ __launch_bounds__(256) void softmax_lastdim_vec(const f32x4 *__restri
         const long long v = live ? vv : n - 1;
         const f32x4 xv = x[v * G + lg];
         float m = fmaxf(fmaxf(xv[0], xv[1]), fmaxf(xv[2], xv[3]));
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        m = nrt_wave_max<G>(m);
         f32x4 e;
 #pragma unroll
         for (int k = 0; k < 4; ++k) e[k] = softmax_exp(xv[k] - m);
         float s = (e[0] + e[1]) + (e[2] + e[3]);
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) s += __shfl_xor(s, off, 64);
+        s = nrt_wave_sum<G>(s);
         const float inv = softmax_rcp(s);
 #pragma unroll
         for (int k = 0; k < 4; ++k) e[k] *= inv;

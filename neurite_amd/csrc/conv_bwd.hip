@@ -17,7 +17,7 @@
 
 #include <type_traits>
 
-#include "nrt_common.h"
+#include "wave_ops.h"
 #include "activations.h"
 
 namespace {
@@ -126,8 +126,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_vec(const nrt_f4 *__restrict_
         const long long v = live ? vv : nvox - 1;
         const nrt_f4 yv = y[v * G + lg], gv = g[v * G + lg];
         float dot = (gv[0] * yv[0] + gv[1] * yv[1]) + (gv[2] * yv[2] + gv[3] * yv[3]);
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) dot += __shfl_xor(dot, off, 64);
+        dot = nrt_wave_sum<G>(dot);
         nrt_f4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = yv[k] * (gv[k] - dot);

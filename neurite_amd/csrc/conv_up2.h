@@ -98,15 +98,6 @@ __host__ __device__ constexpr int u2_newer(int s, int P, int F, int D, int S, in
     return (hi - s) * F;
 }
 
-__device__ __forceinline__ float u2_row_ror(float v, const int n) {      // v of lane (i + n) % 16 inside each row of 16 lanes
-    switch (n) {
-        case 8: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-        case 4: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));
-        case 2: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));
-        default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));
-    }
-}
-
 // order of a tile's chunks: bit k set = chunk k is a B (skip) chunk, the nB of them spread evenly among the nA + nB (Bresenham)
 __host__ __device__ inline unsigned u2_chunk_seq(int nA, int nB) {
     const int n = nA + nB;
@@ -297,15 +288,13 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void conv3d_up2_mfma(ConvArgs
                 for (int j = 0; j < HN; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { d[j][r] += hb[j][r]; m = fmaxf(m, d[j][r]); }
-                m = fmaxf(m, __shfl_xor(m, 16, NRT_WAVE));
-                m = fmaxf(m, __shfl_xor(m, 32, NRT_WAVE));
+                m = nrt_wave_max<NRT_WAVE, 16>(m);
                 float se = 0.0f;
 #pragma unroll
                 for (int j = 0; j < HN; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { d[j][r] = softmax_exp(d[j][r] - m); se += d[j][r]; }
-                se += __shfl_xor(se, 16, NRT_WAVE);
-                se += __shfl_xor(se, 32, NRT_WAVE);
+                se = nrt_wave_sum<NRT_WAVE, 16>(se);
                 const float inv = softmax_rcp(se);
 #pragma unroll
                 for (int j = 0; j < HN; ++j)

@@ -89,11 +89,8 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_soft_vec(const void *__restri
             // y / sum_l y with divide_no_nan (metrics.py:435-436); the label sum spans the lane-group
             float st = (t[0] + t[1]) + (t[2] + t[3]);
             float sp = (p[0] + p[1]) + (p[2] + p[3]);
-#pragma unroll
-            for (int off = 1; off < G; off <<= 1) {
-                st += __shfl_xor(st, off, NRT_WAVE);
-                sp += __shfl_xor(sp, off, NRT_WAVE);
-            }
+            st = nrt_wave_sum<G>(st);
+            sp = nrt_wave_sum<G>(sp);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 t[k] = (st == 0.0f) ? 0.0f : t[k] / st;
@@ -115,10 +112,11 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_soft_vec(const void *__restri
     // ---- wave: combine the 64/G lane-groups (same label quad) ---------------------------------
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        stp[k] = wave_xor_add(stp[k], G);
-        stt[k] = wave_xor_add(stt[k], G);
-        spp[k] = wave_xor_add(spp[k], G);
+        stp[k] = nrt_wave_sum_from(stp[k], G);
+        stt[k] = nrt_wave_sum_from(stt[k], G);
+        spp[k] = nrt_wave_sum_from(spp[k], G);
     }
+    // (nrt_wave_min / nrt_wave_max, four chains in one loop by hand: helpers change the instruction stream)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
@@ -187,6 +185,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_soft_generic(const void *__re
     sh[0 * DICE_BLOCK + threadIdx.x] = a0;
     sh[1 * DICE_BLOCK + threadIdx.x] = a1;
     sh[2 * DICE_BLOCK + threadIdx.x] = a2;
+    // (nrt_wave_min / nrt_wave_max, four chains in one loop by hand: helpers change the instruction stream)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
@@ -269,9 +268,9 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_hard_vec(const void *__restri
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        ntp[k] = wave_xor_add(ntp[k], G);
-        nt[k] = wave_xor_add(nt[k], G);
-        np_[k] = wave_xor_add(np_[k], G);
+        ntp[k] = nrt_wave_sum_from(ntp[k], G);
+        nt[k] = nrt_wave_sum_from(nt[k], G);
+        np_[k] = nrt_wave_sum_from(np_[k], G);
     }
     __shared__ unsigned red[DICE_BLOCK / NRT_WAVE][3 * L];
     __shared__ float redm[DICE_BLOCK / NRT_WAVE][4];
@@ -285,6 +284,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_hard_vec(const void *__restri
         }
     }
     if (MINMAX) {
+        // (nrt_wave_min / nrt_wave_max, four chains in one loop by hand: helpers change the instruction stream)
         for (int off = 1; off < NRT_WAVE; off <<= 1) {
             mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
             mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void dice_hard_label_private(const int 
         unsigned sum = 0;
         if (r < 3 * L)
             for (int k = 0; k < DICE_BLOCK / 2; ++k) sum += hist[r * DICE_BLOCK + half * (DICE_BLOCK / 2) + ((k + r) & (DICE_BLOCK / 2 - 1))];
-        sum += __shfl_xor(sum, 1, NRT_WAVE);
+        sum = nrt_wave_sum<2>(sum);
         if (r < 3 * L && half == 0) ipart[pbase * 3 * L + r] = sum;
     }
 }

@@ -1,8 +1,8 @@
-// Shared pieces of the Dice reductions (dice.hip, fused.hip): workspace layout, wave helpers and the
-// deterministic two-level second stage.
+// Shared pieces of the Dice reductions (dice.hip, fused.hip): workspace layout and the deterministic two-level
+// second stage.  The wave reductions are in wave_ops.h.
 #pragma once
 
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -47,13 +47,6 @@ inline DiceWs dice_ws_carve(void *ws, int L, int batch) {
     w.gsum = (double *)p; p += grp * 3 * L * sizeof(double);
     w.gmm = (float *)p;
     return w;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_xor_add(T v, int from) {
-    // sum over lanes that agree in (lane % from): xor offsets from, 2*from, ..., 32
-    for (int off = from; off < NRT_WAVE; off <<= 1) v += __shfl_xor(v, off, NRT_WAVE);
-    return v;
 }
 
 // Second stage, two levels so that no thread walks a long dependent chain (a single-level version took

@@ -254,6 +254,7 @@ surface_stats(const int *__restrict__ t, const int *__restrict__ labels, const f
         if (hist && x2 >= 0.0f && x2 < (float)nbins) atomicAdd(hist + (size_t)bl * nbins + (unsigned)x2, 1u);
     }
     // lanes by xor shuffles, waves in wave order: a fixed order
+    // (nrt_wave_sum / nrt_wave_max by hand, three chains in one loop: apart, the instruction count moves by 1.6 %)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         cnt += __shfl_xor(cnt, off, NRT_WAVE);
         mx = fmaxf(mx, __shfl_xor(mx, off, NRT_WAVE));

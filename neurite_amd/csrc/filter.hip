@@ -310,6 +310,7 @@ __global__ __launch_bounds__(256) void minmax_reduce(const float *__restrict__ x
             const int k = f2key(xo[e]);
             mn = min(mn, k); mx = max(mx, k);
         }
+        // (nrt_wave_min / nrt_wave_max by hand, here and in block_minmax: apart, the min-max kernels' instruction counts move by up to 5 %)
         for (int off = 1; off < 64; off <<= 1) { mn = min(mn, __shfl_xor(mn, off, 64)); mx = max(mx, __shfl_xor(mx, off, 64)); }
         if ((threadIdx.x & 63) == 0) { atomicMin(&sm[0], mn); atomicMax(&sm[1], mx); }
     } else {
@@ -597,6 +598,7 @@ __global__ __launch_bounds__(256) void conv1d_dk_partial(DkArgs a) {
 #pragma unroll
         for (int q = 0; q < DK_TB; ++q) {
             double v = dacc[q];
+            // (nrt_wave_sum by hand: through the helper conv1d_dk_partial's instruction count moves by 1.7 %)
             for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
             if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
         }

@@ -285,10 +285,11 @@ __device__ __forceinline__ void warp_dice_tile_body(BodyArg<PAD && MODE == NRT_L
     // ---- block reduction (identical tree to dice_soft_vec) -------------------------------------
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        stp[c] = wave_xor_add(stp[c], G);
-        stt[c] = wave_xor_add(stt[c], G);
-        spp[c] = wave_xor_add(spp[c], G);
+        stp[c] = nrt_wave_sum_from(stp[c], G);
+        stt[c] = nrt_wave_sum_from(stt[c], G);
+        spp[c] = nrt_wave_sum_from(spp[c], G);
     }
+    // (nrt_wave_min / nrt_wave_max, four chains in one loop by hand: helpers change the instruction stream)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));

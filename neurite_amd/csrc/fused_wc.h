@@ -469,13 +469,7 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
             // sum over the voxel's 8 lanes on the DPP network (quad xor 1, quad xor 2, then the mirrored half: after the two quad steps a
             // quad's lanes hold the same value, so i <-> 7 - i adds the other quad exactly as xor 4 would)
 #pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                float r = gacc[d];
-                r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xF, 0xF, true));
-                r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x4E, 0xF, 0xF, true));
-                r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x141, 0xF, 0xF, true));
-                gacc[d] = r;
-            }
+            for (int d = 0; d < 3; ++d) gacc[d] = nrt_dpp_sum8(gacc[d]);
             // (one store per 8 passes with all lanes active, lane p keeping the sums of pass 8 k + p, measured the same 1.19 ms)
             __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(wc_u3, (wc_f3){gacc[0], gacc[1], gacc[2]}), gres, gl_lane, xqcur * loc_step, 0);
         } else if (DICE) {
@@ -572,10 +566,11 @@ __device__ __forceinline__ void wc_item(const InterpArgs &a, const TileGeom &tg,
     // ---- block reduction (identical tree to warp_dice_tile / dice_soft_vec) ---------------------------------------------------
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        stp[c] = wave_xor_add(stp[c], G);
-        stt[c] = wave_xor_add(stt[c], G);
-        spp[c] = wave_xor_add(spp[c], G);
+        stp[c] = nrt_wave_sum_from(stp[c], G);
+        stt[c] = nrt_wave_sum_from(stt[c], G);
+        spp[c] = nrt_wave_sum_from(spp[c], G);
     }
+    // (nrt_wave_min / nrt_wave_max, four chains in one loop by hand: helpers change the instruction stream)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));

@@ -24,7 +24,7 @@
 //                  at the end: the indicator sums are short sums of cofactors, exact on integer fields.
 // No atomics, no host synchronisation, no memset; every sum has a fixed partition and order given the shapes: run-to-run bit-identical.
 // Partials travel as the two 32-bit halves of a float64, so the workspace needs 4-byte alignment only.
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 
@@ -48,30 +48,6 @@ __device__ __forceinline__ void store_f64(unsigned *p, double s) {
     p[1] = (unsigned)__double2loint(s);
 }
 __device__ __forceinline__ double load_f64(const unsigned *p) { return __hiloint2double((int)p[0], (int)p[1]); }
-
-// the block's sum of one double per thread, in a fixed order (lanes by xor shuffles, waves in wave order); valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int off = 1; off < NRT_WAVE; off <<= 1) v += __shfl_xor(v, off, NRT_WAVE);
-    __syncthreads();
-    if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int w = 1; w < kWaves; ++w) s += red[w];
-    return s;
-}
-// the same for min (SIGN -1) and max (SIGN +1)
-template <int SIGN> __device__ __forceinline__ float block_extreme(float v, float *red) {
-    for (int off = 1; off < NRT_WAVE; off <<= 1) {
-        const float o = __shfl_xor(v, off, NRT_WAVE);
-        v = SIGN < 0 ? fminf(v, o) : fmaxf(v, o);
-    }
-    __syncthreads();
-    if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < kWaves; ++w) s = SIGN < 0 ? fminf(s, red[w]) : fmaxf(s, red[w]);
-    return s;
-}
 
 // the coordinates of voxel v of a batch entry and the voxel strides of the axes
 template <int ND> struct JacPos { int i[ND]; };
@@ -165,9 +141,9 @@ jacdet_fwd(const float *__restrict__ disp, JacGeom g, float *__restrict__ det, u
         ls += (double)fmaxf(0.0f, -d);
     }
     if (!part) return;
-    const double c = block_sum((double)cnt, red);                                // (an integer below 2^31: exact)
-    const float lo = block_extreme<-1>(mn, redf), hi = block_extreme<1>(mx, redf);
-    const double ts = block_sum(s, red), tss = block_sum(ss, red), tls = block_sum(ls, red);
+    const double c = nrt_block_sum<kWaves>((double)cnt, red);                                // (an integer below 2^31: exact)
+    const float lo = nrt_block_reduce<kWaves>(mn, redf, nrt_op_min()), hi = nrt_block_reduce<kWaves>(mx, redf, nrt_op_max());
+    const double ts = nrt_block_sum<kWaves>(s, red), tss = nrt_block_sum<kWaves>(ss, red), tls = nrt_block_sum<kWaves>(ls, red);
     if (threadIdx.x == 0) {
         unsigned *row = part + (size_t)lb * kPartWords;
         row[0] = (unsigned)(int)c;
@@ -196,9 +172,9 @@ jacdet_finish(const unsigned *__restrict__ part, JacGeom g, void *__restrict__ s
         ss += load_f64(row + 5);
         ls += load_f64(row + 7);
     }
-    const double tc = block_sum(c, red);
-    const float lo = block_extreme<-1>(mn, redf), hi = block_extreme<1>(mx, redf);
-    const double ts = block_sum(s, red), tss = block_sum(ss, red), tls = block_sum(ls, red);
+    const double tc = nrt_block_sum<kWaves>(c, red);
+    const float lo = nrt_block_reduce<kWaves>(mn, redf, nrt_op_min()), hi = nrt_block_reduce<kWaves>(mx, redf, nrt_op_max());
+    const double ts = nrt_block_sum<kWaves>(s, red), tss = nrt_block_sum<kWaves>(ss, red), tls = nrt_block_sum<kWaves>(ls, red);
     if (threadIdx.x != 0) return;
     if (stats) {
         long long *ci = (long long *)stats + 5LL * blockIdx.x;

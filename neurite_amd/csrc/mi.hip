@@ -10,7 +10,7 @@
 // floats per item.  The [items, nb, nb]-sized arithmetic that follows (normalisation, log, sum) is host-side glue.
 // The backward recomputes the weights: dL/dx_v = sum_i (sum_j G_ij wy_j(v) + gx_i) * wx_i(v) * (-2 alpha (x_v - c_i)).
 
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -85,6 +85,7 @@ __global__ __launch_bounds__(256) void mi_joint(MiArgs a) {
     __shared__ float red[4][NJ + 2 * NM];
 #pragma unroll
     for (int t = 0; t < NBT; ++t) {
+        // (nrt_wave_sum<NRT_WAVE, 16> by hand: through the helper mi_joint changes its registers and occupancy)
         sx[t] += __shfl_xor(sx[t], 16, 64); sx[t] += __shfl_xor(sx[t], 32, 64);
         sy[t] += __shfl_xor(sy[t], 16, 64); sy[t] += __shfl_xor(sy[t], 32, 64);
         if (l4 == 0) { red[wv][NJ + 16 * t + l15] = sx[t]; red[wv][NJ + NM + 16 * t + l15] = sy[t]; }
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(256) void mi_joint_bwd_mfma(MiArgs a, const float *
 #pragma unroll
                     for (int r = 0; r < 4; ++r) part += (T[r] + gsxb[it][r]) * wx[it][r] * (m2a * dx[it][r]);
                 }
+                // (nrt_wave_sum<NRT_WAVE, 16> by hand, here and for gy: through the helper mi_joint_bwd_mfma<2> changes its registers)
                 part += __shfl_xor(part, 16, 64);
                 part += __shfl_xor(part, 32, 64);
                 if (s == g4) minex = part;
@@ -321,8 +323,9 @@ __global__ __launch_bounds__(256) void colsum(const float *__restrict__ x, long 
 // metrics.py:262-281 on one item's joint histogram and marginal sums: pxy = J / (sum J + eps), px = sx / (sum sx + eps),
 // py likewise, mi = sum_ij pxy log(pxy / (px_i py_j + eps) + eps).  One block per item (the inference path; under autograd the
 // same arithmetic runs as torch ops so that d mi / d J comes from autodiff).
+// (not nrt_block_sum: the four wave sums meet pairwise here, which rounds differently from wave order)
 __device__ __forceinline__ float block_sum(float v, float *sm) {          // every lane gets the block's sum
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    v = nrt_wave_sum(v);
     __syncthreads();                                                       // sm may still be read from a previous call
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -1,4 +1,5 @@
-// Shared device/host helpers for the gfx950 kernels (wave64 everywhere; no CUDA compatibility).
+// Shared device/host helpers for the gfx950 kernels (wave64 everywhere; no CUDA compatibility).  The cross-lane and block
+// reductions the kernels share are in wave_ops.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -160,6 +160,7 @@ seg_argmax_group(const void *__restrict__ pred, long long nvox, int C, int G, Se
                 const bool take = seg_beats(ov, oi, bv, bi);
                 bv = take ? ov : bv;
                 bi = take ? oi : bi;
+                // (nrt_wave_sum over the group, by hand: G is a run-time value and the loop is the arg-max's)
                 if (PROB) sum += __shfl_xor(sum, off, NRT_WAVE);
             }
             if (PROB) {

@@ -17,13 +17,6 @@ namespace {
 constexpr float SEG_KERAS_EPS = 1e-7f;
 
 template <int G>
-__device__ __forceinline__ float seg_group_sum(float v) {
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) v += __shfl_xor(v, off, NRT_WAVE);
-    return v;
-}
-
-template <int G>
 __global__ __launch_bounds__(DICE_BLOCK) void seg_loss_vec(const nrt_f4 *__restrict__ yt, const nrt_f4 *__restrict__ yp,
                                                            const float *__restrict__ lw, long long nvox, float smooth,
                                                            float *__restrict__ fpart, float *__restrict__ mpart,
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void seg_loss_vec(const nrt_f4 *__restr
             mnt = fminf(mnt, t[k]); mxt = fmaxf(mxt, t[k]);
             mnp = fminf(mnp, p[k]); mxp = fmaxf(mxp, p[k]);
         }
-        const float s = seg_group_sum<G>((p[0] + p[1]) + (p[2] + p[3]));      // cce.hip: wcce_vec, probabilities
+        const float s = nrt_wave_sum<G>((p[0] + p[1]) + (p[2] + p[3]));      // cce.hip: wcce_vec, probabilities
         float l = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -71,10 +64,11 @@ __global__ __launch_bounds__(DICE_BLOCK) void seg_loss_vec(const nrt_f4 *__restr
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        stp[k] = wave_xor_add(stp[k], G);
-        stt[k] = wave_xor_add(stt[k], G);
-        spp[k] = wave_xor_add(spp[k], G);
+        stp[k] = nrt_wave_sum_from(stp[k], G);
+        stt[k] = nrt_wave_sum_from(stt[k], G);
+        spp[k] = nrt_wave_sum_from(spp[k], G);
     }
+    // (nrt_wave_min / nrt_wave_max / nrt_wave_sum over the wave, five chains in one loop by hand: apart, seg_loss_vec<1> drops to 3 waves per SIMD)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         mnt = fminf(mnt, __shfl_xor(mnt, off, NRT_WAVE)); mxt = fmaxf(mxt, __shfl_xor(mxt, off, NRT_WAVE));
         mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE));
@@ -159,7 +153,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_vec(const nrt_f4 *__restrict
 #pragma unroll 2
     for (long long v = vbeg + g; v < vend; v += NG) {
         const nrt_f4 t = yt[base + v * G + lg], p = yp[base + v * G + lg];
-        const float s = seg_group_sum<G>((p[0] + p[1]) + (p[2] + p[3]));      // backward.hip: wcce_bwd_vec, probabilities
+        const float s = nrt_wave_sum<G>((p[0] + p[1]) + (p[2] + p[3]));      // backward.hip: wcce_bwd_vec, probabilities
         float tt[4], q[4], rq = 0.0f;
         bool in[4];
 #pragma unroll
@@ -170,13 +164,13 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_vec(const nrt_f4 *__restrict
             in[k] = q[k] >= SEG_KERAS_EPS && q[k] <= 1.0f - SEG_KERAS_EPS;
             rq += in[k] ? tt[k] : 0.0f;
         }
-        rq = seg_group_sum<G>(rq);
+        rq = nrt_wave_sum<G>(rq);
         nrt_f4 d;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             d[k] = (ca[k] * t[k] + cb[k] * p[k]) + (-gc * ((in[k] ? tt[k] / q[k] : 0.0f) - rq) / s);
         if (SM) {                                                 // conv_bwd.hip: softmax_bwd_vec
-            const float dot = seg_group_sum<G>((d[0] * p[0] + d[1] * p[1]) + (d[2] * p[2] + d[3] * p[3]));
+            const float dot = nrt_wave_sum<G>((d[0] * p[0] + d[1] * p[1]) + (d[2] * p[2] + d[3] * p[3]));
 #pragma unroll
             for (int k = 0; k < 4; ++k) d[k] = p[k] * (d[k] - dot);
         }

@@ -23,13 +23,6 @@ constexpr float SEGL_KERAS_EPS = 1e-7f;
 constexpr int SEGL_MAX_LABELS = 256;
 constexpr int SEGL_BWD_BLOCK = 256;
 
-template <int G>
-__device__ __forceinline__ float segl_group_sum(float v) {
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) v += __shfl_xor(v, off, NRT_WAVE);
-    return v;
-}
-
 // what a lane of a lane group owns: the labels l0 ... l0 + 3 that are < L (none in the padding lanes of the group)
 struct SeglLane {
     int lg, l0;
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void seg_lab_fwd(const int *__restrict_
             }
         }
         if (CCE) {
-            const float sp = segl_group_sum<G>((p[0] + p[1]) + (p[2] + p[3]));
+            const float sp = nrt_wave_sum<G>((p[0] + p[1]) + (p[2] + p[3]));
             float l = 0.0f;
             if (smooth != 0.0f) {                                 // every label carries weight: seg_loss_vec as it stands
 #pragma unroll
@@ -166,9 +159,9 @@ __global__ __launch_bounds__(DICE_BLOCK) void seg_lab_fwd(const int *__restrict_
     if (DICE) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            stp[k] = wave_xor_add(stp[k], G);
-            stt[k] = wave_xor_add(stt[k], G);
-            spp[k] = wave_xor_add(spp[k], G);
+            stp[k] = nrt_wave_sum_from(stp[k], G);
+            stt[k] = nrt_wave_sum_from(stt[k], G);
+            spp[k] = nrt_wave_sum_from(spp[k], G);
         }
         if (lane < Gr) {                                          // (lane < G: lg == lane, s.valid is this lane's)
 #pragma unroll
@@ -181,6 +174,7 @@ __global__ __launch_bounds__(DICE_BLOCK) void seg_lab_fwd(const int *__restrict_
             }
         }
     }
+    // (nrt_wave_min / nrt_wave_max / nrt_wave_sum by hand: one loop, each chain only in the instances that need it)
     for (int off = 1; off < NRT_WAVE; off <<= 1) {
         if (DICE) { mnp = fminf(mnp, __shfl_xor(mnp, off, NRT_WAVE)); mxp = fmaxf(mxp, __shfl_xor(mxp, off, NRT_WAVE)); }
         if (CCE) cce += __shfl_xor(cce, off, NRT_WAVE);
@@ -250,7 +244,7 @@ __global__ __launch_bounds__(SEGL_BWD_BLOCK) void seg_lab_bwd(const int *__restr
             for (int k = 0; k < 4; ++k) d[k] = ca[k] * (kk == (unsigned)k ? 1.0f : 0.0f) + cb[k] * p[k];
         }
         if (CCE) {                                                // backward.hip: wcce_bwd_vec, probabilities
-            const float sp = segl_group_sum<G>((p[0] + p[1]) + (p[2] + p[3]));
+            const float sp = nrt_wave_sum<G>((p[0] + p[1]) + (p[2] + p[3]));
             float tt[4], q[4], rq = 0.0f;
             bool in[4];
 #pragma unroll
@@ -261,7 +255,7 @@ __global__ __launch_bounds__(SEGL_BWD_BLOCK) void seg_lab_bwd(const int *__restr
                 in[k] = s.valid[k] && q[k] >= SEGL_KERAS_EPS && q[k] <= 1.0f - SEGL_KERAS_EPS;
                 rq += in[k] ? tt[k] : 0.0f;
             }
-            rq = segl_group_sum<G>(rq);
+            rq = nrt_wave_sum<G>(rq);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float c = -gc * ((in[k] ? tt[k] / q[k] : 0.0f) - rq) / sp;
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(SEGL_BWD_BLOCK) void seg_lab_bwd(const int *__restr
         for (int k = 0; k < 4; ++k)
             if (!s.valid[k]) d[k] = 0.0f;
         if (SM) {                                                 // conv_bwd.hip: softmax_bwd_vec
-            const float dot = segl_group_sum<G>((d[0] * p[0] + d[1] * p[1]) + (d[2] * p[2] + d[3] * p[3]));
+            const float dot = nrt_wave_sum<G>((d[0] * p[0] + d[1] * p[1]) + (d[2] * p[2] + d[3] * p[3]));
 #pragma unroll
             for (int k = 0; k < 4; ++k) d[k] = p[k] * (d[k] - dot);
         }

@@ -19,7 +19,7 @@
 // adds of one wave to one LDS address are carried out one after the other.  sel_add therefore adds per wave: the lanes that hold the
 // code of the first active lane are counted by a ballot and added once, twice over (the hot code is missed both times with
 // probability 0.09 at 70 % zeros), and only what is left goes lane by lane.
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 #include "select_core.h"
 
@@ -186,11 +186,7 @@ sel_hist(const void *__restrict__ x, const unsigned char *__restrict__ mask, Sel
 // exclusive prefix of x over the threads of the block, and the block's total; every thread of the block calls it
 __device__ __forceinline__ unsigned sel_block_scan(unsigned x, unsigned *red, unsigned &total) {
     const int lane = threadIdx.x & (NRT_WAVE - 1), wave = threadIdx.x / NRT_WAVE;
-    unsigned incl = x;
-    for (int off = 1; off < NRT_WAVE; off <<= 1) {
-        const unsigned y = __shfl_up(incl, off, NRT_WAVE);
-        if (lane >= off) incl += y;
-    }
+    const unsigned incl = nrt_wave_scan_incl(x, lane, nrt_op_sum());
     __syncthreads();
     if (lane == NRT_WAVE - 1) red[wave] = incl;
     __syncthreads();

@@ -35,7 +35,7 @@
 //
 // No atomics, no host synchronisation (every call captures into a graph); all sums have a fixed partition and order: run-to-run
 // bit-identical.  Partials travel as (hi, lo) float pairs (a float64 sum to 48 bits), so the workspace needs 4-byte alignment only.
-#include "nrt_common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 
@@ -74,17 +74,6 @@ __device__ __forceinline__ void split_store(float *p, double s) {
     p[1] = (float)(s - (double)hi);
 }
 __device__ __forceinline__ double split_load(const float *p) { return (double)p[0] + (double)p[1]; }
-
-// the block's sum of one double per thread, in a fixed order (lanes by xor shuffles, waves in wave order); valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int off = 1; off < NRT_WAVE; off <<= 1) v += __shfl_xor(v, off, NRT_WAVE);
-    __syncthreads();
-    if ((threadIdx.x & (NRT_WAVE - 1)) == 0) red[threadIdx.x / NRT_WAVE] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int w = 1; w < kThreads / NRT_WAVE; ++w) s += red[w];
-    return s;
-}
 
 // the epilogue's arithmetic, one rounding per operation (the library is built with -ffp-contract=off; the helpers say so again)
 struct NccStats { float uI, uJ, c0, vI0, vJ0, cross, Ivar, Jvar; };
@@ -273,7 +262,7 @@ ncc_box(const float *__restrict__ I, const float *__restrict__ J, NccGeom g, Ncc
         }
     }
     if (MODE == kFwd && io.part) {
-        const double s = block_sum((double)acc, red);
+        const double s = nrt_block_sum<kThreads / NRT_WAVE>((double)acc, red);
         if (tid == 0) split_store(io.part + 2LL * blockIdx.x, s);
     }
 }
@@ -284,7 +273,7 @@ __global__ void __launch_bounds__(kThreads) ncc_finish(const float *__restrict__
     const float *p = part + 2LL * blockIdx.x * nper;
     double a = 0.0;
     for (int k = threadIdx.x; k < nper; k += kThreads) a += split_load(p + 2LL * k);
-    const double s = block_sum(a, red);
+    const double s = nrt_block_sum<kThreads / NRT_WAVE>(a, red);
     if (threadIdx.x == 0) loss[blockIdx.x] = -(float)(s / (double)V);
 }
 
@@ -348,7 +337,7 @@ __global__ void __launch_bounds__(kThreads) grad_fwd(const float *__restrict__ y
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const double s = block_sum((double)acc[d], red);
+        const double s = nrt_block_sum<kThreads / NRT_WAVE>((double)acc[d], red);
         if (tid == 0) split_store(part + 2LL * ((long long)blockIdx.x * 3 + d), s);
     }
 }
@@ -361,7 +350,7 @@ __global__ void __launch_bounds__(kThreads) grad_finish(const float *__restrict_
     for (int d = 0; d < 3; ++d) {
         double a = 0.0;
         for (int k = threadIdx.x; k < g.nb; k += kThreads) a += split_load(p + 2LL * (k * 3 + d));
-        const double s = block_sum(a, red);
+        const double s = nrt_block_sum<kThreads / NRT_WAVE>(a, red);
         if (threadIdx.x == 0) tot[d] = s;
     }
     if (threadIdx.x != 0) return;

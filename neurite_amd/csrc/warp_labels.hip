@@ -45,17 +45,6 @@ inline size_t wl_ws_bytes(unsigned nblk, int L, int batch) {
     return (size_t)batch * nblk * 3 * L * sizeof(float) + 16 + (size_t)batch * ngrp * 3 * L * sizeof(double);
 }
 
-// sum over the 64 lanes in a fixed order (every lane gets the total): pairs, quads, eights and sixteens inside a row, then the rows
-__device__ __forceinline__ float wl_wave_sum(float r) {
-    r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
-    r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
-    r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x141, 0xF, 0xF, true));     // row_half_mirror
-    r += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r), 0x140, 0xF, 0xF, true));     // row_mirror
-    r += __shfl_xor(r, 16, NRT_WAVE);
-    r += __shfl_xor(r, 32, NRT_WAVE);
-    return r;
-}
-
 // grid (nrt_xcd_grid(nblk), batch); dynamic LDS WL_WAVES * 3 L floats; part [batch][nblk][3][L]
 template <int MODE, bool STORE>
 __global__ __launch_bounds__(WL_BLOCK) void warp_labels_fwd(InterpArgs a, const int *__restrict__ fixed, float *__restrict__ part, int L,
@@ -82,7 +71,7 @@ __global__ __launch_bounds__(WL_BLOCK) void warp_labels_fwd(InterpArgs a, const 
     float acc_pp = 0.0f, acc_tp = 0.0f;
     auto flush = [&]() {
         if ((unsigned)cur < (unsigned)L) {
-            const float pp = wl_wave_sum(acc_pp), tp = wl_wave_sum(acc_tp);
+            const float pp = nrt_dpp_wave_sum(acc_pp), tp = nrt_dpp_wave_sum(acc_tp);
             if (lane == 0) {
                 tab[cur] += tp;
                 tab[2 * L + cur] += pp;
@@ -202,8 +191,8 @@ __global__ __launch_bounds__(WL_BLOCK) void warp_labels_fwd(InterpArgs a, const 
                     sl[o] = h ? -1 : sl[o];
                     pend = h ? (pend & ~(1u << o)) : pend;
                 }
-                const float pp = wl_wave_sum(nrt_mul(pl, pl));
-                const float tp = wl_wave_sum(fl == l ? pl : 0.0f);
+                const float pp = nrt_dpp_wave_sum(nrt_mul(pl, pl));
+                const float tp = nrt_dpp_wave_sum(fl == l ? pl : 0.0f);
                 if (lane == k) { kl = l; kpp = pp; ktp = tp; }
                 if (++k == NRT_WAVE) {                                        // 64 distinct ids so far: add them and start over
                     if (kl >= 0) { tab[kl] += ktp; tab[2 * L + kl] += kpp; }

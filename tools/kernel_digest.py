@@ -3,15 +3,20 @@
     hipcc <build.FLAGS> --cuda-device-only -S neurite_amd/csrc/fused.hip -o fused.s
     python tools/kernel_digest.py fused.s > fused_kernels.txt
     python tools/kernel_digest.py --diff parent_kernels.txt fused_kernels.txt
+    python tools/kernel_digest.py --tree CHECKOUT > tree_kernels.txt     # every csrc/*.hip of that checkout, names as `stem:kernel`
 
 One line per kernel (demangled, sorted): VGPRs, SGPRs, spilled VGPRs, scratch bytes, LDS bytes, the occupancy the compiler reports
 (waves per SIMD), instruction count and a hash of the instruction stream with the local labels renumbered, so that an untouched
 kernel keeps its hash when its neighbours in the file change.  --diff lists the kernels whose line differs between two tables.
 """
 import hashlib
+import importlib.util
+import os
 import re
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 FIELDS = ('vgpr', 'sgpr', 'spill', 'scratch', 'lds', 'occ', 'n')
 LINE = re.compile(r'(.*?)\s+v(\d+)\s+s(\d+)\s+spill(\d+)\s+scr(\d+)\s+lds(\d+)\s+occ(\d+)\s+n(\d+)\s+(\w+)$')
@@ -71,9 +76,26 @@ def diff(pa, pb):
     print('%d kernels in both, %d differ' % (len(set(a) & set(b)), len(moved)))
 
 
+def tree(root):
+    """the table of every translation unit of the checkout at `root`, each kernel prefixed by its file stem"""
+    spec = importlib.util.spec_from_file_location('nrt_tree_build', os.path.join(root, 'neurite_amd', 'build.py'))    # not the package
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    hipcc = os.environ.get('HIPCC', 'hipcc')
+
+    def one(src, tmp):
+        out = os.path.join(tmp, os.path.basename(src)[:-4] + '.s')
+        subprocess.run([hipcc] + build.FLAGS + ['--cuda-device-only', '-S', src, '-o', out], check=True)
+        return ['%s:%s' % (os.path.basename(src)[:-4], row) for row in digest(out)]
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(16) as pool:
+        return sorted(row for rows in pool.map(lambda s: one(s, tmp), build.sources()) for row in rows)
+
+
 if __name__ == '__main__':
     if len(sys.argv) == 4 and sys.argv[1] == '--diff':
         diff(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 3 and sys.argv[1] == '--tree':
+        print('\n'.join(tree(os.path.abspath(sys.argv[2]))))
     elif len(sys.argv) == 2:
         print('\n'.join(digest(sys.argv[1])))
     else:

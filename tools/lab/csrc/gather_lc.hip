@@ -525,9 +525,9 @@ __global__ __launch_bounds__(384, 3) void gather_lc(LcK a) {
                        spp = {spp_l[0], spp_l[1], spp_h[0], spp_h[1]};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    stp[c] = wave_xor_add(stp[c], 8);
-                    stt[c] = wave_xor_add(stt[c], 8);
-                    spp[c] = wave_xor_add(spp[c], 8);
+                    stp[c] = nrt_wave_sum_from(stp[c], 8);
+                    stt[c] = nrt_wave_sum_from(stt[c], 8);
+                    spp[c] = nrt_wave_sum_from(spp[c], 8);
                 }
                 const unsigned long long prow_g = ((unsigned long long)b * per_batch + prow) * 4ull + bw;    // four partial rows per task
                 if (l < 8) {
