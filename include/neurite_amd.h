@@ -337,7 +337,7 @@ int nrt_fuse_labels_i32(const int32_t *atlases, const float *loc, const float *w
  * Label-weighted categorical cross-entropy
  * replaces: neurite/tf/metrics.py:640-650 + tf.keras.losses.CategoricalCrossentropy
  * ------------------------------------------------------------------------------------------ */
-typedef enum { NRT_DT_F32 = 0, NRT_DT_BF16 = 1, NRT_DT_F16 = 2, NRT_DT_F64 = 3, NRT_DT_I32 = 4 } nrt_dtype;
+typedef enum { NRT_DT_F32 = 0, NRT_DT_BF16 = 1, NRT_DT_F16 = 2, NRT_DT_F64 = 3, NRT_DT_I32 = 4, NRT_DT_U8 = 5 } nrt_dtype;
 
 size_t nrt_wcce_workspace_bytes(long long nvox_total, int channels);
 
@@ -1263,6 +1263,44 @@ int nrt_label_stats(const int *ids, const int *labels, int nlabels, const void *
 size_t nrt_label_confusion_workspace_bytes(int batch, long long voxels, int nlabels);
 int nrt_label_confusion_i32(const int *a, const int *b, const int *labels, int nlabels, int batch, long long voxels, long long *counts,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Binary morphology, box minimum / maximum filters and box rank filters of 2-D and 3-D volumes (csrc/morph.hip, csrc/morph_core.h;
+ * DESIGN 4.6o): scipy.ndimage.binary_erosion / binary_dilation, minimum_filter / maximum_filter (grey erosion / dilation by a flat
+ * box) and rank_filter / median_filter / percentile_filter without a copy to the host.  Exact integer and order-statistic results.
+ * Common to the three: x and out [batch, *shape], `shape` holds nd extents (2 or 3), out is not x.
+ *   nrt_binary_morph   x stored as `dtype` (NRT_DT_U8: one byte per voxel, also a bool tensor; NRT_DT_I32; NRT_DT_F32); a voxel is set
+ *                 where x != 0 (read in the kernel).  out: one byte per voxel, 0 or 1.  `structure`: the 3 x 3 (x 3) structuring
+ *                 element as 27 bits, bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) its entry at the offset (dz, dy, dx); with nd = 2 only
+ *                 the plane dz = 0 (bits 9 .. 17) may be set.  Any structure is taken: asymmetric, without its centre, empty.
+ *                 dilate 0: out[p] = AND over the set entries o of m[p + o] (erosion); dilate 1: out[p] = OR of m[p - o].  Every voxel
+ *                 outside the volume holds border_value (0 or 1).  `iterations` >= 1 single steps are composed.  One launch runs up to
+ *                 4 steps on bit-packed rows in LDS; more steps are further launches through the workspace
+ *                 (nrt_binary_morph_workspace_bytes: one byte per voxel above 4 iterations, else 0).  The last extent may be up to 1024.
+ *   nrt_minmax_filter  x and out stored as `dtype` (NRT_DT_F32 or NRT_DT_I32).  size [nd]: the box, every entry odd and 1 .. 31.
+ *                 want_max 0: the minimum over the box, 1: the maximum; one pass per axis whose size is above 1.  The workspace
+ *                 (nrt_minmax_filter_workspace_bytes: 4 bytes per voxel when two or more sizes are above 1) needs 4-byte alignment.
+ *   nrt_rank_filter    x and out as for nrt_minmax_filter.  size [nd]: the box, every entry odd, at most 27 samples in all.  out = the
+ *                 rank-th smallest (0 <= rank < samples) of the samples of the box, compared by value.
+ *   mode (both filters): how an index outside [0, n) is read.  0 reflect (d c b a | a b c d | d c b a), 1 mirror (d c b | a b c d |
+ *                 c b a), 2 nearest (a a a | a b c d | d d d), 3 constant (cval, converted to `dtype` by truncation); the fold holds
+ *                 for a window wider than the axis.  A window that holds a NaN has an unspecified result; +-inf and both zeros are
+ *                 ordinary values (-0.0 == 0.0, either may be returned).
+ * No atomics, no workgroup waits for another, no host synchronisation (the calls capture into a graph), no allocation; bit-identical
+ * run to run.  Checked before any launch, in this order: NRT_ERR_INVALID_ARG for a NULL x, out, shape or size, an unknown dtype,
+ * batch < 1, nd outside {2, 3}, an extent < 1, a structure beyond its bits, iterations < 1, a border_value / dilate / want_max that is
+ * neither 0 nor 1, an even or non-positive size, an unknown mode, a NaN cval (or one that int32 does not hold, for NRT_DT_I32), a rank
+ * outside the box; NRT_ERR_UNSUPPORTED for a size above 31 (27 samples for the rank filter), batch > 65535, batch * voxels >= 2^31
+ * (32-bit indexing), a last extent above 1024 and, with nd = 3, a first extent above 524280 (binary); last, NRT_ERR_WORKSPACE for a missing, misaligned or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nrt_binary_morph_workspace_bytes(int batch, const int shape[], int nd, int iterations);
+int nrt_binary_morph(const void *x, int dtype, int batch, const int shape[], int nd, int structure, int iterations, int border_value,
+                     int dilate, void *out, void *workspace, size_t workspace_bytes, void *stream);
+size_t nrt_minmax_filter_workspace_bytes(int batch, const int shape[], int nd, const int size[]);
+int nrt_minmax_filter(const void *x, int dtype, int batch, const int shape[], int nd, const int size[], int mode, double cval,
+                      int want_max, void *out, void *workspace, size_t workspace_bytes, void *stream);
+int nrt_rank_filter(const void *x, int dtype, int batch, const int shape[], int nd, const int size[], int rank, int mode, double cval,
+                    void *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ NRT_OK = 0
 NRT_ERR_INVALID_ARG, NRT_ERR_UNSUPPORTED, NRT_ERR_LAUNCH, NRT_ERR_WORKSPACE = -1, -2, -3, -4
 LOC_ABSOLUTE, LOC_SHIFT, LOC_LINSPACE = 0, 1, 2
 INTERP_LINEAR, INTERP_NEAREST = 0, 1
-DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32 = 0, 1, 2, 3, 4
+DT_F32, DT_BF16, DT_F16, DT_F64, DT_I32, DT_U8 = 0, 1, 2, 3, 4, 5
 SEG_WANT_DICE, SEG_WANT_CCE = 1, 2
 EDT_SURFACE, EDT_INVERT, EDT_SIGNED, EDT_SQUARED, EDT_ANY_OF = 1, 2, 4, 8, 16
 CCL_LARGEST, CCL_MIN_SIZE, CCL_BORDER_FREE, CCL_INVERT = 1, 2, 4, 8
